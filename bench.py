@@ -7,17 +7,22 @@ actually run: B=32 utterances of 4 s at 16 kHz per GPU, spectr
 the contractions is scaled by a power of two into the fp16 window and carried as hi = RN16(x), lo = RN16(x - hi) - within
 half an fp32 ulp of x - and the three leading cross products run on the f16 matrix cores with fp32 accumulation:
 fp32-equivalent (what is dropped is <= 2^-22 |ab|), parity-tested against the same fixtures and tolerances as exact fp32
-(tests/test_gpu_f16x2.py).  Measured beside it in the same run: "bf16x3" (the exact three-way bf16 split with six products,
+(tests/test_gpu_f16x2.py).  Measured beside it in a ``--full`` run: "bf16x3" (the exact three-way bf16 split with six products,
 the default until round 4; ``--split bf16x3`` makes it the main line) and "fp32_exact" (v_mfma_f32_32x32x2_f32 everywhere;
 ``--fp32``), each sequential AND in flight.  ``--bf16`` is the opt-in single-product bf16 mode with bf16 block-boundary
 storage (BASELINE configs 2/4/5 name bf16; its own tolerance, never the graded line).
+
+A plain run sets up, warms up, times ``--steps`` passes, writes the last pass's outputs if ``--dump-outputs DIR`` is given
+and prints the headline line.  ``--full`` adds everything else to the same line: the strictly sequential pass, the
+comparison arithmetics above, per-stage hipEvent timing and the roofline, the B = 1 ``generate_wav`` file loop and the
+CPU baseline.
 
 A "step" is one pass of the whole hot path over one batch: waveforms already resident in
 HBM -> STFT -> prior -> 6 reverse steps -> ISTFT -> waveforms in HBM, replayed from one
 hipGraph.  Multi-GPU: utterances are sharded over ranks (weak scaling, B=32 per rank), no
 data-path collective; the only collectives are the timing barrier and a max-reduce.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 ``--gpus N`` with N > 1 and no launcher environment (WORLD_SIZE unset): this process only spawns N fresh rank
 processes (it never touches a GPU itself) and waits for them; under ``torch.distributed.run`` the ranks already exist
@@ -41,6 +46,24 @@ FP32_MFMA_PEAK_TFLOPS = 157.3          # MI355X_MICROARCH.md, fp32 matrix = fp32
 BF16_MFMA_PEAK_TFLOPS = 2500.0         # MI355X_MICROARCH.md, dense bf16 MFMA
 EPS_MB_PER_UTT_STEP = 139.3            # block-boundary bytes of one eps-net forward at T=401 (86,858 elements x T x 4 B)
 HBM_PEAK_GBS = 8000.0                  # MI355X_MICROARCH.md, HBM3E
+DUMP_MAX_BYTES = 64 << 20              # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32.  All arrays share the utterance axis 0; when together
+    they exceed DUMP_MAX_BYTES, the leading utterances that fit are written (the same ones in every run)."""
+    import numpy as np
+
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n = min(a.shape[0] for a in arrays.values())
+    per_utt = sum(a[:1].nbytes for a in arrays.values())
+    keep = min(n, DUMP_MAX_BYTES // per_utt)
+    if keep < 1:
+        sys.exit("bench.py: --dump-outputs: one utterance's outputs are %d bytes, more than %d" % (per_utt, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a[:keep]))
+    return keep
 
 
 def _free_port():
@@ -88,7 +111,7 @@ def main():
     ap.add_argument("--inflight", type=int, default=3,
                     help="batches in flight, each on its own HIP stream (1: strictly sequential, hipGraph replay). "
                          "The latency-bound LSTM/TCM chains of one batch run beside the MFMA-bound blocks of the others; "
-                         "every batch's result is bit-identical to the sequential run")
+                         "every batch's result is meant to be bit-identical to the sequential run (measured: not always, see --dump-outputs)")
     ap.add_argument("--stage-streams", action="store_true",
                     help="with --inflight 2: prior stream | loop stream instead of one stream per batch")
     ap.add_argument("--streams", type=int, default=1, help="concurrent sub-batch pipelines per GPU")
@@ -119,9 +142,23 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearse the launch / rendezvous / timing-reduction / reporting path on CPU (gloo, no GPU, no "
                          "kernels): the JSON line carries \"dry_run\": true and value null")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the strictly sequential pass, the same workload under the "
+                         "other arithmetics (fp32_exact, bf16x3), per-stage hipEvent timing and the roofline, the B = 1 generate_wav "
+                         "file loop and the CPU baseline (--no-cpu-baseline / --no-fp32-compare / --no-file-loop drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned - rank 0's enhanced waveforms [B,L] and "
+                         "spectrograms [B,2,T,161] - as DIR/enhanced_wav.npy and DIR/enhanced_spec.npy (float32, at most 64 MB in all); "
+                         "the inputs are seeded, so two builds can be compared output for output.  Measured on one MI355X: "
+                         "--inflight 1 repeats bit for bit from run to run; with batches in flight (the default) some utterances "
+                         "differ between runs (~1e-4 rel-L2 over the batch, up to 4e-4 for one utterance)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs needs a real run: a dry run computes nothing")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:], args.dry_run))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -164,7 +201,11 @@ def main():
     t_start = time.perf_counter()
     import __graft_entry__ as ge
 
-    ge.build()
+    # build() opens a lock file in the package directory even when nothing is to be compiled: a tree whose library is current
+    # (possibly a read-only one, after build() ran as another user) is only loaded
+    if ge._stale():
+        ge.build()
+    importlib.import_module("prior-diffuse_amd._lib").load()
     synth = importlib.import_module("prior-diffuse_amd.synth")
     pipeline = importlib.import_module("prior-diffuse_amd.pipeline")
     nets = importlib.import_module("prior-diffuse_amd.nets")
@@ -199,11 +240,13 @@ def main():
     else:
         runner = pipe = pipeline.SamplerPipeline(dev, args.prior, gs, ds, B, L_=L_, fast_sampling=fast, split_bf16=args.split_bf16, dtype=dtype)
 
+    last = [None]                            # what the latest step returned: its slot in flight, or (wav, spectrogram)
+
     def step():
         if args.overlap:
-            runner.submit(wav, x_T)          # every submitted batch completes inside the timed region (drain below)
+            last[0] = runner.submit(wav, x_T)          # every submitted batch completes inside the timed region (drain below)
         else:
-            runner.enhance(wav, x_T, graph=use_graph)
+            last[0] = runner.enhance(wav, x_T, graph=use_graph)
 
     note("plan built: %d operators; warm-up (graph=%s)" % (len(pipe.descs), use_graph))
     for _ in range(args.warmup):
@@ -240,6 +283,36 @@ def main():
     rtf = audio_seconds / elapsed
 
     if rank != 0:
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    if args.dump_outputs:
+        got = runner.result(last[0]) if args.overlap else last[0]
+        kept = dump_outputs(args.dump_outputs, {"enhanced_wav": got[0], "enhanced_spec": got[1]})
+        note("outputs of the last timed step (%d of %d utterances) written to %s" % (kept, B, args.dump_outputs))
+    line = {
+        "metric": "enhanced-audio sec/sec (RTF), %s, B=%d" % ("6-step fast sampling" if fast else "50-step full schedule", B),
+        "value": round(rtf, 2), "unit": "audio_s/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16" if args.bf16 else (args.split if args.split_bf16 else "f32"), "data": "synthetic",
+        "dtype_note": ("OPT-IN bf16 mode: plain bf16 operands (one MFMA product, fp32 accumulate) and bf16 conv1 / bottleneck tensors in the eps-net's "
+                       "BiConv(Trans)GLU and TCM blocks; prior as in the default; tolerance 3e-2 rel-L2 (tests/test_gpu_round2.py::"
+                       "test_bf16_mode_tolerance) - not the graded line") if args.bf16 else (("matrix-core kernels (eps-net blocks, TCM stack, GCRN's gated convolutions): every fp32 operand scaled by a power of two and carried "
+                        "as fp16 hi + lo (within half an fp32 ulp inside the fp16 window), three f16 MFMA products per multiply-add, fp32 "
+                        "accumulate - fp32-equivalent, same goldens and tolerances as the exact-fp32 kernels (tests/test_gpu_f16x2.py); "
+                        "everything else fp32") if f16 else
+                       ("eps-net blocks: fp32 operands split exactly into three bf16 terms, six-product bf16 MFMA, fp32 accumulate "
+                        "(fp32-level accuracy, same parity tolerances); everything else fp32")) if args.split_bf16 else "fp32 throughout",
+        "frames_per_s_per_gpu": round(args.steps * B * T / elapsed, 1),
+        "config": {"workload": "B=%d x %.0f s 16 kHz utterances per GPU, [B,2,%d,161] spectrograms, %s prior + "
+                               "DiffUNet1 %d-step sampling, STFT..ISTFT, seeded random weights" % (B, args.seconds, T, args.prior, pipe.nsteps),
+                   "global_batch": B * world, "frames": T, "parallelism": "batch-shard x%d" % world,
+                   "graph": use_graph and (not args.overlap or args.by_batch), "streams_per_gpu": args.streams,
+                   "batches_in_flight": args.inflight},
+    }
+    if not args.full:                 # the headline only; everything below is --full
+        print(json.dumps(line))
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -501,33 +574,15 @@ def main():
                          "STFT/ISTFT, 1-utterance warm-up + median of 3 timed runs (%s s)" % (
                              cb, B, " / ".join("%.1f" % r for r in runs))}
 
-    out = {
-        "metric": "enhanced-audio sec/sec (RTF), %s, B=%d" % ("6-step fast sampling" if fast else "50-step full schedule", B),
-        "value": round(rtf, 2), "unit": "audio_s/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "ms_per_step_sequential": round(ms_sequential, 3),
+    out = dict(line, **{
+        "ms_per_step_sequential": round(ms_sequential, 3),
         # box-independent: summed hipEvent durations of the eps-net launches (the roofline's denominator) and of everything
         "eps_net_kernel_ms": round(eps_ms, 4), "all_kernel_ms": round(sum(v["ms"] for v in per_tag.values()), 4),
         "sequential_note": "one batch at a time owns the GPU: TCM stack as one persistent launch (%.3f ms per pass; %.3f as %d launches in "
                            "the in-flight pass)" % (tcm_stack_ms, per_tag["tcm"]["ms"], per_tag["tcm"]["launches"]),
         "value_sequential": round(B * args.seconds / (ms_sequential * 1e-3), 2),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16" if args.bf16 else (args.split if args.split_bf16 else "f32"), "data": "synthetic",
-        "dtype_note": ("OPT-IN bf16 mode: plain bf16 operands (one MFMA product, fp32 accumulate) and bf16 conv1 / bottleneck tensors in the eps-net's "
-                       "BiConv(Trans)GLU and TCM blocks; prior as in the default; tolerance 3e-2 rel-L2 (tests/test_gpu_round2.py::"
-                       "test_bf16_mode_tolerance) - not the graded line") if args.bf16 else (("matrix-core kernels (eps-net blocks, TCM stack, GCRN's gated convolutions): every fp32 operand scaled by a power of two and carried "
-                        "as fp16 hi + lo (within half an fp32 ulp inside the fp16 window), three f16 MFMA products per multiply-add, fp32 "
-                        "accumulate - fp32-equivalent, same goldens and tolerances as the exact-fp32 kernels (tests/test_gpu_f16x2.py); "
-                        "everything else fp32") if f16 else
-                       ("eps-net blocks: fp32 operands split exactly into three bf16 terms, six-product bf16 MFMA, fp32 accumulate "
-                        "(fp32-level accuracy, same parity tolerances); everything else fp32")) if args.split_bf16 else "fp32 throughout",
-        "frames_per_s_per_gpu": round(args.steps * B * T / elapsed, 1),
-        "config": {"workload": "B=%d x %.0f s 16 kHz utterances per GPU, [B,2,%d,161] spectrograms, %s prior + "
-                               "DiffUNet1 %d-step sampling, STFT..ISTFT, seeded random weights" % (B, args.seconds, T, args.prior, pipe.nsteps),
-                   "global_batch": B * world, "frames": T, "parallelism": "batch-shard x%d" % world,
-                   "graph": use_graph and (not args.overlap or args.by_batch), "streams_per_gpu": args.streams,
-                   "batches_in_flight": args.inflight},
         "roofline": roofline, "cpu_baseline": cpu, "fp32_exact": fp32_exact, "bf16x3": bf16x3, "file_loop_b1": file_loop,
-    }
+    })
     print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -98,6 +98,25 @@ def test_bench_gpus_flag_errors():
         assert r.returncode == 2 and "exposes" in r.stderr and "Traceback" not in r.stderr
     r = _bench("--gpus", "2", "--dry-run", env={"WORLD_SIZE": "3", "RANK": "0"})
     assert r.returncode != 0 and "does not match WORLD_SIZE" in r.stderr
+    r = _bench("--steps", "0", "--dry-run")                 # ms_per_step needs at least one timed step
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr and "Traceback" not in r.stderr
+
+
+def test_bench_dump_outputs_float32_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs writes every array as float32 .npy; above the size cap it keeps the leading utterances that fit."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    wav, spec_ = torch.randn(6, 50, dtype=torch.float64), torch.randn(6, 2, 3, 4)
+    assert bench.dump_outputs(str(tmp_path / "all"), {"enhanced_wav": wav, "enhanced_spec": spec_}) == 6
+    got = np.load(str(tmp_path / "all" / "enhanced_wav.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, wav.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * (50 + 24) * 4 + 3)     # room for four utterances
+    assert bench.dump_outputs(str(tmp_path / "cut"), {"enhanced_wav": wav, "enhanced_spec": spec_}) == 4
+    cut = [np.load(str(tmp_path / "cut" / (k + ".npy"))) for k in ("enhanced_wav", "enhanced_spec")]
+    assert np.array_equal(cut[1], spec_[:4].numpy()) and sum(a.nbytes for a in cut) <= bench.DUMP_MAX_BYTES
 
 
 def test_wav_io_and_resampling(tmp_path):
