@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define PDSE_ABI_VERSION 8
+#define PDSE_ABI_VERSION 9
 
 typedef void* pdse_stream_t; /* hipStream_t */
 
@@ -756,6 +756,47 @@ typedef struct pdse_planes_desc {
   int32_t cin0, cin1, nd, pad_;
 } pdse_planes_desc;
 
+/* Objective speech-quality scores of the reference's evaluation (utils/metrics.py: SNRseg :36-55, llr :192-263, wss :266-427,
+ * fwSNRseg :58-174) for B utterance pairs at fs = 16000 (ABI 9, csrc/metrics.hip): 480-sample frames every 120 samples, 1024-point
+ * DFT (bins 0..511), LPC order 16, 25 critical bands.  Utterance b is scored over its own lens[b] samples only; the padding up to
+ * Lmax is never read.  All four measures cover frames 0 .. m-1, m = (len - 480) / 120 (the reference drops its last time-domain
+ * frame and counts its spectral frames that way).  out[b] = {SSNR, LLR, WSS, fwSNRseg}; LLR and WSS are the mean of the lowest
+ * round-half-even(0.95 m) per-frame values.  Three launches on stream s, no host synchronisation; every sum has a fixed order, so
+ * a score does not depend on scheduling, on B or on the utterance's place in the batch.
+ * lens_host is read by the call itself (validation happens before any launch and needs no device): len >= 600, len <= Lmax;
+ * a recorded plan reads it again on every run, so it must outlive the plan.  lens is the same array in device memory.
+ * tables: PDSE_METRICS_TABLE_DOUBLES float64 values built by the caller (prior-diffuse_amd/metrics.py: tables()); the spectral
+ * stage runs in float64 (csrc/metrics.hip says why), so the tables are not rounded to fp32:
+ *   OFF_WIN     [480]        0.5 (1 - cos(2 pi k / 481)), k = 1..480
+ *   OFF_BASIS   [480][1024]  cos(2 pi k j / 1024) for column j < 512, sin(2 pi k (j - 512) / 1024) from column 512 on
+ *   OFF_CRIT    [25][512]    crit_filter with its -30 dB cut
+ *   OFF_WEPS    [2][512]     float64 eps times the window's own transform (cos sums, then sin sums): what the reference's
+ *                            "+ eps" on both signals adds to every frame's spectrum
+ *   OFF_BRANGE  [25][2]      (whole numbers) first and last bin with a non-zero weight in each band (all below bin 256)
+ * frames: [4][B][Mmax] per-frame values in the order of `out` (entries m.. of a shorter utterance are not written);
+ * sorted: [2][B][Mmax] workspace.  Mmax = (Lmax - 480) / 120. */
+#define PDSE_METRICS_SSNR 0
+#define PDSE_METRICS_LLR 1
+#define PDSE_METRICS_WSS 2
+#define PDSE_METRICS_FWSNRSEG 3
+#define PDSE_METRICS_OFF_WIN 0
+#define PDSE_METRICS_OFF_BASIS 512
+#define PDSE_METRICS_OFF_CRIT (512 + 480 * 1024)
+#define PDSE_METRICS_OFF_WEPS (PDSE_METRICS_OFF_CRIT + 25 * 512)
+#define PDSE_METRICS_OFF_BRANGE (PDSE_METRICS_OFF_WEPS + 2 * 512)
+#define PDSE_METRICS_TABLE_DOUBLES (PDSE_METRICS_OFF_BRANGE + 64)
+typedef struct pdse_metrics_desc {
+  const float* clean;        /* device [B][Lmax] */
+  const float* proc;         /* device [B][Lmax]: the enhanced (or noisy) signal */
+  const int32_t* lens_host;  /* host [B] */
+  const int32_t* lens;       /* device [B] */
+  const double* tables;      /* device */
+  float* frames;             /* device [4][B][Mmax] */
+  float* sorted;             /* device [2][B][Mmax] */
+  float* out;                /* device [B][4] */
+  int32_t B, Lmax, Mmax, pad_;
+} pdse_metrics_desc;
+
 enum pdse_op_kind {
   PDSE_OP_GCONV = 0,
   PDSE_OP_TIME = 1,
@@ -785,7 +826,8 @@ enum pdse_op_kind {
   PDSE_OP_GLSTMP = 25,
   PDSE_OP_TCM2S = 26,
   PDSE_OP_DENSE = 27,
-  PDSE_OP_ROWLNB = 28
+  PDSE_OP_ROWLNB = 28,
+  PDSE_OP_METRICS = 29
 };
 
 int pdse_abi_version(void);
@@ -823,6 +865,7 @@ int pdse_bglu_planes(const pdse_bglu_desc* d, pdse_stream_t s);
 int pdse_split_planes(const pdse_planes_desc* d, pdse_stream_t s);
 int pdse_dense_layer_bf16x3(const pdse_dense_desc* d, pdse_stream_t s);
 int pdse_rowln_blocked_f32(const pdse_rowlnb_desc* d, pdse_stream_t s);
+int pdse_quality_metrics_f32(const pdse_metrics_desc* d, pdse_stream_t s);
 /* Kernel form of pdse_bglu_planes (ABI 6; process-wide, tuning only): -1 / 0 = 8 waves with the generated slot schedule
  * (the product kernel).  A library built with -DBGLU_FORMS also holds the forms that were measured and not kept
  * (profiles/r03_bglu_forms.txt, r04_bglu_forms.txt): 1 = 4 waves software-pipelined, 2 / 3 = 16 / 12 waves with strictly

@@ -373,3 +373,38 @@ def synthetic_spectrogram(batch, frames, seed=1234):
     feat = torch.randn(batch, 2, frames, F_BINS, generator=g, dtype=torch.float32)
     x_T = torch.randn(batch, 2, frames, F_BINS, generator=g, dtype=torch.float32)
     return feat, x_T
+
+
+def speechlike(batch, length, seed=1234):
+    """Deterministic non-white test signals for the quality metrics (metrics.py): seeded Gaussian noise through the
+    truncated impulse response of two AR resonators (near 500 and 1500 Hz at 16 kHz, the spectral tilt of voiced speech),
+    amplitude-modulated at a syllabic rate that differs per utterance, scaled so that the peak is 0.5.
+    Returns float32 [batch, length] (numpy)."""
+    rs = np.random.RandomState(int(seed))
+    n = np.arange(256)
+    h = 0.97 ** n * np.cos(2 * np.pi * 500.0 / 16000.0 * n) + 0.5 * 0.95 ** n * np.cos(2 * np.pi * 1500.0 / 16000.0 * n)
+    t = np.arange(length) / 16000.0
+    out = np.empty((batch, length), dtype=np.float32)
+    for b in range(batch):
+        x = np.convolve(rs.standard_normal(length + 255), h, mode="valid")
+        rate, phase = 3.0 + 0.37 * (b % 8), 0.7 * b
+        x = x * (0.15 + 0.85 * np.sin(2 * np.pi * rate * t / 2 + phase) ** 2)
+        out[b] = (0.5 * x / np.abs(x).max()).astype(np.float32)
+    return out
+
+
+def noisy_pair(length, seed, snr_db=None, silence=None):
+    """One (clean, processed) fp32 pair for the quality metrics: ``speechlike`` plus seeded white noise at ``snr_db`` dB
+    (None: processed is a copy of clean); ``silence = (start, stop)`` zeroes that span in both signals."""
+    clean = speechlike(1, length, seed)[0]
+    if snr_db is None:
+        proc = clean.copy()
+    else:
+        noise = np.random.RandomState(int(seed) + 1000).standard_normal(length)
+        c = clean.astype(np.float64)
+        gain = np.sqrt((c ** 2).mean() / ((noise ** 2).mean() * 10.0 ** (snr_db / 10.0)))
+        proc = (c + gain * noise).astype(np.float32)
+    if silence is not None:
+        clean[silence[0]:silence[1]] = 0.0
+        proc[silence[0]:silence[1]] = 0.0
+    return clean, proc

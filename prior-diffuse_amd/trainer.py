@@ -198,6 +198,31 @@ class ComplexDDPMTrainer(object):
         cut = [(n // 160) * 160 if trim_to_frames else n for n in lens]
         return [out[i, :cut[i]].clone() for i in range(B)]
 
+    def evaluate_batch(self, noisy_wavs, clean_wavs, x_T=None):
+        """The validation loop's enhancement and scoring in one call (:408-494 with utils/metrics.py: compare_complex, less
+        PESQ and STOI): ``enhance_batch(noisy_wavs, trim_to_frames=True)``, the clean references cut to the same
+        ``(frame_num - 1) * 160`` samples (utils/metrics.py:562-563), then ``metrics.quality`` on the device-resident result.
+        Returns (enhanced_list, scores): ``scores`` holds the per-utterance device tensors ``ssnr``, ``llr``, ``wss``,
+        ``fwsnrseg`` and, as compare_complex returns means, ``mean_ssnr`` ... ``mean_fwsnrseg`` (0-dim device tensors).
+        One synchronisation in total: the pass's own check (``_checked``); the scores are asynchronous."""
+        from . import metrics
+
+        clean_wavs = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in clean_wavs]
+        noisy_lens = [int(torch.as_tensor(w).numel()) for w in noisy_wavs]
+        if len(clean_wavs) != len(noisy_lens) or any(c.numel() != n for c, n in zip(clean_wavs, noisy_lens)):
+            raise ValueError("every noisy utterance needs a clean reference of its own length")
+        cut = [(n // 160) * 160 for n in noisy_lens]
+        if min(cut) < metrics.MIN_LEN:
+            raise ValueError("utterances must keep at least %d samples after trimming to frames" % metrics.MIN_LEN)
+        enhanced = self.enhance_batch(noisy_wavs, x_T=x_T, trim_to_frames=True)
+        pad = torch.nn.utils.rnn.pad_sequence
+        clean = pad([c[:n] for c, n in zip(clean_wavs, cut)], batch_first=True).to(self.device)
+        with torch.cuda.device(self.device):
+            scores = metrics.quality(clean, pad(enhanced, batch_first=True), lens=cut)
+        for k in ("ssnr", "llr", "wss", "fwsnrseg"):
+            scores["mean_" + k] = scores[k].mean()
+        return enhanced, scores
+
     # ---- A2..A7: the reference's entry point --------------------------------
     def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True):
         """Per-file B=1 enhancement of ``data_path/*.wav`` into ``args.generated_wav``
