@@ -797,6 +797,34 @@ typedef struct pdse_metrics_desc {
   int32_t B, Lmax, Mmax, pad_;
 } pdse_metrics_desc;
 
+/* Wav front end (csrc/resample.hip, additive within ABI 9): integer PCM decode, mono mix and polyphase Kaiser-windowed-sinc rate
+ * conversion of B utterances that share one sample format (width bytes per sample, ch channels, little endian, interleaved) and
+ * one rate pair, in one launch on stream s; no host synchronisation.  The arithmetic is that of prior-diffuse_amd/wavio.py
+ * (read_wav + resample), operation for operation, so out is bit-identical to the host path:
+ *   decode  fp32: i16 / 32768, float(i32) / 2147483648, (u8 - 128) / 128; two channels: (a + b) rounded to fp32, then / 2
+ *   convert out[b][n] = sum over j = -jmax .. jmax (ascending), jmax = half / up + 1, of taps[r + j up + half] * x[k_c - j] with
+ *           q = n down, k_c = q / up, r = q % up, skipping terms with |r + j up| > half or k_c - j outside [0, n_in[b]);
+ *           float64, product rounded before the add (no fused multiply-add), accumulator started at +0.0, one cast to fp32.
+ * up == down (ratio 1): decode and mix only, taps may be null.  Row b holds n_out[b] = ceil(n_in[b] up / down) samples followed by
+ * zeros up to Lmax; every element of out is written.  A row does not depend on B or on the utterance's place in the batch.
+ * pcm: the utterances' frames in one device buffer of pcm_bytes bytes; utterance b starts at byte offs[b] (any alignment) and holds
+ * n_in[b] frames; a frame that would end beyond pcm_bytes reads as zero.  n_in_host is read by the call itself (validation
+ * happens before the launch and needs no device): n_in >= 1, n_out <= Lmax; a recorded plan reads it again on every run, so it
+ * must outlive the plan.  taps: 2 half + 1 float64 values built by the caller (prior-diffuse_amd/wavio.py: taps()).
+ * A workgroup computes PDSE_RESAMPLE_BLOCK consecutive outputs from an input window staged in LDS; ratios whose window of
+ * (PDSE_RESAMPLE_BLOCK - 1) down / up + 2 jmax + 2 samples exceeds 64 KB are refused. */
+#define PDSE_RESAMPLE_BLOCK 256
+typedef struct pdse_resample_desc {
+  const uint8_t* pcm;          /* device [pcm_bytes] */
+  const int64_t* offs;         /* device [B] byte offset of every utterance in pcm */
+  const int32_t* n_in_host;    /* host [B] frames per utterance */
+  const int32_t* n_in;         /* device [B] the same array */
+  const double* taps;          /* device [2 half + 1], or NULL when up == down */
+  float* out;                  /* device [B][Lmax] */
+  int64_t pcm_bytes;
+  int32_t B, Lmax, up, down, half, width, ch, pad_;
+} pdse_resample_desc;
+
 enum pdse_op_kind {
   PDSE_OP_GCONV = 0,
   PDSE_OP_TIME = 1,
@@ -827,7 +855,8 @@ enum pdse_op_kind {
   PDSE_OP_TCM2S = 26,
   PDSE_OP_DENSE = 27,
   PDSE_OP_ROWLNB = 28,
-  PDSE_OP_METRICS = 29
+  PDSE_OP_METRICS = 29,
+  PDSE_OP_RESAMPLE = 30
 };
 
 int pdse_abi_version(void);
@@ -866,6 +895,7 @@ int pdse_split_planes(const pdse_planes_desc* d, pdse_stream_t s);
 int pdse_dense_layer_bf16x3(const pdse_dense_desc* d, pdse_stream_t s);
 int pdse_rowln_blocked_f32(const pdse_rowlnb_desc* d, pdse_stream_t s);
 int pdse_quality_metrics_f32(const pdse_metrics_desc* d, pdse_stream_t s);
+int pdse_pcm_resample_f32(const pdse_resample_desc* d, pdse_stream_t s);
 /* Kernel form of pdse_bglu_planes (ABI 6; process-wide, tuning only): -1 / 0 = 8 waves with the generated slot schedule
  * (the product kernel).  A library built with -DBGLU_FORMS also holds the forms that were measured and not kept
  * (profiles/r03_bglu_forms.txt, r04_bglu_forms.txt): 1 = 4 waves software-pipelined, 2 / 3 = 16 / 12 waves with strictly

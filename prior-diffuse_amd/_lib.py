@@ -16,7 +16,7 @@ EPI_LINEAR, EPI_GLU, EPI_BIGLU = 0, 1, 2
 EW_DIV, EW_UPDATE, EW_UPDATE_FINAL, EW_COPY, EW_ADD_MUL = 0, 1, 2, 3, 4
 (OP_GCONV, OP_TIME, OP_EW, OP_COMPAND, OP_WAVPREP, OP_OLA, OP_SIGMA, OP_LN, OP_LSTM,
  OP_ROWLN, OP_CHLN, OP_ATTN, OP_GRU, OP_GNCOMB, OP_AHAM, OP_QSAMPLE, OP_TRANSPOSE, OP_TCM, OP_CRM, OP_GCRNLAST,
- OP_MASKLOSS, OP_GLSTM, OP_TCM2, OP_BGLU, OP_PLANES, OP_GLSTMP, OP_TCM2S, OP_DENSE, OP_ROWLNB, OP_METRICS) = range(30)
+ OP_MASKLOSS, OP_GLSTM, OP_TCM2, OP_BGLU, OP_PLANES, OP_GLSTMP, OP_TCM2S, OP_DENSE, OP_ROWLNB, OP_METRICS, OP_RESAMPLE) = range(31)
 MASKLOSS_BLOCKS = 32
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -231,13 +231,22 @@ class MetricsDesc(C.Structure):
                 ("sorted", _fp), ("out", _fp), ("B", _i32), ("Lmax", _i32), ("Mmax", _i32), ("pad_", _i32)]
 
 
+class ResampleDesc(C.Structure):
+    """PCM decode, mono mix and rate conversion of B utterances (include/pdse.h: pdse_resample_desc, csrc/resample.hip)."""
+    _fields_ = [("pcm", _fp), ("offs", _fp), ("n_in_host", _fp), ("n_in", _fp), ("taps", _fp), ("out", _fp),
+                ("pcm_bytes", _i64), ("B", _i32), ("Lmax", _i32), ("up", _i32), ("down", _i32), ("half", _i32),
+                ("width", _i32), ("ch", _i32), ("pad_", _i32)]
+
+
+RESAMPLE_BLOCK = 256      # PDSE_RESAMPLE_BLOCK: outputs per workgroup
+
 METRICS_OFF_WIN, METRICS_OFF_BASIS = 0, 512
 METRICS_OFF_CRIT = METRICS_OFF_BASIS + 480 * 1024
 METRICS_OFF_WEPS = METRICS_OFF_CRIT + 25 * 512
 METRICS_OFF_BRANGE = METRICS_OFF_WEPS + 2 * 512
 METRICS_TABLE_DOUBLES = METRICS_OFF_BRANGE + 64
 
-DESC_TYPES = {OP_METRICS: MetricsDesc, OP_DENSE: DenseDesc, OP_ROWLNB: RowlnbDesc, OP_TCM2S: Tcm2sDesc, OP_GLSTMP: GlstmpDesc, OP_BGLU: BgluDesc, OP_PLANES: PlanesDesc, OP_TCM2: Tcm2Desc, OP_GLSTM: GlstmDesc, OP_MASKLOSS: MasklossDesc, OP_GCRNLAST: GcrnLastDesc, OP_CRM: CrmDesc, OP_TCM: TcmDesc, OP_TRANSPOSE: TransposeDesc, OP_QSAMPLE: QsampleDesc, OP_ROWLN: RowlnDesc, OP_CHLN: ChlnDesc, OP_ATTN: AttnDesc, OP_GRU: GruDesc, OP_GNCOMB: GncombDesc,
+DESC_TYPES = {OP_RESAMPLE: ResampleDesc, OP_METRICS: MetricsDesc, OP_DENSE: DenseDesc, OP_ROWLNB: RowlnbDesc, OP_TCM2S: Tcm2sDesc, OP_GLSTMP: GlstmpDesc, OP_BGLU: BgluDesc, OP_PLANES: PlanesDesc, OP_TCM2: Tcm2Desc, OP_GLSTM: GlstmDesc, OP_MASKLOSS: MasklossDesc, OP_GCRNLAST: GcrnLastDesc, OP_CRM: CrmDesc, OP_TCM: TcmDesc, OP_TRANSPOSE: TransposeDesc, OP_QSAMPLE: QsampleDesc, OP_ROWLN: RowlnDesc, OP_CHLN: ChlnDesc, OP_ATTN: AttnDesc, OP_GRU: GruDesc, OP_GNCOMB: GncombDesc,
               OP_AHAM: AhamDesc, OP_GCONV: GconvDesc, OP_TIME: TimeDesc, OP_EW: EwDesc, OP_COMPAND: CompandDesc,
               OP_WAVPREP: WavprepDesc, OP_OLA: OlaDesc, OP_SIGMA: SigmaDesc, OP_LN: LnDesc,
               OP_LSTM: LstmDesc}
@@ -249,7 +258,7 @@ EXPORTS = [
     "pdse_ola_f32", "pdse_sigma_mask_f32", "pdse_layernorm_f32", "pdse_lstm_f32",
     "pdse_rowln_prelu_f32", "pdse_chln_f32", "pdse_attention_f32", "pdse_bigru_f32", "pdse_gn_combine_f32",
     "pdse_aham_f32", "pdse_qsample_f32", "pdse_transpose_f32", "pdse_tcm_f32", "pdse_crm_f32", "pdse_gcrnlast_f32",
-    "pdse_masked_mse_f32", "pdse_glstm_f32", "pdse_glstm_persistent_f32", "pdse_tcm2_bf16x3", "pdse_tcm2_stack_bf16x3", "pdse_bglu_planes", "pdse_split_planes", "pdse_dense_layer_bf16x3", "pdse_rowln_blocked_f32", "pdse_quality_metrics_f32", "pdse_bglu_set_form",
+    "pdse_masked_mse_f32", "pdse_glstm_f32", "pdse_glstm_persistent_f32", "pdse_tcm2_bf16x3", "pdse_tcm2_stack_bf16x3", "pdse_bglu_planes", "pdse_split_planes", "pdse_dense_layer_bf16x3", "pdse_rowln_blocked_f32", "pdse_quality_metrics_f32", "pdse_pcm_resample_f32", "pdse_bglu_set_form",
     "pdse_plan_create", "pdse_plan_add", "pdse_plan_size", "pdse_plan_set_device", "pdse_plan_clear", "pdse_plan_run",
     "pdse_plan_run_range",
     "pdse_plan_build_graph", "pdse_plan_launch_graph", "pdse_plan_time_ops", "pdse_plan_time_tag",
@@ -265,7 +274,7 @@ _DIRECT = {OP_GCONV: "pdse_gconv_f32", OP_TIME: "pdse_time_embed_f32", OP_EW: "p
            OP_MASKLOSS: "pdse_masked_mse_f32", OP_GLSTM: "pdse_glstm_f32", OP_GLSTMP: "pdse_glstm_persistent_f32",
            OP_TCM2: "pdse_tcm2_bf16x3", OP_TCM2S: "pdse_tcm2_stack_bf16x3", OP_BGLU: "pdse_bglu_planes", OP_PLANES: "pdse_split_planes",
            OP_DENSE: "pdse_dense_layer_bf16x3", OP_ROWLNB: "pdse_rowln_blocked_f32",
-           OP_METRICS: "pdse_quality_metrics_f32"}
+           OP_METRICS: "pdse_quality_metrics_f32", OP_RESAMPLE: "pdse_pcm_resample_f32"}
 
 
 class PdseError(RuntimeError):

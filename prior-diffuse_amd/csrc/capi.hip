@@ -64,6 +64,7 @@ union pdse_any_desc {
   pdse_bglu_desc bglu;
   pdse_planes_desc planes;
   pdse_metrics_desc metrics;
+  pdse_resample_desc resample;
 };
 
 struct pdse_op {
@@ -136,6 +137,7 @@ static int op_size(int kind) {
     case PDSE_OP_BGLU: return (int)sizeof(pdse_bglu_desc);
     case PDSE_OP_PLANES: return (int)sizeof(pdse_planes_desc);
     case PDSE_OP_METRICS: return (int)sizeof(pdse_metrics_desc);
+    case PDSE_OP_RESAMPLE: return (int)sizeof(pdse_resample_desc);
     default: return -1;
   }
 }
@@ -172,6 +174,7 @@ static int launch_op(const pdse_op& op, hipStream_t s) {
     case PDSE_OP_BGLU: return pdse_bglu_launch(&op.d.bglu, s);
     case PDSE_OP_PLANES: return pdse_planes_launch(&op.d.planes, s);
     case PDSE_OP_METRICS: return pdse_metrics_launch(&op.d.metrics, s);
+    case PDSE_OP_RESAMPLE: return pdse_resample_launch(&op.d.resample, s);
     default: pdse_set_error("plan: unknown op kind"); return 1;
   }
 }
@@ -212,6 +215,7 @@ int pdse_rowln_blocked_f32(const pdse_rowlnb_desc* d, pdse_stream_t s) { return 
 int pdse_bglu_planes(const pdse_bglu_desc* d, pdse_stream_t s) { return pdse_bglu_launch(d, (hipStream_t)s); }
 int pdse_split_planes(const pdse_planes_desc* d, pdse_stream_t s) { return pdse_planes_launch(d, (hipStream_t)s); }
 int pdse_quality_metrics_f32(const pdse_metrics_desc* d, pdse_stream_t s) { return pdse_metrics_launch(d, (hipStream_t)s); }
+int pdse_pcm_resample_f32(const pdse_resample_desc* d, pdse_stream_t s) { return pdse_resample_launch(d, (hipStream_t)s); }
 
 int pdse_plan_create(pdse_plan** out) {
   if (!out) {

@@ -55,5 +55,6 @@ int pdse_planes_launch(const pdse_planes_desc* d, hipStream_t s);
 int pdse_dense_launch(const pdse_dense_desc* d, hipStream_t s);     /* csrc/dense.hip */
 int pdse_rowlnb_launch(const pdse_rowlnb_desc* d, hipStream_t s);
 int pdse_metrics_launch(const pdse_metrics_desc* d, hipStream_t s);   /* csrc/metrics.hip */
+int pdse_resample_launch(const pdse_resample_desc* d, hipStream_t s);   /* csrc/resample.hip */
 int pdse_gru3_launch(const pdse_gru_desc* d, hipStream_t s);   /* csrc/gru3.hip, reached through pdse_gru_launch */
 #endif

@@ -180,6 +180,23 @@ def load_pairs(pairs):
     return groups
 
 
+def load_pairs_device(pairs, device, chunk=32):
+    """``load_pairs`` with the decoding and the 16 kHz conversion on the device (``wavdev.load``: the same samples bit for
+    bit): {length: [(clean, deg), ...]} of 1-D device tensors, ``chunk`` pairs per launch.  The rows are copies of their own
+    length: a chunk's padded [chunk, Lmax] tensors are released before the next chunk is loaded."""
+    from . import wavdev
+
+    groups = {}
+    for i in range(0, len(pairs), chunk):
+        part = pairs[i:i + chunk]
+        c, cl = wavdev.load([r for r, _ in part], device, FS)
+        p, pl = wavdev.load([g for _, g in part], device, FS)
+        for k, (r, g) in enumerate(part):
+            assert cl[k] == pl[k], "c.shape=%r, p.shape=%r (%s, %s)" % ((cl[k],), (pl[k],), r, g)
+            groups.setdefault(cl[k], []).append((c[k, :cl[k]].clone(), p[k, :pl[k]].clone()))
+    return groups
+
+
 def main(argv=None, device=None, batch=32):
     """device: default the current cuda device."""
     import torch
@@ -188,17 +205,18 @@ def main(argv=None, device=None, batch=32):
     if len(argv) != 2:
         print("usage: python -m prior_diffuse_amd.metrics REF_DIR DEG_DIR")
         return 2
-    groups = load_pairs(pair_files(argv[0], argv[1]))
-    if not groups:
+    pairs = pair_files(argv[0], argv[1])
+    if not pairs:
         print("no *.wav files in %s" % argv[0])
         return 1
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    groups = load_pairs_device(pairs, device, batch)
     rows = []
     for length in sorted(groups):
         items = groups[length]
         for i in range(0, len(items), batch):       # files of one length share a batch
-            c = torch.from_numpy(np.stack([a for a, _ in items[i:i + batch]])).to(device)
-            p = torch.from_numpy(np.stack([a for _, a in items[i:i + batch]])).to(device)
+            c = torch.stack([a for a, _ in items[i:i + batch]])
+            p = torch.stack([a for _, a in items[i:i + batch]])
             q = quality(c, p)
             rows.append(torch.stack([q["ssnr"], q["llr"], q["wss"], q["fwsnrseg"]], dim=1).double().cpu().numpy())
     pm = np.concatenate(rows).mean(axis=0)

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import nets, ops, wavio
+from . import nets, ops, wavdev, wavio
 from .params import PRIOR_SCALE_C, params as default_params
 from .pipeline import SamplerPipeline
 from .schedule import inference_schedule as _inference_schedule
@@ -232,7 +232,9 @@ class ComplexDDPMTrainer(object):
         it by ``newsigma == 0``; the draws change nothing in a file's output but advance the generator, so file k's
         x_T depends on them.  With the flag set the same number of same-shaped draws is made (and discarded) after each
         file, which keeps a seeded ``--generate`` run on the reference's generator stream file for file.
-        Files that cannot be read (unsupported encoding) are logged and skipped instead of aborting the run."""
+        Files that cannot be read (unsupported encoding) are logged and skipped instead of aborting the run.
+        A file's PCM frames are decoded, mixed to mono and converted to 16 kHz on the device (``wavdev.load``); the waveform
+        is ``wavio.read_wav``'s bit for bit, so the written files do not depend on which of the two produced it."""
         if load_pre_train and getattr(self.args, "retrain", False):
             self._load_checkpoint()
         os.makedirs(self.args.generated_wav, exist_ok=True)
@@ -240,7 +242,7 @@ class ComplexDDPMTrainer(object):
         with torch.no_grad():
             for path in sorted(glob.glob(data_path + "/*.wav")):
                 try:
-                    wav = torch.from_numpy(wavio.read_wav(path, 16000))[None]
+                    wav = wavdev.load([path], self.device, 16000)[0]            # [1, L] on the device, read_wav's bits
                 except (ValueError, EOFError, wavio.wave.Error) as e:
                     logging.warning("skipping %s: %s", path, e)
                     continue

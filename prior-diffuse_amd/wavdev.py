@@ -1,0 +1,121 @@
+"""Wav input on the device: a file's raw PCM frames go to HBM as they are, and one launch (csrc/resample.hip, include/pdse.h:
+pdse_resample_desc) decodes them, mixes two channels to mono and converts the rate to 16 kHz.  The result is bit-identical to
+``wavio.read_wav`` - the kernel repeats its arithmetic operation for operation - without the host's float64 polyphase loop in
+front of every pass (DESIGN.md 4.6 and profiles/wav_frontend_timing.txt hold the file-loop times measured on the MI355X machine).
+
+    load(paths, device)                               -> (wav [B, Lmax] fp32 device tensor, lens)
+    decode(pcm_list, channels, width, rate, device)   -> the same for callers that already hold frames
+
+Files of one call that differ in rate or format take one launch per (channels, width, rate).  What the kernel does not cover -
+more than two channels, a file without frames, a rate pair whose input window per workgroup passes the kernel's 64 KB of LDS
+(input rates above about 900 kHz) - is read with ``wavio.read_wav`` and uploaded, as before.  There is no CPU
+fallback for the kernel itself.  The tap table of a rate pair is uploaded once per device and kept; nothing else persists
+between calls."""
+import numpy as np
+
+from . import _lib as L
+from . import wavio
+
+_TAPS = {}      # (device, sr_in, sr_out) -> (uploaded table or None, up, down, half)
+
+
+def _device_taps(device, sr_in, sr_out):
+    import torch
+
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device(), int(sr_in), int(sr_out))
+    if key not in _TAPS:
+        h, up, down, half = wavio.taps(sr_in, sr_out)
+        # pageable host memory: the copy returns only when the data is on the device (see metrics._device_tables)
+        _TAPS[key] = (None if h is None else torch.from_numpy(h).to(device), up, down, half)
+    return _TAPS[key]
+
+
+def kernel_covers(channels, n_frames, rate, sr=16000):
+    """Whether csrc/resample.hip takes such a file: one or two channels, at least one frame, and an input window of one workgroup's
+    outputs ((RESAMPLE_BLOCK - 1) down / up + 2 jmax + 2 fp32 samples, include/pdse.h) within 64 KB of LDS."""
+    if channels > 2 or n_frames < 1:
+        return False
+    up, down, half = _ratio(rate, sr)
+    return up == down or 4 * ((L.RESAMPLE_BLOCK - 1) * down // up + 2 * (half // up + 1) + 2) <= 64 * 1024
+
+
+def _ratio(rate, sr, half_width=16):
+    """(up, down, half) of ``wavio.taps`` without building the table."""
+    from math import gcd
+
+    g = gcd(int(rate), int(sr))
+    up, down = int(sr) // g, int(rate) // g
+    return up, down, half_width * max(up, down)
+
+
+def decode(pcm_list, channels, width, rate, device, sr=16000):
+    """pcm_list: the interleaved little-endian PCM frames of B utterances of one format, each a uint8 array (or bytes) of whole
+    frames (``wavio.read_pcm``); channels 1 or 2, width 1, 2 or 4 bytes, every utterance at least one frame long.
+    Returns (wav, lens): wav [B, Lmax] fp32 on ``device`` with utterance b in wav[b, :lens[b]] - ``wavio.read_wav``'s samples bit
+    for bit - and zeros behind it.  Two uploads and one launch on the current stream; asynchronous."""
+    import torch
+
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.PdseError("wavdev.decode runs on the GPU only (no CPU fallback); wavio.read_wav is the host path")
+    frame = int(channels) * int(width)
+    bufs = [np.frombuffer(p, dtype=np.uint8) if isinstance(p, (bytes, bytearray, memoryview)) else
+            np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in pcm_list]
+    B = len(bufs)
+    if B < 1:
+        raise ValueError("an empty batch has nothing to decode")
+    if any(p.size % frame for p in bufs):
+        raise ValueError("pcm_list: whole frames only (%d bytes each)" % frame)
+    n_in = np.array([p.size // frame for p in bufs], dtype=np.int64)
+    if n_in.max() >= 2 ** 31:
+        raise ValueError("an utterance of 2^31 frames or more")
+    taps, up, down, half = _device_taps(device, rate, sr)
+    lens = [wavio.out_len(int(n), rate, sr) for n in n_in]
+    Lmax = max(max(lens), 1)
+    # one int64 array carries both per-utterance tables: B byte offsets, then the B frame counts as int32
+    meta = np.zeros(B + (B + 1) // 2, dtype=np.int64)
+    meta[1:B] = np.cumsum([p.size for p in bufs])[:-1]
+    n_in32 = meta[B:].view(np.int32)
+    n_in32[:B] = n_in
+    pcm = bufs[0] if B == 1 else np.concatenate(bufs)
+    if pcm.size == 0:
+        pcm = np.zeros(1, dtype=np.uint8)       # a non-null buffer; validation reports the empty utterance
+    with torch.cuda.device(device):
+        pcm_dev = torch.from_numpy(pcm if pcm.flags.writeable else pcm.copy()).to(device)
+        meta_dev = torch.from_numpy(meta).to(device)
+        out = torch.empty(B, Lmax, dtype=torch.float32, device=device)
+        d = L.ResampleDesc()
+        d.pcm, d.offs, d.n_in, d.n_in_host = pcm_dev.data_ptr(), meta_dev.data_ptr(), meta_dev.data_ptr() + 8 * B, n_in32.ctypes.data
+        d.taps, d.out = (taps.data_ptr() if taps is not None else None), out.data_ptr()
+        d.pcm_bytes, d.B, d.Lmax = int(pcm.size), B, Lmax
+        d.up, d.down, d.half, d.width, d.ch = up, down, half, int(width), int(channels)
+        L.launch(d, torch.cuda.current_stream(device).cuda_stream, device=device)
+    return out, lens
+
+
+def load(paths, device, sr=16000):
+    """Read wav files and bring them to ``sr`` mono fp32 on the device: (wav [B, Lmax], lens) with file b in wav[b, :lens[b]],
+    equal to ``wavio.read_wav(paths[b], sr)`` bit for bit, zeros behind it.  Raises what ``wavio.read_wav`` raises for a file it
+    cannot read."""
+    import torch
+
+    device = torch.device(device)
+    rows, groups = [None] * len(paths), {}
+    for i, path in enumerate(paths):
+        frames, n, ch, width, rate = wavio.read_pcm(path)
+        if not kernel_covers(ch, n, rate, sr):
+            rows[i] = torch.from_numpy(wavio.read_wav(path, sr)).to(device)      # the host path, unchanged
+        else:
+            groups.setdefault((ch, width, rate), []).append((i, frames))
+    if len(groups) == 1 and all(r is None for r in rows):                        # the common case: one launch is the result
+        (ch, width, rate), items = next(iter(groups.items()))
+        return decode([f for _, f in items], ch, width, rate, device, sr)
+    for (ch, width, rate), items in groups.items():
+        wav, lens = decode([f for _, f in items], ch, width, rate, device, sr)
+        for (i, _), row, n in zip(items, wav, lens):
+            rows[i] = row[:n]
+    lens = [int(r.numel()) for r in rows]
+    out = torch.zeros(len(rows), max(lens + [0]), dtype=torch.float32, device=device)
+    for i, r in enumerate(rows):
+        out[i, :lens[i]] = r
+    return out, lens

@@ -65,3 +65,41 @@ def write_wav(path, x, sr=16000):
         f.setsampwidth(2)
         f.setframerate(sr)
         f.writeframes(pcm.tobytes())
+
+
+# ---- the pieces of read_wav / resample the device front end needs (prior-diffuse_amd/wavdev.py, csrc/resample.hip) -------------
+def taps(sr_in, sr_out, half_width=16, beta=8.6):
+    """(h, up, down, half): the float64 tap table ``resample`` builds for this rate pair (the same expression, so the same
+    bits), 2 * half + 1 values, and its polyphase constants.  ``up == down`` (equal rates) needs no filter; h is then None."""
+    g = gcd(int(sr_in), int(sr_out))
+    up, down = int(sr_out) // g, int(sr_in) // g
+    m = max(up, down)
+    half = half_width * m
+    if up == down:
+        return None, up, down, half
+    n_h = np.arange(-half, half + 1)
+    h = np.sinc(n_h / m) / m * np.kaiser(2 * half + 1, beta) * up
+    return h, up, down, half
+
+
+def out_len(n, sr_in, sr_out):
+    """Samples ``resample`` returns for n input samples."""
+    if sr_in == sr_out or n == 0:
+        return int(n)
+    g = gcd(int(sr_in), int(sr_out))
+    up, down = int(sr_out) // g, int(sr_in) // g
+    return int(np.ceil(n * up / down))
+
+
+def read_pcm(path):
+    """(frames, n_frames, channels, width, rate): the file's interleaved little-endian PCM frames as a uint8 array, undecoded.
+    Goes through the ``wave`` module like ``read_wav`` and raises what it raises for the same files: wave.Error / EOFError for
+    headers ``wave`` rejects, ValueError for a sample width other than 1, 2 or 4 bytes or a data chunk that ends inside a frame."""
+    with wave.open(path, "rb") as f:
+        n, ch, width, rate = f.getnframes(), f.getnchannels(), f.getsampwidth(), f.getframerate()
+        raw = f.readframes(n)
+    if width not in (1, 2, 4):
+        raise ValueError("unsupported sample width %d in %s" % (width, path))
+    if len(raw) % (ch * width):
+        raise ValueError("%s: the data chunk ends inside a frame (%d bytes, %d per frame)" % (path, len(raw), ch * width))
+    return np.frombuffer(raw, dtype=np.uint8), len(raw) // (ch * width), ch, width, rate
