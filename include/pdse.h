@@ -662,11 +662,12 @@ typedef struct pdse_aham_desc {
  *   Encoder stage 1 (x0.ptr != NULL): K = 10 taps x 4 channels of the fp32 inputs (x, x_init), split in the kernel,
  *   three blocks (packing.pack_s3_gather(.., 3, 16)).
  * ------------------------------------------------------------------------------------------------------------- */
-/* f16x2 planes (np == 2) hold (value * 2^PDSE_F16_ACT_EXP) as hi = RN16(.), lo = RN16(. - hi): exact to half an fp32 ulp for
- * 2^-6 <= |value| < 4094 (lo a normal fp16); below, the absolute error is <= 2^-29 (under the fp32 ulp of any value >= 2^-5 it is
+/* f16x2 planes (np == 2) hold (value * 2^PDSE_F16_ACT_EXP) as hi = RN16(.), lo = RN16(. - hi): |value - hi - lo| <= 2^-23 |value|
+ * (relative; proven from the two roundings) for 2^-6 <= |value| < 4094 (lo a normal fp16); below, the absolute error is <= 2^-29 (under the fp32 ulp of any value >= 2^-5 it is
  * added to); a value beyond +-4094 becomes an INFINITY in its planes (IEEE conversion, no saturation), so it surfaces as a
  * non-finite result (SamplerPipeline.check() raises; the drop-in trainer then re-runs that geometry on the three-plane bf16 split)
- * instead of a silently clipped one.  Nominal activations of the path (unit-RMS spectrograms): |value| <= ~12 (tools/act_range.py). */
+ * instead of a silently clipped one; the bottom edge is silent, and the range audit (pdse_range_desc, SamplerPipeline(audit=True))
+ * is what sees it.  Nominal activations of the path (unit-RMS spectrograms): |value| <= ~12 (tools/act_range.py). */
 #define PDSE_F16_ACT_EXP 4
 
 typedef struct pdse_bglu_desc {
@@ -825,6 +826,43 @@ typedef struct pdse_resample_desc {
   int32_t B, Lmax, up, down, half, width, ch, pad_;
 } pdse_resample_desc;
 
+/* Range audit of the f16x2 window (csrc/range.hip, additive within ABI 9): per-tensor histograms of the fp16 binade of
+ * |x| * 2^exp for a table of tensors, one launch, tensor index on blockIdx.y; no host synchronisation.  PDSE_RANGE_BINS = 32
+ * counters per tensor:
+ *   bin 0: zero;  bin 1: non-zero below 2^-14 (hi an fp16 subnormal);  bin E + 16: 2^E <= |x| 2^exp < 2^(E+1) for E = -14 .. 14;
+ *   bin 31: 2^15 and above, infinities, NaN.
+ * An f16x2 operand is fp32-equivalent (|x - hi - lo| <= 2^-23 |x|) while hi's exponent is >= -2 (lo a normal fp16), i.e. from
+ * bin 14 up; bin 31 is where hi leaves the fp16 range.
+ * PDSE_RANGE_F32: ptr is a contiguous fp32 tensor of n elements in true scale (the inputs csrc/gconv4.hip korder 5,
+ *   csrc/dense.hip and encoder stage 1 scale by 2^PDSE_F16_ACT_EXP and split in registers): binned by the fp32 exponent field
+ *   plus exp - integer arithmetic, no multiply.
+ * PDSE_RANGE_F16HI: ptr is the first logical 8-element vector of the hi plane of a two-plane tensor as the kernels store it
+ *   (hp, hs); the row walks the box n0 x n1 x n2 x n3 of such vectors: vector (i0, i1, i2, i3) starts at uint16 index
+ *   i0 s0 + i1 s1 + i2 s2 + 8 pos(i3 + i0_bin) with pos(i) = i, or (i & 1) par_half + (i >> 1) for a parity-split tensor
+ *   (pdse_bglu_desc.hp_par).  n = 8 n0 n1 n2 n3, exp = 0 (the planes are scaled already).  Margins, pad frames, the lo plane
+ *   and the dump item lie outside the box and are not counted.
+ * mode 0 clears all out_rows rows of out (rows may be NULL); mode 1 adds the rows' histograms to out[row.out_row][32].
+ * The table lives on the device only.  pdse_range_hist and pdse_plan_add read it back once (a synchronous copy: not inside a
+ *   stream capture) and validate every row before anything is launched or recorded - null pointers, unknown kind, n < 0,
+ *   out_row, alignment; a recorded plan launches without further host work, and the kernel skips a row it cannot make sense of
+ *   (a table overwritten after it was recorded), it never follows it.  blocks: workgroups per row (grid x). */
+#define PDSE_RANGE_BINS 32
+#define PDSE_RANGE_F32 0
+#define PDSE_RANGE_F16HI 1
+typedef struct pdse_range_row {
+  const void* ptr;
+  int64_t n;                   /* logical elements */
+  int64_t s0, s1, s2;          /* F16HI: strides of the three outer indices, uint16 units, multiples of 8 */
+  int32_t n0, n1, n2, n3;      /* F16HI: extent of the box of 8-element vectors */
+  int32_t i0, par_half;        /* F16HI: first logical index on the innermost axis; parity split (0: none) */
+  int32_t kind, exp, out_row, pad_;
+} pdse_range_row;
+typedef struct pdse_range_desc {
+  const pdse_range_row* rows;        /* device [nrows] */
+  uint32_t* out;                     /* device [out_rows][PDSE_RANGE_BINS] */
+  int32_t nrows, out_rows, mode, blocks;
+} pdse_range_desc;
+
 enum pdse_op_kind {
   PDSE_OP_GCONV = 0,
   PDSE_OP_TIME = 1,
@@ -856,7 +894,8 @@ enum pdse_op_kind {
   PDSE_OP_DENSE = 27,
   PDSE_OP_ROWLNB = 28,
   PDSE_OP_METRICS = 29,
-  PDSE_OP_RESAMPLE = 30
+  PDSE_OP_RESAMPLE = 30,
+  PDSE_OP_RANGE = 31
 };
 
 int pdse_abi_version(void);
@@ -896,6 +935,7 @@ int pdse_dense_layer_bf16x3(const pdse_dense_desc* d, pdse_stream_t s);
 int pdse_rowln_blocked_f32(const pdse_rowlnb_desc* d, pdse_stream_t s);
 int pdse_quality_metrics_f32(const pdse_metrics_desc* d, pdse_stream_t s);
 int pdse_pcm_resample_f32(const pdse_resample_desc* d, pdse_stream_t s);
+int pdse_range_hist(const pdse_range_desc* d, pdse_stream_t s);
 /* Kernel form of pdse_bglu_planes (ABI 6; process-wide, tuning only): -1 / 0 = 8 waves with the generated slot schedule
  * (the product kernel).  A library built with -DBGLU_FORMS also holds the forms that were measured and not kept
  * (profiles/r03_bglu_forms.txt, r04_bglu_forms.txt): 1 = 4 waves software-pipelined, 2 / 3 = 16 / 12 waves with strictly

@@ -16,7 +16,7 @@ EPI_LINEAR, EPI_GLU, EPI_BIGLU = 0, 1, 2
 EW_DIV, EW_UPDATE, EW_UPDATE_FINAL, EW_COPY, EW_ADD_MUL = 0, 1, 2, 3, 4
 (OP_GCONV, OP_TIME, OP_EW, OP_COMPAND, OP_WAVPREP, OP_OLA, OP_SIGMA, OP_LN, OP_LSTM,
  OP_ROWLN, OP_CHLN, OP_ATTN, OP_GRU, OP_GNCOMB, OP_AHAM, OP_QSAMPLE, OP_TRANSPOSE, OP_TCM, OP_CRM, OP_GCRNLAST,
- OP_MASKLOSS, OP_GLSTM, OP_TCM2, OP_BGLU, OP_PLANES, OP_GLSTMP, OP_TCM2S, OP_DENSE, OP_ROWLNB, OP_METRICS, OP_RESAMPLE) = range(31)
+ OP_MASKLOSS, OP_GLSTM, OP_TCM2, OP_BGLU, OP_PLANES, OP_GLSTMP, OP_TCM2S, OP_DENSE, OP_ROWLNB, OP_METRICS, OP_RESAMPLE, OP_RANGE) = range(32)
 MASKLOSS_BLOCKS = 32
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -238,6 +238,29 @@ class ResampleDesc(C.Structure):
                 ("width", _i32), ("ch", _i32), ("pad_", _i32)]
 
 
+class RangeRow(C.Structure):
+    """One tensor of a range audit (include/pdse.h: pdse_range_row)."""
+    _fields_ = [("ptr", _fp), ("n", _i64), ("s0", _i64), ("s1", _i64), ("s2", _i64),
+                ("n0", _i32), ("n1", _i32), ("n2", _i32), ("n3", _i32), ("i0", _i32), ("par_half", _i32),
+                ("kind", _i32), ("exp", _i32), ("out_row", _i32), ("pad_", _i32)]
+
+
+class RangeDesc(C.Structure):
+    """Binade histograms of a table of tensors (include/pdse.h: pdse_range_desc, csrc/range.hip)."""
+    _fields_ = [("rows", _fp), ("out", _fp),
+                ("nrows", _i32), ("out_rows", _i32), ("mode", _i32), ("blocks", _i32)]
+
+
+RANGE_BINS = 32            # PDSE_RANGE_BINS
+RANGE_F32, RANGE_F16HI = 0, 1
+RANGE_CLEAR, RANGE_ACCUMULATE = 0, 1
+# The bin map of csrc/range.hip, decided there once: RANGE_BINADE[bin] is the exponent E of the bin's lower edge 2^E in scaled
+# units.  Bin 0 counts zeros (None); bin 1 everything non-zero below 2^-14 (-inf: hi is an fp16 subnormal); bins 2 .. 30 one
+# normal fp16 binade each, E = -14 .. 14; bin 31 starts at 2^15 and also takes infinities and NaN.
+RANGE_BINADE = (None, float("-inf")) + tuple(range(-14, 15)) + (15,)
+RANGE_BIN_FULL = RANGE_BINADE.index(-2)      # first bin whose elements are carried at full precision (lo a normal fp16)
+RANGE_BIN_TOP = RANGE_BINS - 1               # hi leaves the fp16 range
+
 RESAMPLE_BLOCK = 256      # PDSE_RESAMPLE_BLOCK: outputs per workgroup
 
 METRICS_OFF_WIN, METRICS_OFF_BASIS = 0, 512
@@ -246,7 +269,7 @@ METRICS_OFF_WEPS = METRICS_OFF_CRIT + 25 * 512
 METRICS_OFF_BRANGE = METRICS_OFF_WEPS + 2 * 512
 METRICS_TABLE_DOUBLES = METRICS_OFF_BRANGE + 64
 
-DESC_TYPES = {OP_RESAMPLE: ResampleDesc, OP_METRICS: MetricsDesc, OP_DENSE: DenseDesc, OP_ROWLNB: RowlnbDesc, OP_TCM2S: Tcm2sDesc, OP_GLSTMP: GlstmpDesc, OP_BGLU: BgluDesc, OP_PLANES: PlanesDesc, OP_TCM2: Tcm2Desc, OP_GLSTM: GlstmDesc, OP_MASKLOSS: MasklossDesc, OP_GCRNLAST: GcrnLastDesc, OP_CRM: CrmDesc, OP_TCM: TcmDesc, OP_TRANSPOSE: TransposeDesc, OP_QSAMPLE: QsampleDesc, OP_ROWLN: RowlnDesc, OP_CHLN: ChlnDesc, OP_ATTN: AttnDesc, OP_GRU: GruDesc, OP_GNCOMB: GncombDesc,
+DESC_TYPES = {OP_RANGE: RangeDesc, OP_RESAMPLE: ResampleDesc, OP_METRICS: MetricsDesc, OP_DENSE: DenseDesc, OP_ROWLNB: RowlnbDesc, OP_TCM2S: Tcm2sDesc, OP_GLSTMP: GlstmpDesc, OP_BGLU: BgluDesc, OP_PLANES: PlanesDesc, OP_TCM2: Tcm2Desc, OP_GLSTM: GlstmDesc, OP_MASKLOSS: MasklossDesc, OP_GCRNLAST: GcrnLastDesc, OP_CRM: CrmDesc, OP_TCM: TcmDesc, OP_TRANSPOSE: TransposeDesc, OP_QSAMPLE: QsampleDesc, OP_ROWLN: RowlnDesc, OP_CHLN: ChlnDesc, OP_ATTN: AttnDesc, OP_GRU: GruDesc, OP_GNCOMB: GncombDesc,
               OP_AHAM: AhamDesc, OP_GCONV: GconvDesc, OP_TIME: TimeDesc, OP_EW: EwDesc, OP_COMPAND: CompandDesc,
               OP_WAVPREP: WavprepDesc, OP_OLA: OlaDesc, OP_SIGMA: SigmaDesc, OP_LN: LnDesc,
               OP_LSTM: LstmDesc}
@@ -258,7 +281,7 @@ EXPORTS = [
     "pdse_ola_f32", "pdse_sigma_mask_f32", "pdse_layernorm_f32", "pdse_lstm_f32",
     "pdse_rowln_prelu_f32", "pdse_chln_f32", "pdse_attention_f32", "pdse_bigru_f32", "pdse_gn_combine_f32",
     "pdse_aham_f32", "pdse_qsample_f32", "pdse_transpose_f32", "pdse_tcm_f32", "pdse_crm_f32", "pdse_gcrnlast_f32",
-    "pdse_masked_mse_f32", "pdse_glstm_f32", "pdse_glstm_persistent_f32", "pdse_tcm2_bf16x3", "pdse_tcm2_stack_bf16x3", "pdse_bglu_planes", "pdse_split_planes", "pdse_dense_layer_bf16x3", "pdse_rowln_blocked_f32", "pdse_quality_metrics_f32", "pdse_pcm_resample_f32", "pdse_bglu_set_form",
+    "pdse_masked_mse_f32", "pdse_glstm_f32", "pdse_glstm_persistent_f32", "pdse_tcm2_bf16x3", "pdse_tcm2_stack_bf16x3", "pdse_bglu_planes", "pdse_split_planes", "pdse_dense_layer_bf16x3", "pdse_rowln_blocked_f32", "pdse_quality_metrics_f32", "pdse_pcm_resample_f32", "pdse_range_hist", "pdse_bglu_set_form",
     "pdse_plan_create", "pdse_plan_add", "pdse_plan_size", "pdse_plan_set_device", "pdse_plan_clear", "pdse_plan_run",
     "pdse_plan_run_range",
     "pdse_plan_build_graph", "pdse_plan_launch_graph", "pdse_plan_time_ops", "pdse_plan_time_tag",
@@ -274,7 +297,7 @@ _DIRECT = {OP_GCONV: "pdse_gconv_f32", OP_TIME: "pdse_time_embed_f32", OP_EW: "p
            OP_MASKLOSS: "pdse_masked_mse_f32", OP_GLSTM: "pdse_glstm_f32", OP_GLSTMP: "pdse_glstm_persistent_f32",
            OP_TCM2: "pdse_tcm2_bf16x3", OP_TCM2S: "pdse_tcm2_stack_bf16x3", OP_BGLU: "pdse_bglu_planes", OP_PLANES: "pdse_split_planes",
            OP_DENSE: "pdse_dense_layer_bf16x3", OP_ROWLNB: "pdse_rowln_blocked_f32",
-           OP_METRICS: "pdse_quality_metrics_f32", OP_RESAMPLE: "pdse_pcm_resample_f32"}
+           OP_METRICS: "pdse_quality_metrics_f32", OP_RESAMPLE: "pdse_pcm_resample_f32", OP_RANGE: "pdse_range_hist"}
 
 
 class PdseError(RuntimeError):
@@ -282,8 +305,10 @@ class PdseError(RuntimeError):
 
 
 class PdseRangeError(PdseError):
-    """A pass on f16x2 operands produced non-finite values: an activation left the fp16 window of include/pdse.h
-    (PDSE_F16_ACT_EXP; its planes became infinities).  The same pass on the three-plane bf16 split has no such window."""
+    """A pass on f16x2 operands left the fp16 window of include/pdse.h (PDSE_F16_ACT_EXP): an activation went beyond its top
+    (its planes became infinities: non-finite output), or - seen by the range audit only, ``SamplerPipeline(audit=True)`` -
+    a whole tensor stayed below its bottom, where no element keeps a normal lo part.  The same pass on the three-plane bf16
+    split has no such window."""
 
 
 _lib = None

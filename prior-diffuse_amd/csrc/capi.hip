@@ -65,6 +65,7 @@ union pdse_any_desc {
   pdse_planes_desc planes;
   pdse_metrics_desc metrics;
   pdse_resample_desc resample;
+  pdse_range_desc range;
 };
 
 struct pdse_op {
@@ -138,6 +139,7 @@ static int op_size(int kind) {
     case PDSE_OP_PLANES: return (int)sizeof(pdse_planes_desc);
     case PDSE_OP_METRICS: return (int)sizeof(pdse_metrics_desc);
     case PDSE_OP_RESAMPLE: return (int)sizeof(pdse_resample_desc);
+    case PDSE_OP_RANGE: return (int)sizeof(pdse_range_desc);
     default: return -1;
   }
 }
@@ -175,6 +177,7 @@ static int launch_op(const pdse_op& op, hipStream_t s) {
     case PDSE_OP_PLANES: return pdse_planes_launch(&op.d.planes, s);
     case PDSE_OP_METRICS: return pdse_metrics_launch(&op.d.metrics, s);
     case PDSE_OP_RESAMPLE: return pdse_resample_launch(&op.d.resample, s);
+    case PDSE_OP_RANGE: return pdse_range_launch(&op.d.range, s);
     default: pdse_set_error("plan: unknown op kind"); return 1;
   }
 }
@@ -216,6 +219,7 @@ int pdse_bglu_planes(const pdse_bglu_desc* d, pdse_stream_t s) { return pdse_bgl
 int pdse_split_planes(const pdse_planes_desc* d, pdse_stream_t s) { return pdse_planes_launch(d, (hipStream_t)s); }
 int pdse_quality_metrics_f32(const pdse_metrics_desc* d, pdse_stream_t s) { return pdse_metrics_launch(d, (hipStream_t)s); }
 int pdse_pcm_resample_f32(const pdse_resample_desc* d, pdse_stream_t s) { return pdse_resample_launch(d, (hipStream_t)s); }
+int pdse_range_hist(const pdse_range_desc* d, pdse_stream_t s) { return pdse_range_validate(d) ? 1 : pdse_range_launch(d, (hipStream_t)s); }
 
 int pdse_plan_create(pdse_plan** out) {
   if (!out) {
@@ -239,6 +243,10 @@ int pdse_plan_add(pdse_plan* p, int op_kind, const void* desc, int tag) {
   if (p->exec) {
     pdse_set_error("plan_add: plan already captured into a graph");
     return 1;
+  }
+  if (op_kind == PDSE_OP_RANGE) {   // the row table is device data: checked once, here, so that a run is launches only
+    device_guard dg(p);
+    if (!dg.ok || pdse_range_validate(static_cast<const pdse_range_desc*>(desc))) return 1;
   }
   pdse_op op;
   op.kind = op_kind;
@@ -515,6 +523,34 @@ int pdse_plan_load(const char* path, pdse_plan** out) {
       memcpy(base + offs[k], &v, 8);
     }
     p->ops.push_back(op);
+  }
+  // The row table of a range audit (PDSE_OP_RANGE) is device data that holds device pointers: rebase them like descriptor
+  // fields.  Every accumulate op of a plan may share one table, so a table is rewritten once; the rebased table is then
+  // validated like a recorded one.
+  std::vector<const void*> tables_done;
+  for (auto& op : p->ops) {
+    if (op.kind != PDSE_OP_RANGE) continue;
+    pdse_range_desc& rd_ = op.d.range;
+    if (!rd_.rows || rd_.nrows < 1 || rd_.nrows > 65535) continue;
+    bool done = false;
+    for (const void* t : tables_done) done = done || t == rd_.rows;
+    if (done) continue;
+    std::vector<pdse_range_row> rows((size_t)rd_.nrows);
+    if (pdse_check_hip(hipMemcpy(rows.data(), rd_.rows, rows.size() * sizeof(pdse_range_row), hipMemcpyDeviceToHost), "plan_load: range table")) return fail(pdse_last_error());
+    for (auto& row : rows) {
+      uint64_t v = reinterpret_cast<uint64_t>(row.ptr);
+      bool found = false;
+      for (uint32_t r = 0; r < nreg && !found; ++r) {
+        if (v >= old_base[r] && v < old_base[r] + p->regions[r].bytes) {
+          row.ptr = reinterpret_cast<const void*>(reinterpret_cast<uint64_t>(p->regions[r].ptr) + (v - old_base[r]));
+          found = true;
+        }
+      }
+      if (!found) return fail("plan_load: a range-audit row points outside every recorded region");
+    }
+    if (pdse_check_hip(hipMemcpy(const_cast<pdse_range_row*>(rd_.rows), rows.data(), rows.size() * sizeof(pdse_range_row), hipMemcpyHostToDevice), "plan_load: range table")) return fail(pdse_last_error());
+    tables_done.push_back(rd_.rows);
+    if (pdse_range_validate(&rd_)) return fail(pdse_last_error());
   }
   fclose(f);
   *out = p;

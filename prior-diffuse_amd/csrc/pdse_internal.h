@@ -56,5 +56,7 @@ int pdse_dense_launch(const pdse_dense_desc* d, hipStream_t s);     /* csrc/dens
 int pdse_rowlnb_launch(const pdse_rowlnb_desc* d, hipStream_t s);
 int pdse_metrics_launch(const pdse_metrics_desc* d, hipStream_t s);   /* csrc/metrics.hip */
 int pdse_resample_launch(const pdse_resample_desc* d, hipStream_t s);   /* csrc/resample.hip */
+int pdse_range_launch(const pdse_range_desc* d, hipStream_t s);   /* csrc/range.hip */
+int pdse_range_validate(const pdse_range_desc* d);                 /* reads the row table back and checks it (direct launches, plan_add) */
 int pdse_gru3_launch(const pdse_gru_desc* d, hipStream_t s);   /* csrc/gru3.hip, reached through pdse_gru_launch */
 #endif

@@ -34,6 +34,12 @@ def parse_args_and_config(argv=None):
     p.add_argument("--bf16", action="store_true",
                    help="(not a flag of the reference) the opt-in reduced-precision mode: plain bf16 operands and bf16 block-boundary "
                         "tensors in the eps-net's blocks and the priors' GEMM-shaped convolutions, tolerance 3e-2 rel-L2 against the fp32 path; default: fp32-equivalent arithmetic")
+    p.add_argument("--split", choices=("f16x2", "bf16x3"), default=None,
+                   help="(not a flag of the reference) the fp32-equivalent operand split of the matrix-core kernels: f16x2 (default; fp32-"
+                        "equivalent inside the fp16 window 2^-6 <= |activation| < 4094) or bf16x3 (the exact three-way bf16 split, no window)")
+    p.add_argument("--audit-range", action="store_true",
+                   help="(not a flag of the reference) audit every f16x2 pass on the device: a geometry with a tensor wholly below the fp16 "
+                        "window is repeated on bf16x3, like one that overflowed it")
     args = p.parse_args(argv)
     args.log = os.path.join(args.assets, "log", args.doc)
     args.checkpoint = os.path.join(args.assets, "checkpoint", args.doc)

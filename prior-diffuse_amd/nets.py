@@ -103,6 +103,8 @@ class PlanBase:
         self.plan = plan if plan is not None else (L.Plan(ctx.device) if ctx.device.type == "cuda" else None)
         self.ns = (type(self).__name__, bool(self.force_generic)) + tuple(ns)
         self._mi = 0
+        self._audit_ops = {}      # (address, kind) -> f16x2 operand of a recorded launch, in recording order (audited())
+        self._audit_names = {}    # data_ptr -> (name, buffer): the buffers audited() may report (named())
 
     def memo(self, label, fn):
         """Weight-derived value (device tensors, folded scalars), computed once per WeightBank: ``fn`` runs only on
@@ -130,6 +132,72 @@ class PlanBase:
         self.descs.append((desc, tag))
         if self.plan is not None:
             self.plan.add(desc, tag)
+        for op in self.f16x2_operands(desc):        # noted as recorded (a few comparisons); resolved by audited() only
+            self._audit_ops.setdefault((op[0], op[1]), op)
+
+    # ---- range audit of the f16x2 window (csrc/range.hip) -----------------------
+    def named(self, name, t):
+        """Give a buffer the name it carries in audited() and in range reports; returns the buffer."""
+        self._audit_names[t.data_ptr()] = (name, t)
+        return t
+
+    @staticmethod
+    def f16x2_operands(desc):
+        """The activation operands an f16x2 contraction of one recorded launch reads from memory, as
+        [(address, kind, layout or None, name suffix)] - empty for every other launch.  kind RANGE_F16HI: a two-plane tensor
+        (layout: the packing.hp_box / tcm2_hs_box of its logical elements, address: its first logical vector; suffix: the branch
+        of a TCM bottleneck tensor); RANGE_F32: an fp32 tensor the kernel scales by 2^PDSE_F16_ACT_EXP and splits in registers
+        (address: anywhere inside it).  This is the one place that knows which launches multiply f16x2 operands: csrc/bglu.hip
+        and csrc/tcm2.hip with np 2, csrc/gconv4.hip korder 5, csrc/dense.hip np 2.  Operands that never reach memory (a block's
+        gate tensor, the chained 1x1 tiles) cannot be audited."""
+        out = []
+        if isinstance(desc, L.BgluDesc) and desc.np == 2:
+            if desc.hp:
+                F_ = desc.hp_Fp - 2 * desc.hp_f0
+                box = P.hp_box(desc.B, desc.hp_Tp - desc.hp_t0, F_, 2, par=bool(desc.hp_par))
+                out.append((desc.hp + 2 * box["off"], L.RANGE_F16HI, box, ""))
+            else:
+                out += [(desc.x0.ptr, L.RANGE_F32, None, ""), (desc.x1.ptr, L.RANGE_F32, None, "")]
+        elif isinstance(desc, L.Tcm2Desc) and desc.np == 2:
+            out.append((desc.x, L.RANGE_F32, None, ""))
+            if desc.mode == 0:
+                for br, suffix in enumerate((".main", ".mask")):
+                    box = P.tcm2_hs_box(desc.B, desc.T, 2, br)
+                    out.append((desc.hs + 2 * box["off"], L.RANGE_F16HI, box, suffix))
+        elif isinstance(desc, L.Tcm2sDesc):
+            for i in range(desc.n):
+                out += PlanBase.f16x2_operands(desc.blk[i])
+        elif isinstance(desc, L.GconvDesc) and desc.korder == 5:
+            out += [(s_.ptr, L.RANGE_F32, None, "") for s_ in (desc.in0, desc.in1) if s_.ptr]
+        elif isinstance(desc, L.DenseDesc) and desc.np == 2:
+            out.append((desc.D, L.RANGE_F32, None, ""))
+        return [o for o in out if o[0]]
+
+    def audited(self):
+        """Every activation tensor an f16x2 contraction of the recorded launches reads from memory, as
+        [(name, tensor, kind, exp, layout)] in recording order - the contract of the range audit
+        (``SamplerPipeline(audit=True)``).  The operands are noted from the descriptors as they are recorded (``add``), so a
+        launch cannot be missing; this call resolves them to the buffers the builder named where it allocated them (``named``)
+        and raises if an operand lies in a buffer without a name - recording itself never fails for the audit's sake.
+        kind / exp / layout are the fields of a pdse_range_row: RANGE_F32 tensors are counted whole (zero padding of the dense
+        buffers included: zeros never decide a verdict) with exp = PDSE_F16_ACT_EXP, RANGE_F16HI tensors over the logical box
+        ``layout`` (packing.hp_box / tcm2_hs_box; off: uint16 offset in ``tensor``), exp 0; the two branches of a TCM
+        bottleneck tensor are two entries (``.main`` / ``.mask``).  Buffers are reused within a pass (both decoders share
+        hp_de*, the TCM blocks ping-pong two hs buffers): an audit after a marked range sees their last contents."""
+        out, seen = [], set()
+        for addr, kind, box, suffix in self._audit_ops.values():
+            hit = next(((n, t) for n, t in self._audit_names.values()
+                        if t.data_ptr() <= addr < t.data_ptr() + t.numel() * t.element_size()), None)
+            if hit is None:
+                raise RuntimeError("range audit: the f16x2 operand at 0x%x lies in no buffer the builder named (PlanBase.named)" % addr)
+            name, t = hit
+            key = (name + suffix, kind)
+            if key in seen:
+                continue
+            seen.add(key)
+            out.append((name + suffix, t, kind, P.F16_ACT_EXP if kind == L.RANGE_F32 else 0,
+                        None if box is None else dict(box, off=(addr - t.data_ptr()) // 2)))
+        return out
 
     def finish(self):
         if self.plan is not None:
@@ -443,6 +511,16 @@ class EpsNetPlan(PlanBase):
             self.hp_en = {k: ctx.alloc_u16(*P.hp_shape(B + 1, T, self.ENC_F[k - 1], self.planes)) for k in range(2, 6)}
             self.hp_de = {k: ctx.alloc_u16(*P.hp_shape(B + 1, T, self.ENC_F[k], self.planes)) for k in range(1, 6)}
             self.hp_de5b = ctx.alloc_u16(*P.hp_shape(B + 1, T, self.ENC_F[5], self.planes))   # stage 5 of the second decoder (both conv1 are computed by one launch)
+            for k, t_ in self.hp_en.items():
+                self.named("hp_en%d" % k, t_)
+            for k, t_ in self.hp_de.items():
+                self.named("hp_de%d" % k, t_)
+            self.named("hp_de5b", self.hp_de5b)
+        # what the f16x2 kernels read besides the plane tensors: the inputs of encoder stage 1, the TCM residual stream, hs
+        for name, t_ in (("x", self.x), ("x_init", self.x_init), ("en5", self.en[4]), ("tcm_a", self.tcm_a), ("tcm_b", self.tcm_b),
+                         ("tcm_hs0", self.tcm_hs[0]), ("tcm_hs1", self.tcm_hs[1])):
+            if t_ is not None:
+                self.named(name, t_)
         if time_cond:
             self.tsteps = a(nsteps, B, zero=True)
             self.tbias = a(nsteps, B, self.NSLOT * 32)
@@ -1227,6 +1305,13 @@ class GcrnPlan(PlanBase):
             self.yn = a(B, 1024, T)
         self.glstm = a(B, 256, T, 4)
         self.d = [a(B, 128, T, 9), a(B, 64, T, 19), a(B, 32, T, 39), a(B, 16, T, 80), a(B, 1, T, 161)]
+        # inputs of the korder-5 GEMM convolutions (range audit): encoder outputs, the LSTM output, the decoders' stage outputs
+        for i, t_ in enumerate(self.e):
+            self.named("gcrn.e%d" % (i + 1), t_)
+        self.named("gcrn.glstm", self.glstm)
+        for i, t_ in enumerate(self.d[:4]):
+            self.named("gcrn.d%d" % (5 - i), t_)
+        self.named("gcrn.x", self.x)
 
     def w(self, k):
         return P._np(self.sd[k])
@@ -1588,6 +1673,8 @@ class AiaPlan(PlanBase):
             self.D161 = a(B, self.G, T + self.TPAD, F0 + 2, 8, zero=True)
             self.D80 = a(B, self.G, T + self.TPAD, FH + 2, 8, zero=True)
             self._d80_holds = None
+            self.named("aia.D161", self.D161)     # the dense buffers: what csrc/dense.hip np 2 and the korder-5 convolutions read
+            self.named("aia.D80", self.D80)
         else:
             self.D161 = a(B, 320, T, F0)            # dense buffer [out4,out3,out2,out1,x]
             self.D80 = a(B, 320, T, FH)

@@ -401,6 +401,16 @@ def tcm2_split_h(v_main, v_mask, npl=3):
     return hs
 
 
+def tcm2_hs_box(B, T, npl, br):
+    """The logical elements of one branch (0 main, 1 mask) of hs as a box of 8-element vectors of plane 0 (hi): uint16 offset of
+    the first vector, extents (b, 1, kb kg, t), strides of the three outer indices.  What lies outside - the TCM2_HS_PAD zero
+    frames on either side, the other planes - is margin: tcm2_join_h drops exactly that, and the range audit (include/pdse.h:
+    pdse_range_row) does not count it."""
+    Tq = T + 2 * TCM2_HS_PAD
+    sg = npl * Tq * 8
+    return dict(off=br * 8 * sg + TCM2_HS_PAD * 8, dims=(B, 1, 8, T), strides=(16 * sg, 0, sg), i0=0, par_half=0)
+
+
 def tcm2_join_h(hs, B, T):
     """Inverse of tcm2_split_h: (v_main, v_mask) float32 [B, 64, T]; asserts the zero margins."""
     hs = np.asarray(hs, np.uint16)
@@ -580,10 +590,25 @@ def hp_split(x, npl):
     return hp
 
 
-def hp_join(hp, with_margins=False):
-    """hp uint16 -> float [B, 32, Tp, Fp] (with_margins) or [B, 32, T, F]."""
+def hp_box(B, T, F, npl, par=False):
+    """The logical elements of an hp tensor (items 0 .. B-1, frames t >= 0, bins 0 .. F-1) as a box of 8-element vectors of
+    plane 0 (hi): uint16 offset of the first vector's row, extents (b, t, g, f), strides of the three outer indices, the
+    first logical index on the bin axis and the parity split (hp_par_pos; 0: none).  What lies outside - the frame at tp 0,
+    HP_F0 bins on either side, the other planes, the kernels' dump item B - is margin: hp_join drops exactly that, and the
+    range audit (include/pdse.h: pdse_range_row) does not count it."""
+    _, Tp, G, _, Fp, E = hp_shape(B, T, F, npl)
+    sg = npl * Fp * E
+    return dict(off=HP_T0 * G * sg, dims=(B, T, G, F), strides=(Tp * G * sg, G * sg, sg), i0=HP_F0,
+                par_half=(Fp + 1) >> 1 if par else 0)
+
+
+def hp_join(hp, with_margins=False, par=False):
+    """hp uint16 -> float [B, 32, Tp, Fp] (with_margins) or [B, 32, T, F].  par: the bins are stored split by parity
+    (hp_par_pos); the result is in natural bin order either way."""
     hp = np.asarray(hp, np.uint16)
     B, Tp, _, npl, Fp, _ = hp.shape
+    if par:
+        hp = hp.take(hp_par_pos(Fp), axis=4)
     v = from_planes(hp.transpose(3, 0, 1, 2, 4, 5), F16_ACT_EXP)            # [B, Tp, g, Fp, e]
     out = np.zeros((B, 32, Tp, Fp), np.float32)
     for g in range(4):

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import nets, packing
+from . import nets, packing, rangeaudit
 from .params import PRIOR_SCALE_C, params as default_params
 from .schedule import inference_schedule, step_coefficients
 
@@ -35,7 +35,7 @@ class SamplerPipeline:
 
     def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, T=None, L_=None, fast_sampling=True,
                  use_sigma=False, params=default_params, with_signal=None, deltamu=False, cond="init", bank=None,
-                 split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None):
+                 split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False):
         """deltamu: the alternative parameterisation of utils/params.py:36 — ddpm_sd is a ``Nocon`` state_dict,
         x_T = noise + X_init/11 (:947-948), eps = Nocon(x, t) (:970-971), no final ``+ X_init`` (:995).
         cond (deltamu False): what conditions DiffUNet1 — "init": X_init/11 (pirorgrad, :967-969, + X_init at the end,
@@ -62,8 +62,15 @@ class SamplerPipeline:
         off (exact fp32 MFMA) for the full 50-step schedule.
         split (with split_bf16, dtype "f32"): which fp32-equivalent operand split the matrix-core kernels use - "bf16x3": the exact
         three-way bf16 split, six bf16 products per multiply-add; "f16x2": fp16 hi + lo of the power-of-two scaled operand (within
-        half an fp32 ulp inside the fp16 window, see include/pdse.h PDSE_F16_ACT_EXP), three f16 products, two thirds of the plane
-        bytes.  Both are held to the same goldens and tolerances.  None: ``SamplerPipeline.default_split``."""
+        2^-23 |x|, relative, inside the fp16 window, see include/pdse.h PDSE_F16_ACT_EXP), three f16 products, two thirds of the plane
+        bytes.  Both are held to the same goldens and tolerances.  None: ``SamplerPipeline.default_split``.
+        audit: record the range audit of the f16x2 window with the plan (csrc/range.hip): one launch that clears the histogram
+        table at the start of the plan and one accumulate launch at the end of every marked range whose builder has audited
+        tensors (``nets.PlanBase.audited()``) - "prior", then every "stepN": the plane buffers are reused by every step, so a
+        look after the pass would see the last step only.  Rows are per (range, tensor); the launches only read the tensors, they
+        are part of the plan and of its hipGraph.  ``range_report()`` / ``check(audit=True)`` read the table.  Only f16x2 passes
+        have a window: with split "bf16x3" (or dtype "bf16", or the exact fp32 arithmetic of the full schedule) the flag is
+        accepted and nothing is recorded.  False (default): the plan is launch for launch the one without the feature."""
         if L_ is not None:
             T = 1 + L_ // 160
         if with_signal is None:
@@ -96,6 +103,11 @@ class SamplerPipeline:
         self.nsteps = S
         self.ranges = {}
         self.descs = []
+        self.audit = bool(audit)
+        # the audit is recorded only where f16x2 operands are multiplied
+        self.audited = self.audit and split == "f16x2" and dtype == "f32" and bool(split_bf16) and self.plan is not None
+        self.range_rows = []          # (range name, tensor name) of every histogram row, in table order
+        self.range_hist = None        # device int32 [RANGE_CAP][32] (the kernel's uint32 counters)
 
         # ---- builders share one plan object and one descriptor list
         def adopt(pb):
@@ -138,9 +150,44 @@ class SamplerPipeline:
         self.xT_in = ctx.alloc(B, 2, T, F0)          # injected x_T (kept so a replay starts from it)
         n = B * 2 * T * F0
 
+        if self.audited:
+            # The clear launch is the plan's first, so the table is sized before the rows are known - by a bound that holds by
+            # construction: audited() reports only buffers the builder named (PlanBase.named), each at most twice (the two
+            # branches of a TCM bottleneck tensor), once per audited range - the prior's range and one range per step.
+            self._range_cap = 2 * (len(self.prior._audit_names) + S * len(self.eps._audit_names))
+            self.range_hist = torch.zeros(max(1, self._range_cap), L.RANGE_BINS, dtype=torch.int32, device=self.device)
+            ctx.keep.append(self.range_hist)
+        self._range_clear = None      # index of the clear launch in the plan
+        self._ranges_run = set()      # marked ranges the last run() executed (range_report() reports those)
+
+        def range_launch(mode, rows=None):
+            d = L.RangeDesc()
+            d.out, d.out_rows, d.mode, d.blocks = self.range_hist.data_ptr(), self.range_hist.shape[0], mode, 1
+            if rows:
+                dev = ctx.up(rangeaudit.table_of(rows), np.uint8)
+                d.rows, d.nrows, d.blocks = dev.data_ptr(), len(rows), rangeaudit.work_blocks(rows)
+            else:
+                self._range_clear = len(self.descs)
+            self.eps.add(d, nets.TAG_NONE)
+
         def mark(name, fn):
             b = len(self.descs)
+            if self.audited and not self.ranges:
+                range_launch(L.RANGE_CLEAR)                     # first launch of the plan
             fn()
+            if self.audited and (name == "prior" or name.startswith("step")):
+                rows = []
+                entries = (self.prior if name == "prior" else self.eps).audited()
+                # rows in the order of the dataflow at the time of the look: the diffusion state was updated by the step's
+                # last launch, so what the audit sees in it is the step's OUTPUT - it goes last (the first ``above`` row of a
+                # report is then the tensor that overflowed, not the state it poisoned)
+                entries.sort(key=lambda a: a[1].data_ptr() == self.audio.data_ptr())
+                for tname, t, kind, e, box in entries:
+                    rows.append(rangeaudit.make_row(t, kind, e, box, len(self.range_rows)))
+                    self.range_rows.append((name, tname))
+                assert len(self.range_rows) <= self._range_cap
+                if rows:
+                    range_launch(L.RANGE_ACCUMULATE, rows)
             self.ranges[name] = (b, len(self.descs))
 
         if with_signal:
@@ -214,14 +261,44 @@ class SamplerPipeline:
                     self.plan.build_graph(self._graph_stream.cuda_stream)
                 self._graph_stream.synchronize()
             self.plan.launch_graph(self._stream())
+            self._ranges_run = set(self.ranges)
             return
         b = self.ranges[first][0] if first else 0
         e = self.ranges[last][1] if last else len(self.descs)
+        if self.audited and not b <= self._range_clear < e:
+            c = self._range_clear                              # a call that starts later still starts from a cleared table
+            self.plan.run_range(c, c + 1, self._stream())
         self.plan.run_range(b, e, self._stream())
+        self._ranges_run = {k for k, (rb, re_) in self.ranges.items() if b <= rb and re_ <= e}
 
-    def check(self):
+    def range_report(self):
+        """Synchronises, copies the histogram table of the last pass to the host (a few KB) and returns its
+        ``rangeaudit.RangeReport``: per (marked range, audited tensor) ``name``, ``range``, ``count``, ``hist[32]``,
+        ``max_binade``, ``below_frac``, ``below``, ``above``; ``ok``, ``worst()`` and a printable table over all of them.  The
+        verdicts follow from the format (derivation: the docstring of ``rangeaudit``): an f16x2 pair carries 11 + 11 significand
+        bits, |x - hi - lo| <= 2^-23 |x|, only while hi's exponent is >= -2 in scaled units (lo a normal fp16, or its subnormal
+        error still inside the bound) - 2^-6 in true scale with PDSE_F16_ACT_EXP = 4.  ``below``: the tensor's largest non-zero
+        magnitude is under that edge, no element of it is carried at full precision; ``below_frac``: the share of its non-zero
+        elements under the edge; ``above``: an element reached 2^15 scaled, the binade in which hi becomes an infinity (or was
+        not finite).  A pipeline built without ``audit=True`` raises ValueError; one built with it whose arithmetic has no
+        window (split "bf16x3") returns an empty report.
+        The report is that of the last ``run()`` call: every call starts from a cleared table, and only the rows of the marked
+        ranges that call executed are reported (a pipeline stepped range by range reports the last range; rows of ranges that
+        did not run would be all-zero and read as clean)."""
+        if not self.audit:
+            raise ValueError("the pipeline was built without the range audit (SamplerPipeline(audit=True))")
+        if not self.audited:
+            return rangeaudit.RangeReport([])
+        hist = self.range_hist[:len(self.range_rows)].cpu().numpy().view(np.uint32)     # synchronises
+        return rangeaudit.RangeReport(rangeaudit.ReportRow(tname, rname, hist[i]) for i, (rname, tname) in enumerate(self.range_rows)
+                                      if rname in self._ranges_run)
+
+    def check(self, audit=False):
         """Synchronises and raises if a persistent launch of the last run gave up (its workgroups wait for each other
-        with bounded polls: another workload on the GPU can keep them from all being resident)."""
+        with bounded polls: another workload on the GPU can keep them from all being resident), or - f16x2 passes - if the
+        result is not finite: an activation left the top of the fp16 window (``PdseRangeError``; an audited pipeline names the
+        tensor).  audit=True (pipelines built with ``audit=True``): also reads the range report and raises ``PdseRangeError``
+        naming the first tensor, and its marked range, that lay wholly below the window - the case that leaves no other trace."""
         for net, field, what in ((self.prior, "status", "persistent LSTM gave up at step %d"), (self.eps, "tcm_status", "TCM stack launch gave up at block %d"),
                                  (self.prior, "tcm_status", "TCM stack launch of the prior gave up at block %d")):
             st = getattr(net, field, None)
@@ -232,9 +309,21 @@ class SamplerPipeline:
                     raise L.PdseError((what % (code - 1)) + ": its workgroups wait for each other and were not all resident in time (is "
                                       "another workload sharing the GPU?); build the pipeline with exclusive=False")
         if self.split == "f16x2" and self.split_bf16 and self.dtype == "f32" and not bool(torch.isfinite(self.spec).all()):
-            raise L.PdseRangeError("non-finite values in the enhanced spectrogram of an f16x2 pass: an activation beyond +-%g left the fp16 "
+            where = ""
+            if self.audited:
+                top = self.range_report().above()
+                if top:
+                    where = " (range audit: first in %s of %s)" % (top[0].name, top[0].range)
+            raise L.PdseRangeError("non-finite values in the enhanced spectrogram of an f16x2 pass%s: an activation beyond +-%g left the fp16 "
                                    "window (include/pdse.h: PDSE_F16_ACT_EXP), or the input was not finite; build the pipeline with "
-                                   "split='bf16x3' (ComplexDDPMTrainer does so for this geometry by itself)" % (65504.0 / 2 ** packing.F16_ACT_EXP))
+                                   "split='bf16x3' (ComplexDDPMTrainer does so for this geometry by itself)" % (where, 65504.0 / 2 ** packing.F16_ACT_EXP))
+        if audit:
+            low = self.range_report().below()
+            if low:
+                raise L.PdseRangeError("range audit: every non-zero element of %s in %s is below 2^%d, the bottom of the fp16 window of an f16x2 "
+                                       "pass (include/pdse.h: PDSE_F16_ACT_EXP): the tensor is not carried at fp32-equivalent precision "
+                                       "(%d tensors in all); build the pipeline with split='bf16x3' (ComplexDDPMTrainer(audit=True) does so "
+                                       "for this geometry by itself)" % (low[0].name, low[0].range, -2 - packing.F16_ACT_EXP, len(low)))
 
     def sample(self, feat, x_T, graph=False):
         """feat, x_T [B,2,T,161] -> (enhanced compressed spectrogram, X_init); the

@@ -123,8 +123,13 @@ def save_prior(path, prior_name, prior_sd, B, T, device="cuda:0"):
 
 def save_pipeline(path, pipe):
     """The whole path of one SamplerPipeline built with the signal front / back end (wav -> ... -> wav): regions wav [B,L],
-    x_T [B,2,T,161], wav_out [B,L], spec [B,2,T,161].  The true lengths are stored as the pipeline holds them (full length)."""
+    x_T [B,2,T,161], wav_out [B,L], spec [B,2,T,161].  The true lengths are stored as the pipeline holds them (full length).
+    A pipeline built with ``audit=True`` on f16x2 operands also carries its range audit: region range_hist, uint32 [rows][32]
+    (rows: ``pipe.range_rows`` in order, then unused ones up to the region's size), cleared and filled by every run."""
     if pipe.stft is None:
         raise ValueError("the pipeline was built without the signal front / back end (pass L_)")
     pipe.stft.lens.fill_(pipe.L)
-    return save(path, pipe.descs, pipe.ctx, {"wav": pipe.stft.wav, "x_T": pipe.xT_in, "wav_out": pipe.istft.wav, "spec": pipe.spec})
+    named = {"wav": pipe.stft.wav, "x_T": pipe.xT_in, "wav_out": pipe.istft.wav, "spec": pipe.spec}
+    if getattr(pipe, "audited", False):
+        named["range_hist"] = pipe.range_hist
+    return save(path, pipe.descs, pipe.ctx, named)

@@ -32,7 +32,7 @@ class ComplexDDPMTrainer(object):
     MAX_PLANS = 3   # recorded (B, T) geometries kept alive (least recently used first out); weights are shared by all
 
     def __init__(self, args, config, device=None, prior_state_dict=None, ddpm_state_dict=None, params=None, exclusive=None,
-                 dtype=None):
+                 dtype=None, split=None, audit=None):
         """args: .retrain .joint .draw .sigma .checkpoint .generated_wav
         config: .model.name, .train.{fft_num, win_size, win_shift, feat_type}
         Weights come from ``<args.checkpoint>/best_checkpoint.pth`` under the reference's
@@ -41,10 +41,26 @@ class ComplexDDPMTrainer(object):
         time), so small batches may take the persistent LSTM launch (csrc/lstmp.hip).  None: True unless the process is
         one rank of a torch.distributed job - a sharded run keeps the kernels that make an utterance's result
         bit-identical whatever the number of ranks (prior-diffuse_amd/shard.py).
-        dtype: "f32" (default: the reference's arithmetic - fp32, or the fp32-equivalent exact three-way bf16 split) or "bf16",
+        dtype: "f32" (default: the reference's arithmetic - fp32, or an fp32-equivalent operand split of the matrix-core kernels,
+        see ``split``) or "bf16",
         the OPT-IN reduced-precision mode BASELINE configs 2/4/5 name (``SamplerPipeline(dtype="bf16")``: plain bf16 operands
         and bf16 block-boundary tensors in the eps-net, tolerance 3e-2 rel-L2; never the default).  None: ``args.bf16`` when the
-        CLI set it (``main.py --bf16``), else "f32"."""
+        CLI set it (``main.py --bf16``), else "f32".
+        split: the fp32-equivalent operand split every plan of this trainer is built with, handed to ``SamplerPipeline`` as is -
+        "f16x2" (fp16 hi + lo of the scaled operand: fp32-equivalent inside the fp16 window of include/pdse.h) or "bf16x3" (the
+        exact three-way bf16 split: no window, 1.45 x the time); None: ``args.split`` when the CLI set it (``main.py --split``),
+        else ``SamplerPipeline.default_split`` ("f16x2").  A geometry whose f16x2 pass leaves the window is repeated on
+        "bf16x3" whatever this says (``_checked``).
+        audit: build the plans with the range audit of the f16x2 window (``SamplerPipeline(audit=True)``) and let ``_checked``
+        treat a tensor that lies wholly BELOW the window - finite output, no other trace - like one that overflowed it: warn,
+        repeat the geometry on "bf16x3".  None: ``args.audit_range`` when the CLI set it (``main.py --audit-range``), else False."""
+        if split is None:
+            split = getattr(args, "split", None)
+        if split not in (None, "f16x2", "bf16x3"):
+            raise ValueError("split must be 'f16x2' or 'bf16x3'")
+        self.split = split
+        self.audit = bool(getattr(args, "audit_range", False) if audit is None else audit)
+        self._audit_clean = set()              # geometries whose audited f16x2 pass came back clean once: their report is not read again
         if dtype is None:
             dtype = "bf16" if getattr(args, "bf16", False) else "f32"
         if dtype not in ("f32", "bf16"):
@@ -101,9 +117,11 @@ class ComplexDDPMTrainer(object):
                 self.ddpm_sd = data[2]
         else:
             self.prior_sd = data
-        if hasattr(self, "bank"):              # new weights: every recorded plan and the packed copies are stale
-            self._pipes.clear()
+        if hasattr(self, "bank"):              # new weights: every recorded plan and the packed copies are stale, and so is every
+            self._pipes.clear()                # verdict on the fp16 window (fallback geometries, clean audits)
             self._hits.clear()
+            self._range_fallback.clear()
+            self._audit_clean.clear()
             self.bank = nets.WeightBank()
             self.model = ops.PRIOR_OPS[self.prior_name](self.prior_sd, self.device, bank=self.bank, exclusive=self.exclusive)
             self.model_ddpm = (ops.NoconOp if self.deltamu else ops.DiffUNet1Op)(self.ddpm_sd, self.device, bank=self.bank, exclusive=self.exclusive)
@@ -128,7 +146,7 @@ class ComplexDDPMTrainer(object):
                 self.device, self.prior_name, self.prior_sd, self.ddpm_sd, B, T=T, L_=L_,
                 fast_sampling=self.params.fast_sampling, use_sigma=key[3], params=self.params, deltamu=self.deltamu,
                 cond=self.cond, bank=self.bank, xT_plus_init=self.xT_plus_init, exclusive=self.exclusive, dtype=self.dtype,
-                split="bf16x3" if key in self._range_fallback else None)
+                split="bf16x3" if key in self._range_fallback else self.split, audit=self.audit)
         else:
             self._pipes.move_to_end(key)
         return pipe
@@ -136,13 +154,21 @@ class ComplexDDPMTrainer(object):
     def _checked(self, run, **geom):
         """``run(pipe) -> result`` on the plan of a geometry, verified (``SamplerPipeline.check``: synchronises).  A pass on f16x2
         operands whose activations left the fp16 window shows as non-finite output (include/pdse.h: PDSE_F16_ACT_EXP): the geometry
-        is then rebuilt on the exact three-plane bf16 split - no window - and the pass repeated; later calls stay on it."""
+        is then rebuilt on the exact three-plane bf16 split - no window - and the pass repeated; later calls stay on it.
+        With ``audit`` the range report of the pass is read as well and a tensor wholly below the window is handled the same
+        way.  The audit is read on a geometry's passes until one comes back clean; after that the geometry keeps its audited
+        plan (re-recording it would cost more than the launches do) and stops reading the report - a geometry is judged on the
+        first inputs it sees, at the price of one small device-to-host copy per pass until then and of the audit launches for
+        as long as the plan lives."""
         pipe = self._pipe(**geom)
+        key = next(reversed(self._pipes))
         res = run(pipe)
         try:
-            pipe.check()
+            read = self.audit and pipe.audited and key not in self._audit_clean
+            pipe.check(audit=read)
+            if read:
+                self._audit_clean.add(key)
         except L.PdseRangeError as e:
-            key = next(reversed(self._pipes))
             logging.warning("%s - repeating this geometry with split='bf16x3'", e)
             self._range_fallback.add(key)
             del self._pipes[key]

@@ -1,40 +1,39 @@
-"""Largest magnitudes of the plane tensors the f16x2 kernels exchange (hp of every stage, the TCM bottleneck hs) for the nominal
-inputs of the bench: python tools/act_range.py  (how far the fp16 window of include/pdse.h: PDSE_F16_ACT_EXP is from them)."""
+"""Where the tensors the f16x2 kernels multiply sit in the fp16 window of include/pdse.h (PDSE_F16_ACT_EXP), for the nominal inputs
+of the bench: the device report of an audited pass (``SamplerPipeline(audit=True).range_report()``, csrc/range.hip) - per marked
+range and tensor the element count, the largest binade, the share of elements under the full-precision edge and the verdict.
+
+    python tools/act_range.py [--prior GCRN] [-B 2] [-L 32000]
+"""
+import argparse
 import importlib
 import os
 import sys
-
-import numpy as np
-import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
-ge.build()
-nets = importlib.import_module("prior-diffuse_amd.nets")
-synth = importlib.import_module("prior-diffuse_amd.synth")
-Pk = importlib.import_module("prior-diffuse_amd.packing")
 
-B, T = 2, 200
-net = nets.EpsNetPlan(nets.Ctx("cuda:0"), synth.make_state_dict("DiffUNet1"), B, T, time_cond=True, nsteps=1, planes=2)
-net.build_time()
-net.build_step(0)
-net.finish()
-g = torch.Generator().manual_seed(5)
-net.x.copy_(torch.randn(B, 2, T, 161, generator=g))
-net.x_init.copy_(torch.randn(B, 2, T, 161, generator=g) * 0.3)
-net.tsteps.fill_(10.45)
-net.plan.run()
-torch.cuda.synchronize()
-print("window: full precision for %.4g <= |x|, saturation at %.5g" % (2.0 ** (-2 - Pk.F16_ACT_EXP), 65504.0 / 2 ** Pk.F16_ACT_EXP))
-for name, hp in [("hp_en%d" % k, v) for k, v in net.hp_en.items()] + [("hp_de%d" % k, v) for k, v in net.hp_de.items()]:
-    v = Pk.hp_join(hp.cpu().numpy().view(np.uint16)[:B], with_margins=True)
-    a = np.abs(v[v != 0])
-    print("%-8s max %.3g  rms %.3g  1%% quantile %.3g" % (name, a.max(), np.sqrt((a ** 2).mean()), np.quantile(a, 0.01)))
-for i, hs in enumerate(net.tcm_hs):
-    vm, vk = Pk.tcm2_join_h(hs.cpu().numpy().view(np.uint16), B, T)
-    for nm, v in (("main", vm), ("mask", vk)):
-        a = np.abs(v[v != 0])
-        print("tcm hs%d %s max %.3g rms %.3g" % (i, nm, a.max(), np.sqrt((a ** 2).mean())))
-print("eps-net output rms %.3g" % float(net.out.pow(2).mean().sqrt()))
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--prior", default="GCRN")
+    ap.add_argument("-B", type=int, default=2)
+    ap.add_argument("-L", type=int, default=32000)
+    a = ap.parse_args()
+    ge.build()
+    synth = importlib.import_module("prior-diffuse_amd.synth")
+    Pk = importlib.import_module("prior-diffuse_amd.packing")
+    pipeline = importlib.import_module("prior-diffuse_amd.pipeline")
+    wav, x_T = synth.synthetic_waveforms(a.B, a.L, seed=1234)
+    pipe = pipeline.SamplerPipeline("cuda:0", a.prior, synth.make_state_dict(a.prior), synth.make_state_dict("DiffUNet1"), a.B, L_=a.L,
+                                    audit=True)
+    pipe.enhance(wav.cuda(), x_T.cuda())
+    pipe.check()
+    rep = pipe.range_report()
+    print("window: fp32-equivalent for %.4g <= |x|, hi leaves the fp16 range at %.5g" % (2.0 ** (-2 - Pk.F16_ACT_EXP), 65504.0 / 2 ** Pk.F16_ACT_EXP))
+    print(rep)
+    print("ok" if rep.ok else "NOT ok: worst %r" % rep.worst())
+
+
+if __name__ == "__main__":
+    main()
