@@ -936,11 +936,10 @@ int pdse_rowln_blocked_f32(const pdse_rowlnb_desc* d, pdse_stream_t s);
 int pdse_quality_metrics_f32(const pdse_metrics_desc* d, pdse_stream_t s);
 int pdse_pcm_resample_f32(const pdse_resample_desc* d, pdse_stream_t s);
 int pdse_range_hist(const pdse_range_desc* d, pdse_stream_t s);
-/* Kernel form of pdse_bglu_planes (ABI 6; process-wide, tuning only): -1 / 0 = 8 waves with the generated slot schedule
- * (the product kernel).  A library built with -DBGLU_FORMS also holds the forms that were measured and not kept
- * (profiles/r03_bglu_forms.txt, r04_bglu_forms.txt): 1 = 4 waves software-pipelined, 2 / 3 = 16 / 12 waves with strictly
- * sequential tiles, 4 = 8 waves with the vector-memory instructions spread over the slots.  Every form reads the same
- * descriptor and computes the same block.  Returns the previous setting, or -2 for a form this library does not hold. */
+/* Kernel form of pdse_bglu_planes (ABI 6; process-wide): the library holds one form, 8 waves with the generated slot
+ * schedule, named by -1 and by 0.  (The forms that were measured and not kept - 4 waves software-pipelined, 12 / 16 waves
+ * with strictly sequential tiles, spread vector-memory issue: profiles/r03_bglu_forms.txt, r04_bglu_forms.txt - were
+ * forms 1..4.)  Returns the previous setting, or -2 for any other form. */
 int pdse_bglu_set_form(int form);
 
 /* plans: a recorded operator sequence replayed by one call (and capturable in a hipGraph) */

@@ -7,11 +7,12 @@
 //     cycles), and the time per tile on a SIMD was their SUM plus ~5k of waits, scalar work and ~70 exec-mask branches:
 //     vector instructions of one wave do not hide behind matrix instructions of the other wave of the SIMD, only behind
 //     matrix instructions of their own stream (MI355X_MICROARCH.md: <= 5 vector instructions per 32x32x16 gap);
-//   * so the loop is software-pipelined by hand: ONE wave per SIMD (4-wave workgroups, 512 registers), and every
-//     iteration issues the K loop of tile i+1 - matrix instructions and LDS reads only, because the input arrives as
-//     the producer's bf16 split planes - together with the tail of tile i - vector instructions mostly - in one
-//     basic block (no exec-mask branches: out-of-range taps are zero margins, lanes beyond the last position compute
-//     on position 0 and only the final stores are predicated);
+//   * so a tile's instruction order is spelled out by hand (csrc/bglu_sched.inc: slots of one product beside one chunk of
+//     vector work) - the K loop is matrix instructions and LDS reads only, because the input arrives as the producer's
+//     bf16 split planes - in one basic block (no exec-mask branches: out-of-range taps are zero margins, lanes beyond
+//     the last position compute on position 0 and only the final stores are predicated), 8 waves per workgroup.  The
+//     4-wave form that overlapped the K loop of tile i+1 with the tail of tile i, and the 12/16-wave and spread-issue
+//     forms, measured slower and left the tree after commit ae0a628;
 //   * vector work removed from the tail: BatchNorm folded into conv2, -log2 e into l_conv / r_conv, biases seed the
 //     accumulators from LDS, PReLU is mul + max.
 // NP = 3: exact three-way bf16 split of every operand, six products per multiply-add (fp32-equivalent);
@@ -35,9 +36,8 @@
 
 namespace {
 
-#ifdef BGLU_DIAG   // diagnostic build only (tools/time_bglu.py --diag): shader-clock and 100 MHz stamps around the loop
-__device__ unsigned long long g_bglu_diag[4];
-__device__ unsigned long long g_bglu_slots[97];   // BGLU_SLOTSTAMP: shader cycles per slot of the 8-wave form, summed over waves and tiles; [96]: tiles
+#ifdef BGLU_DIAG   // diagnostic build only (-DBGLU_DIAG, timed with tools/time_bglu.py)
+__device__ unsigned long long g_bglu_slots[97];   // BGLU_SLOTSTAMP: shader cycles per slot, summed over waves and tiles; [96]: tiles
 #endif
 
 constexpr int popc(int m) { return m ? (m & 1) + popc(m >> 1) : 0; }
@@ -153,9 +153,9 @@ __device__ __forceinline__ float vmax(const float a, const float b) {
 // float operands behind the fragment areas: bl 0, br 32, bl0 64, br0 96, blc 128, brc 160, bc2 192 (64), nxb 256 (96), wc2v 352
 enum { F_BL = 0, F_BR = 32, F_BL0 = 64, F_BR0 = 96, F_BLC = 128, F_BRC = 160, F_BC2 = 192, F_NXB = 256, F_WC2V = 352 };
 
-template <int NT, int P1MASK, int C2, int NXN, bool IN4, int NP, bool PIPE>
+template <int NT, int P1MASK, int C2, int NXN, bool IN4, int NP>
 struct bglu_cfg {
-  static constexpr int WV = PIPE ? 4 : 8;
+  static constexpr int WV = 8;
   static constexpr int NB = IN4 ? 3 : 2 * NT;
   static constexpr int NT1 = popc(P1MASK), NB1 = 2 * NT1;
   static constexpr bool DUAL = P1MASK != 0;
@@ -166,12 +166,11 @@ struct bglu_cfg {
   static constexpr size_t lds_bytes = (size_t)o_f * sizeof(uint4) + BGLU_FLOATS * sizeof(float);
 };
 
-// PIPE true: 4 waves (one per SIMD, 512 registers), the K loop of tile i+1 interleaved with the tail of tile i.
-// PIPE false: 8 waves (two per SIMD, 256 registers), K loop and tail of the same tile one after the other - a wave issues at
-// most one instruction per four cycles, so two waves per SIMD double the issue rate and cover each other's stalls.
-template <int NT, int P1MASK, int C2, int NXN, bool IN4, int NP, bool PIPE, bool SPR = false>
-__global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(const pdse_bglu_desc d) {
-  using CF = bglu_cfg<NT, P1MASK, C2, NXN, IN4, NP, PIPE>;
+// 8 waves (two per SIMD, 256 registers), K loop and tail of the same tile one after the other - a wave issues at most one
+// instruction per four cycles, so two waves per SIMD double the issue rate and cover each other's stalls.
+template <int NT, int P1MASK, int C2, int NXN, bool IN4, int NP>
+__global__ __launch_bounds__(512, 2) void bglu_kernel(const pdse_bglu_desc d) {
+  using CF = bglu_cfg<NT, P1MASK, C2, NXN, IN4, NP>;
   constexpr int WV = CF::WV, NB = CF::NB, NB1 = CF::NB1, BS = CF::BS;
   constexpr bool DUAL = CF::DUAL;
   extern __shared__ uint4 img[];
@@ -279,10 +278,6 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl) in.pl[tap][q][pl] = bload16(r_in, ps.vin, soff_in(tap, q, pl));
   };
-  auto request_one = [&](const pos_t& ps, in_t& in, const int tap, const int q, const int pl) {   // one 16-byte load (spread schedules)
-    const __amdgpu_buffer_rsrc_t r_in = make_rsrc(d.hp + (int64_t)b * d.hp_sb, (uint32_t)d.hp_Tp * 4u * NP * (uint32_t)Fp * 16u);
-    in.pl[tap][q][pl] = bload16(r_in, ps.vin, soff_in(tap, q, pl));
-  };
   auto request_in4 = [&](const pos_t& ps, in_t& in) {
     // slot s = 2q + w: tap 4q + 2h + w of the ten (2,5) taps, channels (x 0, x 1, x_init 0, x_init 1); taps >= 10: zero
     in.live = 0;
@@ -305,14 +300,6 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
       in.raw[s_][3] = bload4(r_x1, o1 << 2, (int)(d.x1.sc << 2));
     }
   };
-  auto request_all = [&](const pos_t& ps, in_t& in) {
-    if constexpr (IN4) {
-      request_in4(ps, in);
-    } else {
-#pragma unroll
-      for (int tap = 0; tap < NT; ++tap) request_tap(ps, in, tap);
-    }
-  };
 
   struct acc_t {
     f32x16 L, R, L1, R1;
@@ -325,31 +312,6 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
     if constexpr (DUAL) {
       a.L1 = a.L;
       a.R1 = a.R;
-    }
-  };
-  auto kblock = [&](acc_t& a, const uint4 (&bp)[NP], const int tap, const int q) {
-    const int blk = (tap * 2 + q) * BS + lane;
-    a.L = mm<NP>(img + CF::o_gL + blk, bp, a.L);
-    a.R = mm<NP>(img + CF::o_gR + blk, bp, a.R);
-    if constexpr (DUAL) {
-      if ((P1MASK >> tap) & 1) {
-        const int blk1 = (rank_of(P1MASK, tap) * 2 + q) * BS + lane;
-        a.L1 = mm<NP>(img + CF::o_gL1 + blk1, bp, a.L1);
-        a.R1 = mm<NP>(img + CF::o_gR1 + blk1, bp, a.R1);
-      }
-    }
-  };
-  auto kloop_in4 = [&](acc_t& a, const in_t& in) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      float x[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = ((in.live >> (2 * q + (e >> 2))) & 1u) ? in.raw[2 * q + (e >> 2)][e & 3] : 0.f;
-      uint4 bp[NP];
-      split8p<NP>(x, bp, s_in);
-      const int blk = q * BS + lane;
-      a.L = mm<NP>(img + CF::o_gL + blk, bp, a.L);
-      a.R = mm<NP>(img + CF::o_gR + blk, bp, a.R);
     }
   };
 
@@ -380,16 +342,6 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
     for (int q = 0; q < 2; ++q)
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl) bstore16<BGLU_ST_AUX>(zp[q][pl], r_nx, o, ((2 * q * NP + pl) * nFp) << 4);
-  };
-  auto plane_off = [&](const bool ok, const int t, const int bin) -> uint32_t {
-    const int bi = bin + d.nx_f0;
-    const int bpos = d.nx_par ? (bi & 1) * ((nFp + 1) >> 1) + (bi >> 1) : bi;
-    return ok ? (uint32_t)b * item_hp + ((uint32_t)(((t + d.nx_t0) * 4 + h) * (NP * nFp) + bpos) << 4)
-              : (uint32_t)d.B * item_hp + ((uint32_t)(h * (NP * nFp)) << 4);
-  };
-  auto store_planes_q = [&](const uint4 (&zq)[NP], const uint32_t o, const int q) {   // K block q of a tile: its NP planes
-#pragma unroll
-    for (int pl = 0; pl < NP; ++pl) bstore16<BGLU_ST_AUX>(zq[pl], r_nx, o, ((2 * q * NP + pl) * nFp) << 4);
   };
   const __amdgpu_buffer_rsrc_t r_sk0 = make_rsrc(NXN > 1 ? d.nx_out[0] : nullptr, NXN > 1 ? (uint32_t)((d.B + 1) * d.nx_sb[0] * 4) : 0u);
   const __amdgpu_buffer_rsrc_t r_sk1 = make_rsrc(NXN > 2 ? d.nx_out[1] : nullptr, NXN > 2 ? (uint32_t)((d.B + 1) * d.nx_sb[1] * 4) : 0u);
@@ -448,7 +400,6 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
     f32x16 L, R, mL, mR, G, O0, O1, Z0, Z1, Z2;
     uint4 lp[2][NP], rp[2][NP], gp[2][NP], yp[2][2][NP], zp[2][NP];
     float v;
-    uint32_t zo, so;   // spread schedules: byte offsets of the addend loads / the plane stores of this phase
   };
   auto split_half = [&](const f32x16& X, const int s_, uint4 (&p)[NP], const float sc = 1.0f) {
     float x[8];
@@ -470,18 +421,6 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
       z[4 * q] = __uint_as_float(v.x), z[4 * q + 1] = __uint_as_float(v.y), z[4 * q + 2] = __uint_as_float(v.z), z[4 * q + 3] = __uint_as_float(v.w);
       if constexpr (NP == 2) z[4 * q] *= s_NXin, z[4 * q + 1] *= s_NXin, z[4 * q + 2] *= s_NXin, z[4 * q + 3] *= s_NXin;   // seeds an accumulator
     }
-  };
-
-  auto zoff = [&](const pos_t& ps, const int ph) -> uint32_t {
-    const bool two = ph == 0 || ps.j < d.Fout1;
-    const int bin0 = 2 * ps.j + (two ? ph : 0);
-    const int bin = d.skip_Fh ? (two ? ph : 0) * d.skip_Fh + ps.j : bin0;
-    return (uint32_t)(((int64_t)b * d.add_sb + (int64_t)ps.t * d.add_st + (int64_t)bin * d.add_sf + (int64_t)h * d.add_sc) << 2);
-  };
-  auto zload = [&](const uint32_t o, const int q, f32x16& z) {
-    const uint4 v = bload16(r_add, o, (int)((2 * q * d.add_sc) << 2));
-    z[4 * q] = __uint_as_float(v.x), z[4 * q + 1] = __uint_as_float(v.y), z[4 * q + 2] = __uint_as_float(v.z), z[4 * q + 3] = __uint_as_float(v.w);
-    if constexpr (NP == 2) z[4 * q] *= s_NXin, z[4 * q + 1] *= s_NXin, z[4 * q + 2] *= s_NXin, z[4 * q + 3] *= s_NXin;
   };
 
 #define FRAG(buf, ptr)                                         \
@@ -554,20 +493,6 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
     }                                                                                                  \
   }
 #define V_STSKIP(S, i) store_skip(S.Z##i, (i)-1, pc);
-#define V_ZOFF(S, ph) S.zo = zoff(pc, ph);
-#define V_ZLD(S, q) zload(S.zo, q, S.Z0);
-#define V_ST0Q(S, ph, q)                                                                                \
-  {                                                                                                    \
-    if ((q) == 0) S.so = DUAL ? plane_off(pc.valid && ((ph) == 0 || pc.j < d.Fout1), pc.t, 2 * pc.j + (ph)) : plane_off(pc.valid, pc.t, pc.j); \
-    store_planes_q(S.zp[q], S.so, q);                                                                  \
-    if constexpr (!DUAL) {                                                                             \
-      if ((q) == 1 && d.nx_row0) {                                                                     \
-        uint4 bp_[2][NP];                                                                              \
-        split16p<NP>(ld16(fop + F_NXB + 4 * h), bp_, s_NX);                                            \
-        store_planes(bp_, pc.valid && pc.t == 0, -1, pc.j);                                            \
-      }                                                                                                \
-    }                                                                                                  \
-  }
 #define V_DOT(S, ph)                                                              \
   {                                                                               \
     const f32x16 vw_ = ld16(fop + F_WC2V + 4 * h);                                \
@@ -586,8 +511,6 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
 #define REQ(tap) request_tap(p_req, in, tap);
 #define REQ_CUR(tap) request_tap(pc, in, tap);
 #define REQ_IN4() request_in4(p_req, in);
-#define REQ1(tap, q, pl) request_one(p_req, in, tap, q, pl);
-#define REQ_CUR1(tap, q, pl) request_one(pc, in, tap, q, pl);
 #define V_TAKE()          \
   {                       \
     SA.L = acc.L;         \
@@ -622,12 +545,6 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
 #define V_SZ(S, s_)
 #undef V_ZSEED
 #define V_ZSEED(S, ph)
-#undef V_ZOFF
-#undef V_ZLD
-#undef V_ST0Q
-#define V_ZOFF(S, ph)
-#define V_ZLD(S, q)
-#define V_ST0Q(S, ph, q)
 #define V_ST0(S, ph)
 #define V_STSKIP(S, i)
 #define V_DOT(S, ph)
@@ -683,7 +600,7 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
   unsigned long long dg_prev = 0;
   unsigned dg_tiles = 0;
 #define DG_SLOT(c_)                                                                 \
-  if constexpr (!PIPE) {                                                            \
+  {                                                                                 \
     const unsigned long long t_ = __builtin_amdgcn_s_memtime();                     \
     dg_slot[(c_) - dg_base - 1] += (unsigned)(t_ - dg_prev);                        \
     dg_prev = t_;                                                                   \
@@ -692,562 +609,73 @@ __global__ __launch_bounds__(PIPE ? 256 : 512, PIPE ? 1 : 2) void bglu_kernel(co
 #define DG_SLOT(c_)
 #endif
 
-  // ---- the software pipeline over this workgroup's rounds r_k = blockIdx.x + k gridDim.x
+  // ---- this workgroup's rounds r_k = blockIdx.x + k gridDim.x: K loop, then tail, per tile; the first two taps of the next
+  // tile are in flight during the tail
   const int stride = gridDim.x;
   int rd = blockIdx.x;
   if (rd >= nrounds) return;
-  if constexpr (PIPE) {
   pos_t pc, pn;
   in_t in;
-  acc_t accs[2];   // accumulators of the current / the next tile; the roles swap every iteration (the loop is unrolled twice:
-                   // as one body with "acc = accn" at its end hipcc copied all 64 accumulator registers per iteration)
+  acc_t acc;
   locate(rd, pc);
-  request_all(pc, in);
-  seed(pc, accs[0]);
   if constexpr (IN4) {
-    kloop_in4(accs[0], in);
+    request_in4(pc, in);
   } else {
-#pragma unroll
-    for (int tap = 0; tap < NT; ++tap)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) kblock(accs[0], in.pl[tap][q], tap, q);
+    request_tap(pc, in, 0);
+    request_tap(pc, in, 1);
   }
-  locate(rd + stride, pn);
-  request_all(pn, in);
-  constexpr int SCHED = IN4 ? 5 : (DUAL ? (C2 == 64 ? 1 : 2) : (NXN == 3 ? 3 : 4));
-#ifdef BGLU_DIAG
-  const unsigned long long dg_c0 = __builtin_amdgcn_s_memtime(), dg_r0 = __builtin_amdgcn_s_memrealtime();
-  unsigned dg_n = 0;
-#endif
-  // one iteration: tail of the current tile (vector instructions) beside the K loop of the next tile (matrix instructions),
-  // the requests of the tile after that behind each consumed tap - in the order of bglu_sched.inc.  Returns true after
-  // the last tile of this wave.
-  auto iteration = [&](auto PAR) __attribute__((always_inline)) -> bool {
-    constexpr int I = decltype(PAR)::value;
-    acc_t& acc = accs[I];
-    acc_t& accn = accs[1 - I];
-    pos_t pnn;
-    locate(rd + 2 * stride, pnn);
-    const pos_t& p_req = pnn;
+  constexpr int SCHED = 10 + (IN4 ? 5 : (DUAL ? (C2 == 64 ? 1 : 2) : (NXN == 3 ? 3 : 4)));
+  while (true) {
+    locate(rd + stride, pn);
+    const pos_t& p_req = pn;
     ph_t SA, SB;
     uint4 fr[2][NP];
     uint4 kb[IN4 ? 3 : 1][NP];
-    SA.L = acc.L;
-    SA.R = acc.R;
-    if constexpr (DUAL) {
-      SB.L = acc.L1;
-      SB.R = acc.R1;
-    }
-    seed(pn, accn);
+    seed(pc, acc);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (SCHED == 1) {
-#define BGLU_SCHED 1
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#ifdef BGLU_FORMS
-#include "bglu_sched_forms.inc"
+#if defined(BGLU_DIAG) && defined(BGLU_SLOTSTAMP)
+    dg_prev = __builtin_amdgcn_s_memtime();
+    ++dg_tiles;
 #endif
+    if constexpr (SCHED == 11) {
+#define BGLU_SCHED 11
+    [[maybe_unused]] constexpr int dg_base = __COUNTER__;
+#include "bglu_sched.inc"
 #undef BGLU_SCHED
-    } else if constexpr (SCHED == 2) {
-#define BGLU_SCHED 2
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#ifdef BGLU_FORMS
-#include "bglu_sched_forms.inc"
-#endif
+    } else if constexpr (SCHED == 12) {
+#define BGLU_SCHED 12
+    [[maybe_unused]] constexpr int dg_base = __COUNTER__;
+#include "bglu_sched.inc"
 #undef BGLU_SCHED
-    } else if constexpr (SCHED == 3) {
-#define BGLU_SCHED 3
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#ifdef BGLU_FORMS
-#include "bglu_sched_forms.inc"
-#endif
+    } else if constexpr (SCHED == 13) {
+#define BGLU_SCHED 13
+    [[maybe_unused]] constexpr int dg_base = __COUNTER__;
+#include "bglu_sched.inc"
 #undef BGLU_SCHED
-    } else if constexpr (SCHED == 4) {
-#define BGLU_SCHED 4
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#ifdef BGLU_FORMS
-#include "bglu_sched_forms.inc"
-#endif
+    } else if constexpr (SCHED == 14) {
+#define BGLU_SCHED 14
+    [[maybe_unused]] constexpr int dg_base = __COUNTER__;
+#include "bglu_sched.inc"
 #undef BGLU_SCHED
     } else {
-#define BGLU_SCHED 5
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#ifdef BGLU_FORMS
-#include "bglu_sched_forms.inc"
-#endif
+#define BGLU_SCHED 15
+    [[maybe_unused]] constexpr int dg_base = __COUNTER__;
+#include "bglu_sched.inc"
 #undef BGLU_SCHED
     }
     if constexpr (C2 == 1 || NXN == 0) stores_masked(pc, SA, SB);
     rd += stride;
-#ifdef BGLU_DIAG
-    ++dg_n;
-    if (rd >= nrounds && lane == 0) {
-      atomicAdd(&g_bglu_diag[0], __builtin_amdgcn_s_memtime() - dg_c0);
-      atomicAdd(&g_bglu_diag[1], __builtin_amdgcn_s_memrealtime() - dg_r0);
-      atomicAdd(&g_bglu_diag[2], (unsigned long long)dg_n);
-      atomicAdd(&g_bglu_diag[3], 1ull);
-    }
-#endif
-    pc = pn;
-    pn = pnn;
-    return rd >= nrounds;
-  };
-  while (true) {
-    if (iteration(std::integral_constant<int, 0>{})) break;
-    if (iteration(std::integral_constant<int, 1>{})) break;
-  }
-    return;
-  } else {
-    // ---- 8 waves: K loop, then tail, per tile; the first two taps of the next tile are in flight during the tail
-    pos_t pc, pn;
-    in_t in;
-    acc_t acc;
-    locate(rd, pc);
-    if constexpr (IN4) {
-      request_in4(pc, in);
-    } else {
-      request_tap(pc, in, 0);
-      request_tap(pc, in, 1);
-    }
-    constexpr int SCHED = ((SPR && !IN4) ? 20 : 10) + (IN4 ? 5 : (DUAL ? (C2 == 64 ? 1 : 2) : (NXN == 3 ? 3 : 4)));
-    while (true) {
-      locate(rd + stride, pn);
-      const pos_t& p_req = pn;
-      ph_t SA, SB;
-      uint4 fr[2][NP];
-      uint4 kb[IN4 ? 3 : 1][NP];
-      seed(pc, acc);
-      __builtin_amdgcn_sched_barrier(0);
-#if defined(BGLU_DIAG) && defined(BGLU_SLOTSTAMP)
-      dg_prev = __builtin_amdgcn_s_memtime();
-      ++dg_tiles;
-#endif
-      if constexpr (SCHED == 11) {
-#define BGLU_SCHED 11
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#include "bglu_sched.inc"
-#undef BGLU_SCHED
-      } else if constexpr (SCHED == 12) {
-#define BGLU_SCHED 12
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#include "bglu_sched.inc"
-#undef BGLU_SCHED
-      } else if constexpr (SCHED == 13) {
-#define BGLU_SCHED 13
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#include "bglu_sched.inc"
-#undef BGLU_SCHED
-      } else if constexpr (SCHED == 14) {
-#define BGLU_SCHED 14
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#include "bglu_sched.inc"
-#undef BGLU_SCHED
-      } else if constexpr (SCHED == 15) {
-#define BGLU_SCHED 15
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#include "bglu_sched.inc"
-#undef BGLU_SCHED
-      } else if constexpr (SCHED == 21) {
-#define BGLU_SCHED 21
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#ifdef BGLU_FORMS
-#include "bglu_sched_forms.inc"
-#endif
-#undef BGLU_SCHED
-      } else if constexpr (SCHED == 22) {
-#define BGLU_SCHED 22
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#ifdef BGLU_FORMS
-#include "bglu_sched_forms.inc"
-#endif
-#undef BGLU_SCHED
-      } else if constexpr (SCHED == 23) {
-#define BGLU_SCHED 23
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#ifdef BGLU_FORMS
-#include "bglu_sched_forms.inc"
-#endif
-#undef BGLU_SCHED
-      } else {
-#define BGLU_SCHED 24
-      [[maybe_unused]] constexpr int dg_base = __COUNTER__;
-#ifdef BGLU_FORMS
-#include "bglu_sched_forms.inc"
-#endif
-#undef BGLU_SCHED
-      }
-      if constexpr (C2 == 1 || NXN == 0) stores_masked(pc, SA, SB);
-      rd += stride;
-      if (rd >= nrounds) break;
-      pc = pn;
-    }
-#if defined(BGLU_DIAG) && defined(BGLU_SLOTSTAMP)
-    if (lane == 0) {
-#pragma unroll
-      for (int k_ = 0; k_ < 96; ++k_)
-        if (dg_slot[k_]) atomicAdd(&g_bglu_slots[k_], (unsigned long long)dg_slot[k_]);
-      atomicAdd(&g_bglu_slots[96], (unsigned long long)dg_tiles);
-    }
-#endif
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// 16-wave form (round 4).  What round 3 measured on the 8-wave form (profiles/r03_bglu_forms.txt): every unit of the CU busy
-// a quarter to a third of the time and the launch taking about the SUM - a wave spends 70 % of a tile queueing at the
-// vector-memory pipeline (loads 7k cycles away under load, stores sharing the in-order vmcnt), and with two waves per SIMD
-// nothing runs meanwhile.  The remedy named there was more independent waves per CU; what stood in the way was the
-// 256-register tail of the slot schedule, which keeps both phases' tails and all taps of a tile live at once to feed one
-// wave's matrix pipe.  This form trades that instruction-level overlap for thread-level overlap: 16 waves (four per SIMD,
-// <= 128 registers) share the same LDS weight image, and each wave runs a tile strictly in sequence - K loop of phase 0
-// (two taps in a register ring), tail of phase 0 with its values consumed as soon as they exist (one half-tile split
-// live at a time), then the same for phase 1 - so a wave that waits for memory, for LDS fragments or for an MFMA result
-// leaves the SIMD to three others.  Same descriptor, same image, same plane tensors, same roundings per element
-// (identical mm / split / gate expressions): results are bit-identical to the 8-wave form.
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int nth_tap(int m, int k) { return (m & 1) ? (k == 0 ? 0 : 1 + nth_tap(m >> 1, k - 1)) : 1 + nth_tap(m >> 1, k); }
-
-template <int NT, int P1MASK, int C2, int NXN, bool IN4, int NP, int WV>
-__global__ __launch_bounds__(64 * WV) void bglu16_kernel(const pdse_bglu_desc d) {
-  using CF = bglu_cfg<NT, P1MASK, C2, NXN, IN4, NP, false>;
-  constexpr int NB = CF::NB, NB1 = CF::NB1, NT1 = CF::NT1, BS = CF::BS;
-  constexpr bool DUAL = CF::DUAL;
-  static_assert(IN4 || (NT % 2 == 0 && NT1 % 2 == 0), "the two-slot tap ring assumes an even number of taps per phase");
-  extern __shared__ uint4 img[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int col = lane & 31, h = lane >> 5;
-  const int b = blockIdx.y;
-  const int P = d.Tout * d.Fout;
-
-  // ---- the LDS image (as bglu_kernel)
-  {
-    const uint4* const srcs[8] = {reinterpret_cast<const uint4*>(d.w0), reinterpret_cast<const uint4*>(d.w1),
-                                  reinterpret_cast<const uint4*>(d.w2), reinterpret_cast<const uint4*>(d.w3),
-                                  reinterpret_cast<const uint4*>(d.wlc), reinterpret_cast<const uint4*>(d.wrc),
-                                  reinterpret_cast<const uint4*>(d.wc2), reinterpret_cast<const uint4*>(d.nx_w)};
-    const int cnt[8] = {NB * NP, NB * NP, NB1 * NP, NB1 * NP, 2 * NP, 2 * NP, C2 == 64 ? 4 * NP : 0, NXN * 4 * NP};
-    constexpr int total = CF::o_f >> 6;
-    for (int c = __builtin_amdgcn_readfirstlane(wave); c < total; c += WV) {
-      int cc = c;
-      const uint4* src = nullptr;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (src == nullptr) {
-          if (cc < cnt[k]) src = srcs[k] + cc * 64;
-          else cc -= cnt[k];
-        }
-      }
-      glds16(src + lane, img + c * 64);
-    }
-    float* const fo = reinterpret_cast<float*>(img + CF::o_f);
-    for (int s = tid; s < BGLU_FLOATS; s += 64 * WV) {
-      const int k = s & 31;
-      float v = 0.f;
-      if (s < 32) v = d.bias0[(int64_t)b * d.bias_sb + k];
-      else if (s < 64) v = d.bias1[(int64_t)b * d.bias_sb + k];
-      else if (s < 96) v = (d.bias0_t0 ? d.bias0_t0 : d.bias0)[(int64_t)b * d.bias_sb + k];
-      else if (s < 128) v = (d.bias1_t0 ? d.bias1_t0 : d.bias1)[(int64_t)b * d.bias_sb + k];
-      else if (s < 160) v = d.blc[k];
-      else if (s < 192) v = d.brc[k];
-      else if (s < 256) v = (s - 192) < C2 ? d.bc2[s - 192] : 0.f;
-      else if (s < 352) {
-        const int i = (s - 256) >> 5;
-        v = (i < NXN && d.nx_bias[i]) ? d.nx_bias[i][(int64_t)b * d.nx_bias_sb[i] + k] : 0.f;
-      } else if (s < 384) v = (C2 == 1) ? d.wc2v[k] : 0.f;
-      fo[s] = v;
-    }
-  }
-  __syncthreads();
-  const float* const fop = reinterpret_cast<const float*>(img + CF::o_f);
-  const int ntiles = (P + 31) >> 5;
-  const int nrounds = (ntiles + WV - 1) / WV;
-
-  struct pos_t {
-    int t, j;
-    bool valid;
-    uint32_t vin;
-  };
-  const int Fp = d.hp_Fp;
-  auto locate = [&](const int rd, pos_t& ps) {
-    const int p = (rd * WV + wave) * 32 + col;
-    ps.valid = p < P;
-    const int pp = ps.valid ? p : 0;
-    ps.t = pp / d.Fout;
-    ps.j = pp - ps.t * d.Fout;
-    ps.vin = (uint32_t)(ps.t * (4 * NP * Fp) + h * (NP * Fp) + (d.hp_par ? ps.j : ps.j * d.sf_in)) << 4;
-  };
-  const int Fh = (Fp + 1) >> 1;
-  // byte offset of (tap, K block q, plane pl) = a per-tap base + a per-(q, pl) part, added where the load is issued: kept as
-  // one loop-invariant scalar per load (36 of them in the six-tap kernels) they overflow the scalar registers into vector lanes
-  auto tap_base = [&](const int tap) -> int {
-    const int bin0 = d.tap_df[tap] + d.hp_f0;
-    int tb = __builtin_amdgcn_readfirstlane((((d.tap_dt[tap] + d.hp_t0) * 4) * (NP * Fp) + (d.hp_par ? (bin0 & 1) * Fh + (bin0 >> 1) : bin0)) << 4);
-    asm volatile("" : "+s"(tb));   // opaque: the sums below stay inside the tile loop
-    return tb;
-  };
-  // one tap's planes [q][plane] into a ring slot
-  auto request_tap = [&](const pos_t& ps, uint4 (&sl)[2][NP], const int tap) {
-    const __amdgpu_buffer_rsrc_t r_in = make_rsrc(d.hp + (int64_t)b * d.hp_sb, (uint32_t)d.hp_Tp * 4u * NP * (uint32_t)Fp * 16u);
-    const int tb = tap_base(tap);
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int pl = 0; pl < NP; ++pl) sl[q][pl] = bload16(r_in, ps.vin, tb + (((2 * q) * NP + pl) * Fp << 4));
-  };
-  struct raw_t {
-    float raw[IN4 ? 6 : 1][4];
-    unsigned live;
-  };
-  auto request_in4 = [&](const pos_t& ps, raw_t& in) {
-    in.live = 0;
-    const __amdgpu_buffer_rsrc_t r_x0 = make_rsrc(d.x0.ptr, 0xfffffffcu), r_x1 = make_rsrc(d.x1.ptr, 0xfffffffcu);
-#pragma unroll
-    for (int s_ = 0; s_ < 6; ++s_) {
-      const int ta = 4 * (s_ >> 1) + (s_ & 1), tb = ta + 2;
-      const bool has_b = tb < 10, has_a = ta < 10;
-      const int dt = h ? (has_b ? d.tap_dt[tb < 10 ? tb : 0] : 0) : (has_a ? d.tap_dt[ta < 10 ? ta : 0] : 0);
-      const int df = h ? (has_b ? d.tap_df[tb < 10 ? tb : 0] : 0) : (has_a ? d.tap_df[ta < 10 ? ta : 0] : 0);
-      const bool has = h ? has_b : has_a;
-      const int tin = ps.t + dt, fin = ps.j * d.sf_in + df;
-      const bool inb = has && ps.valid && fin >= 0 && fin < d.Fin && tin >= 0 && tin < d.Tin;
-      if (inb) in.live |= 1u << s_;
-      const uint32_t o0 = inb ? (unsigned)((int64_t)b * d.x0.sb + (int64_t)tin * d.x0.st + (int64_t)fin * d.x0.sf) : 0u;
-      const uint32_t o1 = inb ? (unsigned)((int64_t)b * d.x1.sb + (int64_t)tin * d.x1.st + (int64_t)fin * d.x1.sf) : 0u;
-      in.raw[s_][0] = bload4(r_x0, o0 << 2, 0);
-      in.raw[s_][1] = bload4(r_x0, o0 << 2, (int)(d.x0.sc << 2));
-      in.raw[s_][2] = bload4(r_x1, o1 << 2, 0);
-      in.raw[s_][3] = bload4(r_x1, o1 << 2, (int)(d.x1.sc << 2));
-    }
-  };
-  auto seed = [&](const pos_t& ps, f32x16& L, f32x16& R) {
-    const bool f0 = ps.t == 0;
-    L = ld16(fop + (f0 ? F_BL0 : F_BL) + 4 * h);
-    R = ld16(fop + (f0 ? F_BR0 : F_BR) + 4 * h);
-  };
-
-  // ---- stores (as bglu_kernel)
-  const int nFp = d.nx_Fp;
-  const uint32_t item_hp = NXN > 0 ? (uint32_t)(d.nx_hp_sb * 2) : 0u;
-  const __amdgpu_buffer_rsrc_t r_nx = make_rsrc(NXN > 0 ? d.nx_hp : nullptr, NXN > 0 ? (uint32_t)(d.B + 1) * item_hp : 0u);
-  auto store_planes = [&](const uint4 (&zp)[2][NP], const bool ok, const int t, const int bin) {
-    const int bi = bin + d.nx_f0;
-    const int bpos = d.nx_par ? (bi & 1) * ((nFp + 1) >> 1) + (bi >> 1) : bi;
-    const uint32_t o = ok ? (uint32_t)b * item_hp + ((uint32_t)(((t + d.nx_t0) * 4 + h) * (NP * nFp) + bpos) << 4)
-                          : (uint32_t)d.B * item_hp + ((uint32_t)(h * (NP * nFp)) << 4);
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int pl = 0; pl < NP; ++pl) bstore16<BGLU_ST_AUX>(zp[q][pl], r_nx, o, ((2 * q * NP + pl) * nFp) << 4);
-  };
-  const __amdgpu_buffer_rsrc_t r_sk0 = make_rsrc(NXN > 1 ? d.nx_out[0] : nullptr, NXN > 1 ? (uint32_t)((d.B + 1) * d.nx_sb[0] * 4) : 0u);
-  const __amdgpu_buffer_rsrc_t r_sk1 = make_rsrc(NXN > 2 ? d.nx_out[1] : nullptr, NXN > 2 ? (uint32_t)((d.B + 1) * d.nx_sb[1] * 4) : 0u);
-  auto store_skip = [&](const f32x16& z, const int i, const pos_t& ps) {
-    const int jp = d.skip_Fh ? (ps.j & 1) * d.skip_Fh + (ps.j >> 1) : ps.j;
-    // 32-bit arithmetic: pdse_bglu_launch validates (B + 1) * nx_sb * 4 < 2^32
-    const uint32_t o = ((uint32_t)(ps.valid ? b : d.B) * (uint32_t)d.nx_sb[i] + (ps.valid ? (uint32_t)ps.t * (uint32_t)d.nx_st[i] + (uint32_t)jp * (uint32_t)d.nx_sf[i] : 0u) +
-                        (uint32_t)h * (uint32_t)d.nx_sc[i]) << 2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      bstore16<BGLU_ST_AUX>(make_uint4(__float_as_uint(z[4 * q]), __float_as_uint(z[4 * q + 1]), __float_as_uint(z[4 * q + 2]), __float_as_uint(z[4 * q + 3])),
-               i == 0 ? r_sk0 : r_sk1, o, (int)((2 * q * (uint32_t)d.nx_sc[i]) << 2));
-  };
-  const __amdgpu_buffer_rsrc_t r_add = make_rsrc((DUAL && NXN > 0) ? d.nx_add : nullptr, (DUAL && NXN > 0) ? (uint32_t)(d.B * d.add_sb * 4) : 0u);
-  auto zseed = [&](const pos_t& ps, const int ph, f32x16& z) {
-    const bool two = ph == 0 || ps.j < d.Fout1;
-    const int bin0 = 2 * ps.j + (two ? ph : 0);
-    const int bin = d.skip_Fh ? (two ? ph : 0) * d.skip_Fh + ps.j : bin0;
-    const uint32_t o = ((uint32_t)b * (uint32_t)d.add_sb + (uint32_t)ps.t * (uint32_t)d.add_st + (uint32_t)bin * (uint32_t)d.add_sf + (uint32_t)h * (uint32_t)d.add_sc) << 2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint4 v = bload16(r_add, o, (int)((2 * q * (uint32_t)d.add_sc) << 2));
-      z[4 * q] = __uint_as_float(v.x), z[4 * q + 1] = __uint_as_float(v.y), z[4 * q + 2] = __uint_as_float(v.z), z[4 * q + 3] = __uint_as_float(v.w);
-    }
-  };
-  auto split_half = [&](const f32x16& X, const int s_, uint4 (&p)[NP]) {
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = X[8 * s_ + j];
-    split8p<NP>(x, p);
-  };
-  const float slope = d.slope;
-
-  // ---- the tail of one output phase, values consumed as soon as they exist.  Returns the phase's output value for C2 == 1.
-  auto tail = [&](const pos_t& pc, auto PH, const f32x16& L, const f32x16& R) __attribute__((always_inline)) -> float {
-    constexpr int ph = decltype(PH)::value;
-    f32x16 mL = ld16(fop + F_BLC + 4 * h), mR = ld16(fop + F_BRC + 4 * h);
-#pragma unroll
-    for (int s_ = 0; s_ < 2; ++s_) {
-      uint4 p[NP];
-      split_half(L, s_, p);
-      mL = mm<NP>(img + CF::o_lc + s_ * BS + lane, p, mL);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int s_ = 0; s_ < 2; ++s_) {
-      uint4 p[NP];
-      split_half(R, s_, p);
-      mR = mm<NP>(img + CF::o_rc + s_ * BS + lane, p, mR);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    f32x16 G;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) G[r] = L[r] * sigm2(mR[r]) + R[r] * sigm2(mL[r]);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (C2 == 1) {
-      const f32x16 vw_ = ld16(fop + F_WC2V + 4 * h);
-      float part_ = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) part_ += vw_[r] * G[r];
-      const float v_ = part_ + __shfl_xor(part_, 32) + fop[F_BC2];
-      return vmax(v_, slope * v_);
-    } else {
-      f32x16 Z0;
-      if constexpr (DUAL && NXN > 0) zseed(pc, ph, Z0);           // the addend: in flight during conv2
-      f32x16 O0 = ld16(fop + F_BC2 + 4 * h), O1 = ld16(fop + F_BC2 + 32 + 4 * h);
-#pragma unroll
-      for (int s_ = 0; s_ < 2; ++s_) {
-        uint4 p[NP];
-        split_half(G, s_, p);
-        O0 = mm<NP>(img + CF::o_c2 + s_ * BS + lane, p, O0);
-        __builtin_amdgcn_sched_barrier(0);
-        O1 = mm<NP>(img + CF::o_c2 + (2 + s_) * BS + lane, p, O1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        O0[r] = vmax(O0[r], slope * O0[r]);
-        O1[r] = vmax(O1[r], slope * O1[r]);
-      }
-      if constexpr (NXN == 0) {
-        // the 64-channel block output itself (encoder stage 5 -> TCM): lane offset + a scalar channel offset per store
-        const __amdgpu_buffer_rsrc_t r_out = make_rsrc(d.out, pc.valid ? 0xfffffffcu : 0u);   // lanes without a position: out of range, dropped
-        const uint32_t o = (uint32_t)(((int64_t)b * d.out_sb + (int64_t)pc.t * d.out_st + (int64_t)pc.j * d.out_sf + d.out_off + (int64_t)(4 * h) * d.out_sc) << 2);
-#pragma unroll
-        for (int m2 = 0; m2 < 2; ++m2)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) bstore4<0>((m2 ? O1 : O0)[r], r_out, o, (int)(((32 * m2 + PDSE_KR(r)) * d.out_sc) << 2));
-      } else {
-        uint4 yp[2][2][NP];
-        split_half(O0, 0, yp[0][0]);
-        split_half(O0, 1, yp[0][1]);
-        split_half(O1, 0, yp[1][0]);
-        split_half(O1, 1, yp[1][1]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < NXN; ++i) {
-          f32x16 Z;
-          if constexpr (DUAL) Z = Z0;                              // DUAL: one chained tile, seeded by the encoder's skip half
-          else Z = ld16(fop + F_NXB + 32 * i + 4 * h);
-#pragma unroll
-          for (int m2 = 0; m2 < 2; ++m2)
-#pragma unroll
-            for (int s_ = 0; s_ < 2; ++s_) {
-              Z = mm<NP>(img + CF::o_nx + (i * 4 + m2 * 2 + s_) * BS + lane, yp[m2][s_], Z);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          if (i == 0) {
-            uint4 zp[2][NP];
-            split16p<NP>(Z, zp);
-            if constexpr (DUAL) {
-              store_planes(zp, pc.valid && (ph == 0 || pc.j < d.Fout1), pc.t, 2 * pc.j + ph);
-            } else {
-              store_planes(zp, pc.valid, pc.t, pc.j);
-              if (d.nx_row0) {   // uniform: the explicit pad frame of the next encoder stage = the folded bias
-                uint4 bp_[2][NP];
-                split16p<NP>(ld16(fop + F_NXB + 4 * h), bp_);
-                store_planes(bp_, pc.valid && pc.t == 0, -1, pc.j);
-              }
-            }
-          } else {
-            store_skip(Z, i - 1, pc);
-          }
-        }
-      }
-      return 0.f;
-    }
-  };
-
-  const int stride = gridDim.x;
-  int rd = blockIdx.x;
-  if (rd >= nrounds) return;
-  pos_t pc, pn;
-  locate(rd, pc);
-  uint4 ring[2][2][NP];   // two taps: [slot][q][plane]
-  raw_t raw;
-  if constexpr (IN4) request_in4(pc, raw);
-  else request_tap(pc, ring[0], 0);
-  while (true) {
-    locate(rd + stride, pn);
-    f32x16 L, R;
-    seed(pc, L, R);
-    if constexpr (IN4) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        float x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = ((raw.live >> (2 * q + (e >> 2))) & 1u) ? raw.raw[2 * q + (e >> 2)][e & 3] : 0.f;
-        uint4 kb[NP];
-        split8p<NP>(x, kb);
-        L = mm<NP>(img + CF::o_gL + q * BS + lane, kb, L);
-        __builtin_amdgcn_sched_barrier(0);
-        R = mm<NP>(img + CF::o_gR + q * BS + lane, kb, R);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      request_in4(pn, raw);                                        // the next tile's gathers: in flight during this tile's tail
-      __builtin_amdgcn_sched_barrier(0);
-    } else {
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        if (i + 1 < NT) request_tap(pc, ring[(i + 1) & 1], i + 1);
-        else if constexpr (DUAL) request_tap(pc, ring[0], nth_tap(P1MASK, 0));   // phase 1's first tap: in flight during tail 0
-        else request_tap(pn, ring[0], 0);                                         // the next tile's first tap
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          L = mm<NP>(img + CF::o_gL + (i * 2 + q) * BS + lane, ring[i & 1][q], L);
-          __builtin_amdgcn_sched_barrier(0);
-          R = mm<NP>(img + CF::o_gR + (i * 2 + q) * BS + lane, ring[i & 1][q], R);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-    const float v0 = tail(pc, std::integral_constant<int, 0>{}, L, R);
-    float v1 = 0.f;
-    if constexpr (DUAL) {
-      seed(pc, L, R);
-#pragma unroll
-      for (int k = 0; k < NT1; ++k) {
-        if (k + 1 < NT1) request_tap(pc, ring[(k + 1) & 1], nth_tap(P1MASK, k + 1));
-        else request_tap(pn, ring[0], 0);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          L = mm<NP>(img + CF::o_gL1 + (k * 2 + q) * BS + lane, ring[k & 1][q], L);
-          __builtin_amdgcn_sched_barrier(0);
-          R = mm<NP>(img + CF::o_gR1 + (k * 2 + q) * BS + lane, ring[k & 1][q], R);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      v1 = tail(pc, std::integral_constant<int, 1>{}, L, R);
-    }
-    if constexpr (C2 == 1) {
-      if (pc.valid && h == 0) {
-        float* const po = d.out + ((int64_t)b * d.out_sb + (int64_t)pc.t * d.out_st + (int64_t)pc.j * d.out_sf + d.out_off);
-        if constexpr (DUAL) {
-          const bool two = pc.j < d.Fout1;
-          const int64_t bin = d.out_sf >> 1;
-          if (two && bin == 1) store_pair(po, v0, v1);
-          else {
-            po[0] = v0;
-            if (two) po[bin] = v1;
-          }
-        } else {
-          po[0] = v0;
-        }
-      }
-    }
-    rd += stride;
     if (rd >= nrounds) break;
     pc = pn;
   }
+#if defined(BGLU_DIAG) && defined(BGLU_SLOTSTAMP)
+  if (lane == 0) {
+#pragma unroll
+    for (int k_ = 0; k_ < 96; ++k_)
+      if (dg_slot[k_]) atomicAdd(&g_bglu_slots[k_], (unsigned long long)dg_slot[k_]);
+    atomicAdd(&g_bglu_slots[96], (unsigned long long)dg_tiles);
+  }
+#endif
 }
 
 // fp32 [B, 32, T, F] -> planes (the first decoder stage's standalone conv1 output)
@@ -1325,9 +753,9 @@ __global__ __launch_bounds__(256) void planes_conv_kernel(const pdse_planes_desc
     for (int pl = 0; pl < NP; ++pl) base[(2 * q * NP + pl) * d.hp_Fp] = p[q][pl];
 }
 
-template <int NT, int P1MASK, int C2, int NXN, bool IN4, int NP, bool PIPE, bool SPR = false>
-int launch_(const pdse_bglu_desc* d, hipStream_t s) {
-  using CF = bglu_cfg<NT, P1MASK, C2, NXN, IN4, NP, PIPE>;
+template <int NT, int P1MASK, int C2, int NXN, bool IN4, int NP>
+int launch(const pdse_bglu_desc* d, hipStream_t s) {
+  using CF = bglu_cfg<NT, P1MASK, C2, NXN, IN4, NP>;
   const int P = d->Tout * d->Fout;
   const int rounds = (((P + 31) >> 5) + CF::WV - 1) / CF::WV;
   static const int wgs = PDSE_DIAG_ENV("PDSE_BGLU_WGS") ? atoi(PDSE_DIAG_ENV("PDSE_BGLU_WGS")) : 256;
@@ -1338,20 +766,17 @@ int launch_(const pdse_bglu_desc* d, hipStream_t s) {
     pdse_set_error("bglu: LDS image too large");
     return 1;
   }
-  const void* fn = (const void*)bglu_kernel<NT, P1MASK, C2, NXN, IN4, NP, PIPE, SPR>;
+  const void* fn = (const void*)bglu_kernel<NT, P1MASK, C2, NXN, IN4, NP>;
   static unsigned long long attr_mask = 0;   // per instantiation and device
   if (pdse_lds_attr(fn, &attr_mask, "bglu lds attribute")) return 1;
 #ifdef BGLU_DIAG
-  unsigned long long z[4] = {0, 0, 0, 0};
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bglu_diag), z, sizeof(z));
   static unsigned long long zs[97];
   for (int k = 0; k < 97; ++k) zs[k] = 0;
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bglu_slots), zs, sizeof(zs));
 #endif
-  hipLaunchKernelGGL((bglu_kernel<NT, P1MASK, C2, NXN, IN4, NP, PIPE, SPR>), dim3(gx, d->B, 1), dim3(64 * CF::WV), CF::lds_bytes, s, *d);
+  hipLaunchKernelGGL((bglu_kernel<NT, P1MASK, C2, NXN, IN4, NP>), dim3(gx, d->B, 1), dim3(64 * CF::WV), CF::lds_bytes, s, *d);
 #ifdef BGLU_DIAG
   (void)hipStreamSynchronize(s);
-  (void)hipMemcpyFromSymbol(z, HIP_SYMBOL(g_bglu_diag), sizeof(z));
   (void)hipMemcpyFromSymbol(zs, HIP_SYMBOL(g_bglu_slots), sizeof(zs));
   if (zs[96]) {
     fprintf(stderr, "bglu slots NT %d P1 %d C2 %d NXN %d NP %d (cycles per slot and tile, %llu tiles):", NT, P1MASK, C2, NXN, NP, zs[96]);
@@ -1363,49 +788,8 @@ int launch_(const pdse_bglu_desc* d, hipStream_t s) {
       }
     fprintf(stderr, " | sum %.0f\n", tot);
   }
-  if (z[3]) fprintf(stderr, "bglu diag NT %d P1 %d C2 %d NXN %d NP %d: %.0f cycles per iteration, %.2f iterations per wave, clock %.0f MHz\n", NT, P1MASK, C2, NXN, NP,
-                    (double)z[0] / (double)z[2], (double)z[2] / (double)z[3], (double)z[0] / (double)z[1] * 100.0);
 #endif
   return pdse_check_launch("bglu");
-}
-
-int g_bglu_form = -1;   // pdse_bglu_set_form: -1 = chosen per geometry (default), 0 = 8 waves, 1 = 4 waves pipelined, 2 = 16 waves, 3 = 12 waves
-
-#ifdef BGLU_FORMS
-template <int NT, int P1MASK, int C2, int NXN, bool IN4, int NP, int WV>
-int launch16_(const pdse_bglu_desc* d, hipStream_t s) {
-  using CF = bglu_cfg<NT, P1MASK, C2, NXN, IN4, NP, false>;
-  const int P = d->Tout * d->Fout;
-  const int rounds = (((P + 31) >> 5) + WV - 1) / WV;
-  int gx = (256 + d->B - 1) / d->B;
-  if (gx > rounds) gx = rounds;
-  if (gx < 1) gx = 1;
-  if (CF::lds_bytes > 160 * 1024) {
-    pdse_set_error("bglu: LDS image too large");
-    return 1;
-  }
-  const void* fn = (const void*)bglu16_kernel<NT, P1MASK, C2, NXN, IN4, NP, WV>;
-  static unsigned long long attr_mask = 0;   // per instantiation and device
-  if (pdse_lds_attr(fn, &attr_mask, "bglu16 lds attribute")) return 1;
-  hipLaunchKernelGGL((bglu16_kernel<NT, P1MASK, C2, NXN, IN4, NP, WV>), dim3(gx, d->B, 1), dim3(64 * WV), CF::lds_bytes, s, *d);
-  return pdse_check_launch("bglu16");
-}
-
-#endif
-
-template <int NT, int P1MASK, int C2, int NXN, bool IN4, int NP>
-int launch(const pdse_bglu_desc* d, hipStream_t s) {
-  // measured (profiles/r03_bglu_forms.txt, B=32, T=401): the 8-wave form is 10-25 % faster than the pipelined 4-wave form
-  // on every geometry and for both plane counts: a wave issues at most one instruction per four cycles whatever its type,
-  // so two waves per SIMD double the issue rate, which the interleaving inside one wave does not make up for
-#ifdef BGLU_FORMS   // the forms that were measured and not kept (profiles/r03_bglu_forms.txt, r04_bglu_forms.txt): diagnostic builds only
-  const int form = NP == 2 ? -1 : g_bglu_form;   // the experimental forms know the bf16 plane counts only
-  if (form == 1) return launch_<NT, P1MASK, C2, NXN, IN4, NP, true>(d, s);
-  if (form == 2) return launch16_<NT, P1MASK, C2, NXN, IN4, NP, 16>(d, s);
-  if (form == 3) return launch16_<NT, P1MASK, C2, NXN, IN4, NP, 12>(d, s);
-  if (form == 4) return launch_<NT, P1MASK, C2, NXN, IN4, NP, false, !IN4>(d, s);
-#endif
-  return launch_<NT, P1MASK, C2, NXN, IN4, NP, false>(d, s);
 }
 
 template <int NP>
@@ -1523,14 +907,10 @@ int pdse_bglu_launch(const pdse_bglu_desc* d, hipStream_t s) {
 }
 
 int pdse_bglu_set_form(int form) {
-#ifdef BGLU_FORMS
-  const int top = 4;
-#else
-  const int top = 0;   // the product library holds the 8-wave form only
-#endif
-  if (form < -1 || form > top) return -2;
-  const int prev = g_bglu_form;
-  g_bglu_form = form;
+  static int cur = -1;   // the library holds one form (8 waves): -1 and 0 both name it
+  if (form < -1 || form > 0) return -2;
+  const int prev = cur;
+  cur = form;
   return prev;
 }
 

@@ -448,7 +448,7 @@ static int launch3(const pdse_gconv_desc* d, hipStream_t s) {
   const int P = d->Tout * d->Fout;
   const int rounds = ((P + 31) / 32 + WV - 1) / WV;
   // one workgroup per CU holds the image: about 256 persistent workgroups in all, each walking its share of its item's rounds
-  static const int wgs = getenv("PDSE_S3_WGS") ? atoi(getenv("PDSE_S3_WGS")) : 256;
+  static const int wgs = PDSE_DIAG_ENV("PDSE_S3_WGS") ? atoi(PDSE_DIAG_ENV("PDSE_S3_WGS")) : 256;
   int gx = (wgs + d->B - 1) / d->B;
   if (gx > rounds || !PERSIST) gx = rounds;
   if (gx < 1) gx = 1;
@@ -520,7 +520,7 @@ int pdse_gconv3_launch(const pdse_gconv_desc* d, hipStream_t s) {
   // Waves per workgroup of the single-phase (encoder) blocks: 16 (1024 threads, four waves per SIMD at <= 128 registers,
   // one tap in flight) when a batch item has enough position tiles to fill such workgroups (measured 229 -> 180 us on
   // the 401 x 39 stage), else 8.  PDSE_S3_WAVES = 8 | 16 overrides (tuning / diagnostics).
-  static const int wv_env = getenv("PDSE_S3_WAVES") ? atoi(getenv("PDSE_S3_WAVES")) : 0;
+  static const int wv_env = PDSE_DIAG_ENV("PDSE_S3_WAVES") ? atoi(PDSE_DIAG_ENV("PDSE_S3_WAVES")) : 0;
   const int tiles = (d->Tout * d->Fout + 31) / 32;
   const bool wv16 = wv_env == 16 || (wv_env != 8 && tiles >= 100);
   if (d->w2 != nullptr) {
@@ -531,7 +531,7 @@ int pdse_gconv3_launch(const pdse_gconv_desc* d, hipStream_t s) {
     // transposed (two-phase) blocks always run 8 waves: a 16-wave form (the phases one after the other on one accumulator
     // pair to fit 128 registers, odd-phase taps gathered and split a second time) measured the same - 213 vs 211 us on
     // the 401 x 40 stage, 340 vs 346 us on the last stage - and was dropped
-    static const bool pf_off = getenv("PDSE_S3_PF") && atoi(getenv("PDSE_S3_PF")) == 0;   // tuning: one tap in flight
+    static const bool pf_off = PDSE_DIAG_ENV("PDSE_S3_PF") && atoi(PDSE_DIAG_ENV("PDSE_S3_PF")) == 0;   // tuning: one tap in flight
     if (d->ntaps == 4 && d->p1mask == 5) {
       if (d->nx_n) return pf_off ? launch3<4, 5, true, 8, false>(d, s) : launch3<4, 5, true, 8>(d, s);
       return launch3<4, 5, false, 8, false>(d, s);

@@ -15,7 +15,8 @@
 //     output tile per wave, 32 frames per workgroup, h rows of 768 B gathered at 16 B per lane) pulled 960 KB + its
 //     line overfetch per CU through that path in phase A alone: 30,000 of its 52,000 cycles, the same 37 us per
 //     block as the fp32 kernel.  Hence: every operand fragment is loaded by exactly one wave of the workgroup, and a
-//     workgroup covers 64 frames (NT = 2) once 32-frame workgroups would outnumber the CUs;
+//     workgroup covers one tile of 32 frames (64-frame workgroups, which halve the weight bytes per CU, measured slower:
+//     see pdse_tcm2_launch);
 //   * A  wave (branch, kq): both output tiles of one branch over a quarter of K = 5 taps x 64 channels (5 K blocks;
 //        each A fragment feeds NT frame tiles, each B fragment both output tiles), operands two K blocks ahead in
 //        registers; the quarters meet in LDS in two steps (fixed order);
@@ -147,8 +148,9 @@ __device__ long long* g_trace = nullptr;   // PDSE_TCM2_TRACE=1 (diagnostic): [w
   } while (0)
 
 // NT = frame tiles of 32 per wave, TW = teams of 8 waves per workgroup (workgroup = 32 NT TW frames of one utterance).
-// The teams of a workgroup run the same instruction stream on neighbouring frames between the same barriers, so
-// their weight requests reach the CU's L1 together.
+// Both kernels below instantiate NT = TW = 1, the shape that measured fastest (pdse_tcm2_launch).  The body stays written
+// over NT and TW: with the two folded by hand hipcc emits other code for the same block (the team index is a run-time value
+// behind readfirstlane; scalars in place of the one-element arrays select other instructions: 114 -> 118 registers at NP = 3).
 // One residual block for the frame tile(s) of this workgroup.  HSA: cache policy of the hs loads - 0 for one launch per block, 16
 // (sc1) inside the persistent stack kernel, where hs was written by other workgroups of the SAME launch (tcm2s_kernel below).
 struct tcm2_nowait {
@@ -475,14 +477,14 @@ __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const
   STAMP(7);
 }
 
-template <int MODE, int NT, int TW, int NP = 3>
-__global__ __launch_bounds__(512 * TW, NT == 1 ? 4 : 2) void tcm2_kernel(const pdse_tcm2_desc d) {
+template <int MODE, int NP>
+__global__ __launch_bounds__(512, 4) void tcm2_kernel(const pdse_tcm2_desc d) {
   // par: [64][4] main bias, mask bias, BN scale, BN shift of the gate | [256] conv2 bias | [64] next conv1 bias |
   //      [64][4] next block's input transforms: main scale, shift, mask scale, shift
   __shared__ __attribute__((aligned(16))) float par[832];
-  __shared__ float part_[TW * NT][4][64][33];                                    // A: [2 branch + kh]; C: partial sums of four waves
-  __shared__ __attribute__((aligned(16))) char gls_[TW * NT][NP * 32 * GL_ROW];   // conv2's B operand: [plane][frame][64 + 8 bf16]
-  tcm2_block<MODE, NT, TW, NP, 0>(d, par, part_, gls_);
+  __shared__ float part_[1][4][64][33];                                    // A: [2 branch + kh]; C: partial sums of four waves
+  __shared__ __attribute__((aligned(16))) char gls_[1][NP * 32 * GL_ROW];   // conv2's B operand: [plane][frame][64 + 8 bf16]
+  tcm2_block<MODE, 1, 1, NP, 0>(d, par, part_, gls_);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -550,11 +552,11 @@ __global__ __launch_bounds__(512, 4) void tcm2s_kernel(const pdse_tcm2s_desc s) 
   }
 }
 
-template <int NT, int TW, int NP>
+template <int NP>
 int launch_tcm2(const pdse_tcm2_desc* d, hipStream_t s) {
-  const dim3 grid((d->T + 32 * NT * TW - 1) / (32 * NT * TW), d->B);
+  const dim3 grid((d->T + 31) / 32, d->B);
   static long long* tbuf = nullptr;
-  const size_t nst = (size_t)grid.x * grid.y * 64 * TW;
+  const size_t nst = (size_t)grid.x * grid.y * 64;
   // (diagnostic builds only) the trace buffer holds 65536 * 64 stamps: larger launches are not traced
   static const bool tracing_env = PDSE_DIAG_ENV("PDSE_TCM2_TRACE") != nullptr;
   const bool tracing = tracing_env && nst <= (size_t)65536 * 64;
@@ -565,8 +567,8 @@ int launch_tcm2(const pdse_tcm2_desc* d, hipStream_t s) {
     }
     (void)hipMemsetAsync(tbuf, 0, nst * sizeof(long long), s);
   }
-  if (d->mode == 1) hipLaunchKernelGGL((tcm2_kernel<1, NT, TW, NP>), grid, dim3(512 * TW), 0, s, *d);
-  else hipLaunchKernelGGL((tcm2_kernel<0, NT, TW, NP>), grid, dim3(512 * TW), 0, s, *d);
+  if (d->mode == 1) hipLaunchKernelGGL((tcm2_kernel<1, NP>), grid, dim3(512), 0, s, *d);
+  else hipLaunchKernelGGL((tcm2_kernel<0, NP>), grid, dim3(512), 0, s, *d);
   if (tracing) {   // diagnostic: per-phase shader-clock averages over all waves, and the spread of start times (100 MHz clock)
     (void)hipStreamSynchronize(s);
     long long* h = (long long*)malloc(nst * sizeof(long long));
@@ -580,7 +582,7 @@ int launch_tcm2(const pdse_tcm2_desc* d, hipStream_t s) {
       if (q[0] > w1) w1 = q[0];
       for (int k = 2; k < 8; ++k) sum[k] += q[k] ? (double)(q[k] - q[1]) : 0.0;
     }
-    fprintf(stderr, "tcm2 trace mode %d NT %d TW %d dil %d: start spread %.2f us; cycles since wave start:", d->mode, NT, TW, d->dil, (w1 - w0) * 0.01);
+    fprintf(stderr, "tcm2 trace mode %d dil %d: start spread %.2f us; cycles since wave start:", d->mode, d->dil, (w1 - w0) * 0.01);
     for (int k = 2; k < 8; ++k) fprintf(stderr, " %.0f", sum[k] / nw);
     fprintf(stderr, "\n");
     free(h);
@@ -628,20 +630,12 @@ int pdse_tcm2_launch(const pdse_tcm2_desc* d, hipStream_t s) {
     REQ(d->hs && d->x_out && d->wbr && d->wc2, "tcm2: null pointer");
     REQ(d->hs_out != d->hs, "tcm2: hs_out must not alias hs (other workgroups gather from hs)");
   }
-  // workgroup shape 10 NT + TW.  Measured at B=32, T=401 (us per forward, 18 blocks): 11 -> 592, 21 (64 frames, two
-  // tiles per wave) -> 730, 12 (64 frames, two teams of 8 waves) -> 769: the shapes that halve the weight bytes per
-  // CU lose more to their longer dependent chains / simultaneous identical requests.  PDSE_TCM2_SHAPE: ablation.
+  // 32 frames per 8-wave workgroup: 592 us per forward at B=32, T=401, against 730 (two tiles per wave) and 769 (two teams of 8 waves)
   REQ(d->np == 0 || d->np == 3 || d->np == 2 || d->np == 1, "tcm2: np is 3 (exact splits; 0 means 3), 2 (f16x2) or 1 (plain bf16)");
-  if (d->np == 1) return launch_tcm2<1, 1, 1>(d, s);   // the opt-in bf16 mode
+  if (d->np == 1) return launch_tcm2<1>(d, s);   // the opt-in bf16 mode
   if (d->np == 2) {
     REQ(d->qexp[0] >= -40 && d->qexp[0] <= 40 && d->qexp[1] >= -40 && d->qexp[1] <= 40 && d->qexp[2] >= -40 && d->qexp[2] <= 40, "tcm2: qexp out of range");
-    return launch_tcm2<1, 1, 2>(d, s);
+    return launch_tcm2<2>(d, s);
   }
-  static const int force = PDSE_DIAG_ENV("PDSE_TCM2_SHAPE") ? atoi(PDSE_DIAG_ENV("PDSE_TCM2_SHAPE")) : 0;
-  const int shape = force ? force : 11;
-  switch (shape) {
-    case 12: return launch_tcm2<1, 2, 3>(d, s);
-    case 21: return launch_tcm2<2, 1, 3>(d, s);
-    default: return launch_tcm2<1, 1, 3>(d, s);
-  }
+  return launch_tcm2<3>(d, s);
 }

@@ -1,10 +1,10 @@
-"""Builds a DIAGNOSTIC libpdse (never the product library) with extra compile-time switches, e.g. the block-kernel forms that were
-measured and not kept:
+"""Builds a DIAGNOSTIC libpdse (never the product library) with extra compile-time switches:
 
-    python tools/build_diag.py -o /tmp/libpdse_forms.so -DBGLU_FORMS
-    PDSE_LIB=/tmp/libpdse_forms.so BGLU_FORM=3 python tools/time_bglu.py
+    python tools/build_diag.py -o /tmp/libpdse_diag.so -DPDSE_DIAG                    # the trace / ablation environment hooks
+    python tools/build_diag.py -o /tmp/libpdse_slots.so -DBGLU_DIAG -DBGLU_SLOTSTAMP  # the block kernel's per-slot clock stamps
+    PDSE_LIB=/tmp/libpdse_slots.so python tools/time_bglu.py
 
-(-DPDSE_DIAG: trace / mask environment hooks; -DBGLU_DIAG -DBGLU_SLOTSTAMP, -DBGLU_NO_MM ...: README.md.)"""
+(-DBGLU_NO_MM / NO_REQ / ...: the block kernel's timing ablations, README.md.)"""
 import os
 import subprocess
 import sys

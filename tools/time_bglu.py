@@ -102,10 +102,6 @@ DEC = [(0, 0), (0, -1), (-1, 0), (-1, -1)]
 DEC1 = [(0, 0), (0, -1), (0, -2), (-1, 0), (-1, -1), (-1, -2)]
 ENC = [(-1, 0), (-1, 1), (-1, 2), (0, 0), (0, 1), (0, 2)]
 if __name__ == "__main__":
-    form = int(os.environ.get("BGLU_FORM", "-1"))       # pdse_bglu_set_form: 0 = 8 waves, 1 = 4 waves pipelined, 2 = 16 waves, 3 = 12 waves
-    if L.load().pdse_bglu_set_form(form) == -2:
-        sys.exit("this libpdse.so holds the product form only: build with -DBGLU_FORMS (HIPCC_FLAGS) to time the others")
-    print("kernel form %d" % form, flush=True)
     for NP in (3, 1):
         for Fin in (4, 9, 19, 39):
             bench("decoder (4 taps, dual, nx 1)", 4, 5, 64, 1, Fin, Fin + 1, Fin, 1, DEC, NP)
