@@ -228,6 +228,10 @@ typedef struct pdse_wavprep_desc {
   float* c;         /* [B] */
   const int32_t* lens;
   int32_t B, L, pad, normalize; /* normalize 0: c = 1 */
+  /* reflect_own 1 (with lens; exact ragged batches): the right-hand reflection sits at the utterance's own end,
+   *   xpad[b][pad + len_b + j] = x[len_b - 2 - j] / c for j < pad, zeros behind (len_b clamped to pad + 1 .. L);
+   * frames t < 1 + len_b / hop of the STFT are then those of the utterance alone.  0 (default): reflect at L. */
+  int32_t reflect_own, pad_;
 } pdse_wavprep_desc;
 
 /* overlap-add of windowed inverse-DFT frames, window-envelope normalisation, trim, rescale
@@ -238,6 +242,11 @@ typedef struct pdse_ola_desc {
   const float* c;    /* [B] or NULL */
   float* out;        /* [B][L] */
   int32_t B, T, L, n_fft, hop, pad_;
+  /* exact ragged batches (both NULL: every utterance has T frames and L samples): frames t >= nframes[b] contribute neither
+   * to the sum nor to the window envelope, samples n >= lens[b] are written as zeros - torch.istft(length = lens[b]) of
+   * the utterance's own frames.  Device int32 [B] each, clamped to 0 .. T and 0 .. L. */
+  const int32_t* nframes;
+  const int32_t* lens;
 } pdse_ola_desc;
 
 /* forward noising of the training step (trainer/complex_ddpm_trainer.py:707-729), a = sqrt(alpha_bar_t),
@@ -280,6 +289,9 @@ typedef struct pdse_sigma_desc {
   float* maxbuf; /* [B*2] scratch */
   int64_t plane;
   int32_t nplanes, pad_;
+  /* exact ragged batches: valid[p] (device int32 [nplanes], NULL: plane) leading elements of plane p take part in the
+   * abs-max and are scaled (the utterance's own frames x F); the elements behind them are copied from a unscaled. */
+  const int32_t* valid;
 } pdse_sigma_desc;
 
 /* LayerNorm over the last dim of [B][T][N] rows with a strided/transposed store
@@ -548,6 +560,9 @@ typedef struct pdse_tcm_desc {
   const float* bn1;
   float slope_main, slope_mask, slope2;
   int32_t dil, B, T;
+  /* exact ragged batches: frames[b] (device int32 [B], NULL: T) own frames of utterance b - BN(PReLU(h)) reads as zero at
+   * t >= frames[b], the dilated convolutions' zero padding at the utterance's own end */
+  const int32_t* frames;
 } pdse_tcm_desc;
 
 /* The same residual block in split-bf16 arithmetic (csrc/tcm2.hip; exact three-way bf16 splits, six products, fp32
@@ -578,6 +593,10 @@ typedef struct pdse_tcm2_desc {
                             round to nearest even: the opt-in bf16 mode) or 2 (ABI 8, f16x2: fp16 hi + lo of the operand scaled by
                             a power of two - hs by 2^PDSE_F16_ACT_EXP, the weights by 2^qexp) - hs is [B][2][4][2][np][T + 128][8] */
   int32_t qexp[3];       /* np == 2: exponents of wbr (both branches), wc2, wn1 (packing.f16_wexp); par stays in true scale */
+  /* exact ragged batches: frames[b] (device int32 [B], NULL: T) own frames of utterance b - hs_out is STORED AS ZEROS at
+   * frames[b] <= t < T (the dilated convolutions' zero padding at the utterance's own end; stored, not skipped: the hs
+   * buffers outlive a pass).  The blocks of one stack launch share one table. */
+  const int32_t* frames;
 } pdse_tcm2_desc;
 
 /* The residual blocks of the TCM stack as ONE launch (ABI 6, csrc/tcm2.hip: tcm2s_kernel): blk[0..n-1] are the mode-0

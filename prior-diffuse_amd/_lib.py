@@ -72,17 +72,18 @@ class CompandDesc(C.Structure):
 
 class WavprepDesc(C.Structure):
     _fields_ = [("wav", _fp), ("xpad", _fp), ("c", _fp), ("lens", _fp),
-                ("B", _i32), ("L", _i32), ("pad", _i32), ("normalize", _i32)]
+                ("B", _i32), ("L", _i32), ("pad", _i32), ("normalize", _i32), ("reflect_own", _i32), ("pad_", _i32)]
 
 
 class OlaDesc(C.Structure):
     _fields_ = [("frames", _fp), ("win2", _fp), ("c", _fp), ("out", _fp),
-                ("B", _i32), ("T", _i32), ("L", _i32), ("n_fft", _i32), ("hop", _i32), ("pad_", _i32)]
+                ("B", _i32), ("T", _i32), ("L", _i32), ("n_fft", _i32), ("hop", _i32), ("pad_", _i32),
+                ("nframes", _fp), ("lens", _fp)]
 
 
 class SigmaDesc(C.Structure):
     _fields_ = [("init", _fp), ("a", _fp), ("out", _fp), ("maxbuf", _fp), ("plane", _i64),
-                ("nplanes", _i32), ("pad_", _i32)]
+                ("nplanes", _i32), ("pad_", _i32), ("valid", _fp)]
 
 
 class LnDesc(C.Structure):
@@ -171,13 +172,15 @@ class TransposeDesc(C.Structure):
 class TcmDesc(C.Structure):
     _fields_ = [("x", _fp), ("h", _fp), ("x_out", _fp), ("h_out", _fp), ("wbr", _fp), ("bmain", _fp), ("bmask", _fp),
                 ("xf", _fp), ("wc2", _fp), ("bc2", _fp), ("xf2", _fp), ("wn1", _fp), ("bn1", _fp),
-                ("slope_main", _f32), ("slope_mask", _f32), ("slope2", _f32), ("dil", _i32), ("B", _i32), ("T", _i32)]
+                ("slope_main", _f32), ("slope_mask", _f32), ("slope2", _f32), ("dil", _i32), ("B", _i32), ("T", _i32),
+                ("frames", _fp)]
 
 
 class Tcm2Desc(C.Structure):
     _fields_ = [("x", _fp), ("x_out", _fp), ("hs", _fp), ("hs_out", _fp), ("wbr", _fp), ("wc2", _fp), ("wn1", _fp),
                 ("par", _fp), ("slope2", _f32), ("slope_main_next", _f32), ("slope_mask_next", _f32),
-                ("dil", _i32), ("B", _i32), ("T", _i32), ("mode", _i32), ("np", _i32), ("qexp", _i32 * 3)]
+                ("dil", _i32), ("B", _i32), ("T", _i32), ("mode", _i32), ("np", _i32), ("qexp", _i32 * 3),
+                ("frames", _fp)]
 
 
 TCM2S_MAX = 20

@@ -218,6 +218,18 @@ __global__ __launch_bounds__(1024) void wavprep_kernel(const pdse_wavprep_desc d
   if (tid == 0 && d.c) d.c[b] = c;
   const int Lp = d.L + 2 * d.pad;
   float* o = d.xpad + (size_t)b * Lp;
+  if (d.reflect_own && d.lens) {
+    // exact ragged batches: reflect at the utterance's own end, zeros behind the reflected tail
+    const int len = min(max(d.lens[b], d.pad + 1), d.L);
+    for (int i = tid; i < Lp; i += 1024) {
+      int k = i - d.pad;
+      if (k < 0) k = -k;
+      const bool tail = k >= len + d.pad;
+      if (k >= len) k = tail ? 0 : 2 * (len - 1) - k;
+      o[i] = tail ? 0.f : x[k] / c;
+    }
+    return;
+  }
   for (int i = tid; i < Lp; i += 1024) {
     int k = i - d.pad;
     if (k < 0) k = -k;
@@ -237,6 +249,8 @@ int pdse_wavprep_launch(const pdse_wavprep_desc* d, hipStream_t s) {
 // Overlap-add + envelope normalisation + centre trim + rescale (torch.istft, :1010-1016).
 // frames[b][n][t] already carry the synthesis window; every output sample sums two frames.
 // ---------------------------------------------------------------------------------------
+// RAGGED (exact ragged batches): utterance b owns nframes[b] frames and lens[b] samples; the dense form is the code it was.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void ola_kernel(const pdse_ola_desc d) {
   const int64_t total = (int64_t)d.B * d.L;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -244,11 +258,19 @@ __global__ __launch_bounds__(256) void ola_kernel(const pdse_ola_desc d) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     const int b = (int)(i / d.L);
     const int n = (int)(i - (int64_t)b * d.L) + half;  // index in the un-trimmed signal
+    int Tb = d.T;
+    if constexpr (RAGGED) {
+      if (d.nframes) Tb = min(max(d.nframes[b], 0), d.T);
+      if (d.lens && n - half >= min(max(d.lens[b], 0), d.L)) {
+        d.out[i] = 0.f;
+        continue;
+      }
+    }
     float acc = 0.f, env = 0.f;
     // frames t with 0 <= n - t*hop < n_fft
     const int t_hi = n / d.hop;
     for (int t = t_hi; t >= 0 && n - t * d.hop < d.n_fft; --t) {
-      if (t < d.T) {
+      if (t < Tb) {
         const int r = n - t * d.hop;
         acc += d.frames[((size_t)b * d.n_fft + r) * d.T + t];
         env += d.win2[r];
@@ -265,7 +287,10 @@ int pdse_ola_launch(const pdse_ola_desc* d, hipStream_t s) {
   REQ(d->B > 0 && d->T > 0 && d->L > 0 && d->n_fft > 0 && d->hop > 0, "ola: bad sizes");
   int64_t blocks = ((int64_t)d->B * d->L + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(ola_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *d);
+  if (d->nframes || d->lens)
+    hipLaunchKernelGGL(ola_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, *d);
+  else
+    hipLaunchKernelGGL(ola_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, *d);
   return pdse_check_launch("ola");
 }
 
@@ -276,8 +301,9 @@ int pdse_ola_launch(const pdse_ola_desc* d, hipStream_t s) {
 __global__ __launch_bounds__(256) void sigma_max_kernel(const pdse_sigma_desc d) {
   const int pl = blockIdx.y;
   const float* x = d.init + (size_t)pl * d.plane;
+  const int64_t live = d.valid ? min((int64_t)max(d.valid[pl], 0), d.plane) : d.plane;
   float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < d.plane; i += (int64_t)gridDim.x * 256)
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < live; i += (int64_t)gridDim.x * 256)
     m = fmaxf(m, fabsf(x[i]));
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o));
   if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned int*>(d.maxbuf) + pl, __float_as_uint(m));
@@ -287,13 +313,16 @@ __global__ __launch_bounds__(256) void sigma_apply_kernel(const pdse_sigma_desc 
   const int pl = blockIdx.y;
   const float mx = d.maxbuf[pl];
   const size_t base = (size_t)pl * d.plane;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < d.plane; i += (int64_t)gridDim.x * 256) {
+  const int64_t live = d.valid ? min((int64_t)max(d.valid[pl], 0), d.plane) : d.plane;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < live; i += (int64_t)gridDim.x * 256) {
 #pragma clang fp contract(off)
     float m = fabsf(d.init[base + i]) / mx;
     m = m * 0.5f;
     m = m + 0.5f;
     d.out[base + i] = d.a[base + i] * sqrtf(m);
   }
+  // behind an utterance's own frames (exact ragged batches): the state is carried over unscaled
+  for (int64_t i = live + (int64_t)blockIdx.x * 256 + threadIdx.x; i < d.plane; i += (int64_t)gridDim.x * 256) d.out[base + i] = d.a[base + i];
 }
 
 int pdse_sigma_launch(const pdse_sigma_desc* d, hipStream_t s) {

@@ -39,6 +39,8 @@ __device__ __forceinline__ float prelu_f(float v, float slope) { return v > 0.f 
 
 // Addressing: every global access is (wave-uniform base pointer) + (one of a few 32-bit lane offsets), so the
 // compiler keeps the bases in SGPRs and no per-access 64-bit vector arithmetic or address registers are needed.
+// RAGGED (exact ragged batches, pdse_tcm_desc.frames): the transformed h reads as zero from the utterance's own end on.
+template <bool RAGGED>
 __global__ __launch_bounds__(256, 2) void tcm_block_kernel(const pdse_tcm_desc d) {
   __shared__ float xfs[64][4];          // per input channel: scale/shift of the main and of the mask branch
   __shared__ float gpar[64][4];         // per gate channel: main bias, mask bias, BN scale, BN shift (conv2 input)
@@ -77,10 +79,12 @@ __global__ __launch_bounds__(256, 2) void tcm_block_kernel(const pdse_tcm_desc d
   const float* hb = d.h + (size_t)b * 64 * T;
   int loff[5];        // lane offsets of the five taps: channel parity row + clamped frame
   bool tv[5];
+  int Tb = T;         // frames the taps may read: the utterance's own
+  if constexpr (RAGGED) Tb = min(max(d.frames[b], 0), T);
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     const int tt = t + (k - 2) * d.dil;
-    tv[k] = tt >= 0 && tt < T;
+    tv[k] = tt >= 0 && tt < Tb;
     loff[k] = hh * T + min(max(tt, 0), T - 1);
   }
   float raw[80];
@@ -246,6 +250,9 @@ int pdse_tcm_launch(const pdse_tcm_desc* d, hipStream_t s) {
   REQ(!d->h_out || (d->wn1 && d->bn1), "tcm: the chained conv1 needs its weights and bias");
   REQ(d->h_out != d->h, "tcm: h_out must not alias h (other workgroups gather from h)");
   REQ(d->B > 0 && d->B <= 65535 && d->T > 0 && d->dil > 0, "tcm: bad sizes");
-  hipLaunchKernelGGL(tcm_block_kernel, dim3((d->T + 31) / 32, d->B), dim3(256), 0, s, *d);
+  if (d->frames)
+    hipLaunchKernelGGL(tcm_block_kernel<true>, dim3((d->T + 31) / 32, d->B), dim3(256), 0, s, *d);
+  else
+    hipLaunchKernelGGL(tcm_block_kernel<false>, dim3((d->T + 31) / 32, d->B), dim3(256), 0, s, *d);
   return pdse_check_launch("tcm");
 }

@@ -141,6 +141,11 @@ __device__ __forceinline__ void split4n(const float (&x)[4], uint2 (&p)[NP], con
   else p[0] = make_uint2(pack_bf16_rne(x[0], x[1]), pack_bf16_rne(x[2], x[3]));
 }
 
+// two idle issue slots behind a wide store, ordered behind the store and in front of every later write of its data registers
+__device__ __forceinline__ void store_pad(const uint4& x) {
+  asm volatile("s_nop 1" ::"v"(x.x), "v"(x.y), "v"(x.z), "v"(x.w) : "memory");
+}
+
 __device__ long long* g_trace = nullptr;   // PDSE_TCM2_TRACE=1 (diagnostic): [workgroup][wave][8] clock stamps
 #define STAMP(i)                                                                                       \
   do {                                                                                                 \
@@ -159,7 +164,8 @@ struct tcm2_nowait {
 
 // hs_ready(): called once, by every thread, after the block's first weight requests have gone out and before the first hs request
 // (the stack kernel waits for the neighbours' progress counters there, with the weight fetch already in flight).
-template <int MODE, int NT, int TW, int NP, int HSA, typename Wait = tcm2_nowait>
+// RAGGED (exact ragged batches, pdse_tcm2_desc.frames): hs_out is stored as zeros from the utterance's own end on.
+template <int MODE, int NT, int TW, int NP, int HSA, bool RAGGED, typename Wait = tcm2_nowait>
 __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const par, float (*const part_)[4][64][33],
                                            char (*const gls_)[NP * 32 * GL_ROW], const Wait hs_ready = Wait()) {
   int tid_ = threadIdx.x & 511;                                                  // within the team
@@ -448,6 +454,8 @@ __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const
   __syncthreads();
   // 8 channels (one fragment half) x one frame per thread: 16-byte stores, 512 contiguous bytes per 32 lanes
   const __amdgpu_buffer_rsrc_t r_ho = make_rsrc((char*)d.hs_out + (size_t)(b * 2) * (8 * NP) * (TP * 16), (uint32_t)(16 * NP * TP * 16));
+  [[maybe_unused]] int Tb = T;
+  if constexpr (RAGGED) Tb = min(max(d.frames[b], 0), T);
   for (int item = tid; item < NT * 256; item += 512) {
     const int n = item >> 8, cg = (item >> 5) & 7, f = item & 31;
     const int t = t0 + 32 * n + f;
@@ -462,29 +470,41 @@ __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const
         const f32x4 xp = *(const f32x4*)&par[576 + 4 * c];
         vm[i] = xp[0] * prelu2(s, d.slope_main_next) + xp[1];
         vk[i] = xp[2] * prelu2(s, d.slope_mask_next) + xp[3];
+        if constexpr (RAGGED) {   // behind the utterance's own frames the dilated convolutions read their zero padding
+          if (t >= Tb) vm[i] = vk[i] = 0.f;
+        }
       }
       const int plane = TP * 16;
       const uint32_t ho = (uint32_t)(cg * NP * plane + (t + HS_PAD) * 16);
       uint4 pq[NP];
       split8n<NP>(vm, pq, s_pl);
 #pragma unroll
-      for (int p = 0; p < NP; ++p) bstore16<TCM2_ST_AUX>(pq[p], r_ho, ho, p * plane);
+      for (int p = 0; p < NP; ++p) {
+        bstore16<TCM2_ST_AUX>(pq[p], r_ho, ho, p * plane);
+        // a 16-byte store with a scalar offset reads its data registers up to two issue slots behind it, and hipcc pads that case
+        // for stores without one only (tests/test_isa_guards.py); in the masked form the second split followed at once.  The
+        // pad names the stored registers as inputs, so nothing may overwrite them in front of it.
+        if constexpr (RAGGED) store_pad(pq[p]);
+      }
       split8n<NP>(vk, pq, s_pl);
 #pragma unroll
-      for (int p = 0; p < NP; ++p) bstore16<TCM2_ST_AUX>(pq[p], r_ho, ho, (8 * NP + p) * plane);
+      for (int p = 0; p < NP; ++p) {
+        bstore16<TCM2_ST_AUX>(pq[p], r_ho, ho, (8 * NP + p) * plane);
+        if constexpr (RAGGED) store_pad(pq[p]);
+      }
     }
   }
   STAMP(7);
 }
 
-template <int MODE, int NP>
+template <int MODE, int NP, bool RAGGED>
 __global__ __launch_bounds__(512, 4) void tcm2_kernel(const pdse_tcm2_desc d) {
   // par: [64][4] main bias, mask bias, BN scale, BN shift of the gate | [256] conv2 bias | [64] next conv1 bias |
   //      [64][4] next block's input transforms: main scale, shift, mask scale, shift
   __shared__ __attribute__((aligned(16))) float par[832];
   __shared__ float part_[1][4][64][33];                                    // A: [2 branch + kh]; C: partial sums of four waves
   __shared__ __attribute__((aligned(16))) char gls_[1][NP * 32 * GL_ROW];   // conv2's B operand: [plane][frame][64 + 8 bf16]
-  tcm2_block<MODE, 1, 1, NP, 0>(d, par, part_, gls_);
+  tcm2_block<MODE, 1, 1, NP, 0, RAGGED>(d, par, part_, gls_);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -509,7 +529,7 @@ __global__ __launch_bounds__(512, 4) void tcm2_kernel(const pdse_tcm2_desc d) {
 // ---------------------------------------------------------------------------------------------------------------
 #define TCM2S_SPINS 60000   // polls of one neighbour counter before a workgroup gives up (~50-100 ms)
 
-template <int NP>
+template <int NP, bool RAGGED>
 __global__ __launch_bounds__(512, 4) void tcm2s_kernel(const pdse_tcm2s_desc s) {
   __shared__ __attribute__((aligned(16))) float par[832];
   __shared__ float part_[1][4][64][33];
@@ -539,7 +559,7 @@ __global__ __launch_bounds__(512, 4) void tcm2s_kernel(const pdse_tcm2s_desc s) 
       __syncthreads();   // the neighbours' block i - 1 is visible to every wave
       gave_up = dead != 0;
     };
-    tcm2_block<0, 1, 1, NP, 16>(s.blk[i], par, part_, gls_, wait);
+    tcm2_block<0, 1, 1, NP, 16, RAGGED>(s.blk[i], par, part_, gls_, wait);
     // a workgroup that gave up still ran the block (on whatever hs held): every barrier of the block was reached by all waves;
     // it records the failure and leaves before publishing, so its neighbours give up at their next wait
     if (gave_up) {
@@ -567,8 +587,14 @@ int launch_tcm2(const pdse_tcm2_desc* d, hipStream_t s) {
     }
     (void)hipMemsetAsync(tbuf, 0, nst * sizeof(long long), s);
   }
-  if (d->mode == 1) hipLaunchKernelGGL((tcm2_kernel<1, NP>), grid, dim3(512), 0, s, *d);
-  else hipLaunchKernelGGL((tcm2_kernel<0, NP>), grid, dim3(512), 0, s, *d);
+  const bool ragged = d->frames != nullptr && d->hs_out != nullptr;   // the table masks hs_out only
+  if (d->mode == 1) {
+    if (ragged) hipLaunchKernelGGL((tcm2_kernel<1, NP, true>), grid, dim3(512), 0, s, *d);
+    else hipLaunchKernelGGL((tcm2_kernel<1, NP, false>), grid, dim3(512), 0, s, *d);
+  } else {
+    if (ragged) hipLaunchKernelGGL((tcm2_kernel<0, NP, true>), grid, dim3(512), 0, s, *d);
+    else hipLaunchKernelGGL((tcm2_kernel<0, NP, false>), grid, dim3(512), 0, s, *d);
+  }
   if (tracing) {   // diagnostic: per-phase shader-clock averages over all waves, and the spread of start times (100 MHz clock)
     (void)hipStreamSynchronize(s);
     long long* h = (long long*)malloc(nst * sizeof(long long));
@@ -609,13 +635,18 @@ int pdse_tcm2s_launch(const pdse_tcm2s_desc* d, hipStream_t s) {
     // i - 1 READ, i.e. the one block i - 2 wrote (two buffers, strictly alternating)
     REQ(!k.hs_out || k.hs_out == (i >= 2 ? d->blk[i - 2].hs_out : (i == 1 ? d->blk[0].hs : k.hs_out)), "tcm2s: the hs buffers must alternate strictly");
     REQ(k.x != k.x_out, "tcm2s: x and x_out of a block differ (other tiles never read them, but a tile's waves do)");
+    REQ(k.frames == d->blk[0].frames, "tcm2s: the blocks of one stack share one frames table");
   }
   const int ntiles = (T + 31) / 32;
   if (pdse_check_hip(hipMemsetAsync(d->flags, 0, (size_t)B * ntiles * sizeof(int), s), "tcm2s: memset")) return 1;
   const dim3 grid(ntiles, B);
-  if (np == 1) hipLaunchKernelGGL((tcm2s_kernel<1>), grid, dim3(512), 0, s, *d);
-  else if (np == 2) hipLaunchKernelGGL((tcm2s_kernel<2>), grid, dim3(512), 0, s, *d);
-  else hipLaunchKernelGGL((tcm2s_kernel<3>), grid, dim3(512), 0, s, *d);
+  if (d->blk[0].frames) {
+    if (np == 1) hipLaunchKernelGGL((tcm2s_kernel<1, true>), grid, dim3(512), 0, s, *d);
+    else if (np == 2) hipLaunchKernelGGL((tcm2s_kernel<2, true>), grid, dim3(512), 0, s, *d);
+    else hipLaunchKernelGGL((tcm2s_kernel<3, true>), grid, dim3(512), 0, s, *d);
+  } else if (np == 1) hipLaunchKernelGGL((tcm2s_kernel<1, false>), grid, dim3(512), 0, s, *d);
+  else if (np == 2) hipLaunchKernelGGL((tcm2s_kernel<2, false>), grid, dim3(512), 0, s, *d);
+  else hipLaunchKernelGGL((tcm2s_kernel<3, false>), grid, dim3(512), 0, s, *d);
   return pdse_check_launch("tcm2s");
 }
 

@@ -40,6 +40,9 @@ def parse_args_and_config(argv=None):
     p.add_argument("--audit-range", action="store_true",
                    help="(not a flag of the reference) audit every f16x2 pass on the device: a geometry with a tensor wholly below the fp16 "
                         "window is repeated on bf16x3, like one that overflowed it")
+    p.add_argument("--batch", type=int, default=1,
+                   help="(not a flag of the reference) --generate: enhance this many files per pass as exact ragged batches - every file's "
+                        "result and noise are those of the one-file loop (priors GCRN and DiffUNet); default 1: one file per pass")
     args = p.parse_args(argv)
     args.log = os.path.join(args.assets, "log", args.doc)
     args.checkpoint = os.path.join(args.assets, "checkpoint", args.doc)
@@ -68,7 +71,7 @@ def main(argv=None):
         raise NotImplementedError("only ComplexDDPMTrainer's sampling path is built")
     trainer = ComplexDDPMTrainer(args, config)
     if args.generate:
-        return trainer.generate_wav(load_pre_train=True, data_path=args.data)
+        return trainer.generate_wav(load_pre_train=True, data_path=args.data, batch=args.batch)
     trainer.train_ddpm()
 
 

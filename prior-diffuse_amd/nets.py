@@ -450,8 +450,11 @@ class EpsNetPlan(PlanBase):
     NSLOT = 20  # 15 stages + en1 real-row bias + 4 composed encoder-stage-1 biases (l/r x frame >= 1 / frame 0)
 
     def __init__(self, ctx, sd, B, T, time_cond=True, nsteps=1, plan=None, table=None, with_pre=None, split_bf16=None,
-                 planes=None, plane_h=None, exclusive=False):
+                 planes=None, plane_h=None, exclusive=False, frames=None):
         """with_pre False + time_cond True: ``Nocon`` (model/piror_grad.py), DiffUNet1 without Preprocess.
+        frames: device int32 [B] owned by the caller, every utterance's own frame count (exact ragged batches): the TCM launches
+        are recorded with the table and zero their bottleneck tensor from an utterance's own end on - the only place where this
+        network looks forward in time (the BiConv(Trans)GLU blocks look back one frame).  None: the dense launches.
         exclusive: the plan owns the GPU while it runs (one batch in flight): the TCM stack then runs as one persistent launch
         (``tcm_stack``; bit-identical results).  With several batches in flight the persistent workgroups keep CUs from the other
         batches' block kernels while they wait for their neighbours - measured 17.8 instead of 17.4 ms per pass - so the
@@ -471,6 +474,9 @@ class EpsNetPlan(PlanBase):
             self.plane_h = True
         self.tcm_planes = 3 if (self.planes == 2 and not self.TCM_F16) else self.planes
         self.use_tcm_stack = bool(self.tcm_stack and exclusive)
+        self.frames = frames
+        if frames is not None and (self.force_generic or not self.fused_tcm):
+            raise ValueError("exact ragged batches need a fused TCM form (csrc/tcm.hip, csrc/tcm2.hip): the three-launch form has no frames table")
         self.sd = sd
         ok = (self.split_bf16 and self.chain_conv1 and self.compose_stage1 and time_cond and with_pre and not self.force_generic
               and all(float(P._np(sd[k])[0]) <= 1.0 for k in sd if k.endswith(".weight") and P._np(sd[k]).shape == (1,)))
@@ -840,6 +846,7 @@ class EpsNetPlan(PlanBase):
         if p_next is not None:
             d.h_out = hout.data_ptr()
         d.dil, d.B, d.T = dil, self.B, self.T
+        d.frames = Ctx.ptr(self.frames)
         self.add(d, TAG_TCM)
 
     def _residual_split(self, p, dil, xin, xout, hin, hout, p_next, mode=0):
@@ -885,6 +892,7 @@ class EpsNetPlan(PlanBase):
         if p_next is not None:
             d.hs_out = hout.data_ptr()
         d.dil, d.B, d.T, d.mode, d.np = dil, self.B, self.T, mode, self.tcm_planes
+        d.frames = Ctx.ptr(self.frames)
         if mode == 0 and self._tcm_stack is not None:
             self._tcm_stack.append(d)          # collected: one pdse_tcm2s_desc for the whole stack (build_step)
         else:
@@ -1563,8 +1571,9 @@ class StftPlan(PlanBase):
     """wav [B,L] -> c [B], compressed spectrogram [B,2,T,161]
     (trainer/complex_ddpm_trainer.py:921-937)."""
 
-    def __init__(self, ctx, B, L_, plan=None, normalize=True, split_bf16=False):
-        """split_bf16: the framing GEMM on the bf16 matrix cores with exact three-way operand splits (csrc/gconv4.hip)."""
+    def __init__(self, ctx, B, L_, plan=None, normalize=True, split_bf16=False, reflect_own=False):
+        """split_bf16: the framing GEMM on the bf16 matrix cores with exact three-way operand splits (csrc/gconv4.hip).
+        reflect_own: exact ragged batches - the right-hand reflect padding sits at every utterance's own end (``lens``)."""
         super().__init__(ctx, plan, ns=("stft", bool(split_bf16)))
         self.split_bf16 = bool(split_bf16)
         if L_ <= 160:
@@ -1579,6 +1588,7 @@ class StftPlan(PlanBase):
         ctx.keep.append(self.lens)
         self.feat = ctx.alloc(B, 2, self.T, F0)
         self.normalize = normalize
+        self.reflect_own = bool(reflect_own)
 
     def build(self, feat=None):
         B, L_, T = self.B, self.L, self.T
@@ -1586,6 +1596,7 @@ class StftPlan(PlanBase):
         d = L.WavprepDesc()
         d.wav, d.xpad, d.c, d.lens = self.wav.data_ptr(), self.xpad.data_ptr(), self.c.data_ptr(), self.lens.data_ptr()
         d.B, d.L, d.pad, d.normalize = B, L_, 160, 1 if self.normalize else 0
+        d.reflect_own = 1 if self.reflect_own else 0
         self.add(d, TAG_SIGNAL)
         Lp = L_ + 320
         # a frame's 320 samples as 320 "channels" of stride 1 at position 160 j: one GEMM [B T, 320] x [320, 322] (as 320
@@ -1604,8 +1615,11 @@ class IstftPlan(PlanBase):
     """compressed spectrogram [B,2,T,161] -> wav [B,L] * c
     (trainer/complex_ddpm_trainer.py:1004-1016)."""
 
-    def __init__(self, ctx, B, T, L_, plan=None, split_bf16=False):
+    def __init__(self, ctx, B, T, L_, plan=None, split_bf16=False, frames=None, lens=None):
+        """frames, lens: device int32 [B] owned by the caller (exact ragged batches): the overlap-add takes an utterance's own
+        frames only and writes zeros behind its own samples."""
         super().__init__(ctx, plan, ns=("istft", bool(split_bf16)))
+        self.frames_tab, self.lens_tab = frames, lens
         self.split_bf16 = bool(split_bf16)
         self.B, self.T, self.L = B, T, L_
         self.spec = ctx.alloc(B, 2, T, F0)
@@ -1629,6 +1643,7 @@ class IstftPlan(PlanBase):
         o = L.OlaDesc()
         o.frames, o.win2, o.c, o.out = (self.frames.data_ptr(), self.win2.data_ptr(), Ctx.ptr(c), self.wav.data_ptr())
         o.B, o.T, o.L, o.n_fft, o.hop = B, T, self.L, 320, 160
+        o.nframes, o.lens = Ctx.ptr(self.frames_tab), Ctx.ptr(self.lens_tab)
         self.add(o, TAG_SIGNAL)
         return self.wav
 

@@ -23,6 +23,31 @@ from .schedule import inference_schedule, step_coefficients
 F0 = 161
 
 
+RAGGED_PRIORS = ("GCRN", "DiffUNet")
+
+
+def ragged_args(prior_name, L_):
+    """Argument check of ``SamplerPipeline(ragged=True)``, without a device."""
+    if prior_name not in RAGGED_PRIORS:
+        raise ValueError("exact ragged batches: prior %r attends and runs a bidirectional GRU over all T frames of the padded batch, "
+                         "so padding reaches every frame of an utterance (supported priors: %s)" % (prior_name, ", ".join(RAGGED_PRIORS)))
+    if L_ is None:
+        raise ValueError("exact ragged batches need the signal front / back end (pass L_)")
+
+
+def ragged_tables(lens, B, L_):
+    """lens (one int for all, or B of them) -> (lens, frames) as int32 arrays, frames = 1 + lens // 160; ValueError for a
+    length outside 161 .. L_ (the centred STFT reflects 160 samples) or a list that is not B long.  Host only."""
+    lens_h = np.asarray(lens, dtype=np.int64).reshape(-1)
+    if lens_h.size == 1 and B != 1:
+        lens_h = np.repeat(lens_h, B)
+    if lens_h.size != B:
+        raise ValueError("lens: expected %d lengths, got %d" % (B, lens_h.size))
+    if lens_h.min() < 161 or lens_h.max() > L_:
+        raise ValueError("lens: every length must lie in 161 .. %d (the padded length), got %d .. %d" % (L_, lens_h.min(), lens_h.max()))
+    return lens_h.astype(np.int32), (1 + lens_h // 160).astype(np.int32)
+
+
 def _expect(t, like, name):
     """Inputs must have exactly the geometry the plan was recorded for (``copy_`` would silently broadcast)."""
     if tuple(t.shape) != tuple(like.shape) or t.dtype != like.dtype:
@@ -35,7 +60,7 @@ class SamplerPipeline:
 
     def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, T=None, L_=None, fast_sampling=True,
                  use_sigma=False, params=default_params, with_signal=None, deltamu=False, cond="init", bank=None,
-                 split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False):
+                 split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False, ragged=False):
         """deltamu: the alternative parameterisation of utils/params.py:36 — ddpm_sd is a ``Nocon`` state_dict,
         x_T = noise + X_init/11 (:947-948), eps = Nocon(x, t) (:970-971), no final ``+ X_init`` (:995).
         cond (deltamu False): what conditions DiffUNet1 — "init": X_init/11 (pirorgrad, :967-969, + X_init at the end,
@@ -70,7 +95,18 @@ class SamplerPipeline:
         look after the pass would see the last step only.  Rows are per (range, tensor); the launches only read the tensors, they
         are part of the plan and of its hipGraph.  ``range_report()`` / ``check(audit=True)`` read the table.  Only f16x2 passes
         have a window: with split "bf16x3" (or dtype "bf16", or the exact fp32 arithmetic of the full schedule) the flag is
-        accepted and nothing is recorded.  False (default): the plan is launch for launch the one without the feature."""
+        accepted and nothing is recorded.  False (default): the plan is launch for launch the one without the feature.
+        The audit of a ragged plan sees the padding frames of the shorter utterances too: its histograms are over whole buffers.
+        ragged: EXACT ragged batches (needs L_; priors GCRN and DiffUNet).  ``enhance(wav, x_T, lens=..., exact=True)`` then gives
+        every utterance b of a zero-padded batch, in samples [0, len_b) and frames [0, T_b = 1 + len_b // 160), exactly what a
+        B = 1 pass of length len_b with x_T[b, :, :T_b] gives; samples and frames behind an utterance's own come back as zeros
+        (what the intermediate buffers hold there is unspecified, but finite).  The plan records the masked variants of the four
+        places where padding could reach an utterance's own frames - the STFT's right-hand reflection (``wavprep``), the TCM
+        bottleneck of the eps-net (and of a DiffUNet prior), the overlap-add and the ``--sigma`` maximum - and owns their length
+        tables (``lens``, ``frames_tab``, ``valid_tab``: device int32, written by a copy before each pass, so a replayed
+        hipGraph sees new lengths).  Everything else on the path is per-frame or looks back in time only.  The
+        DB-AIAT priors attend and run a bidirectional GRU over all of T: ValueError.  False (default): every table is NULL and
+        the plan is launch for launch today's."""
         if L_ is not None:
             T = 1 + L_ // 160
         if with_signal is None:
@@ -91,6 +127,9 @@ class SamplerPipeline:
             # schedule amplifies rounding noise ~500x (the fp32 CPU path itself sits 4-7e-5 from the exact answer), so
             # it keeps exact fp32 MFMA arithmetic - BASELINE config 3 is an fp32 configuration anyway.
             split_bf16 = bool(fast_sampling)
+        self.ragged = bool(ragged)
+        if self.ragged:
+            ragged_args(prior_name, L_)
         self.B, self.T, self.L = B, T, L_
         self.device = torch.device(device)
         self.ctx = ctx = nets.Ctx(device, bank)
@@ -114,7 +153,13 @@ class SamplerPipeline:
             pb.descs = self.descs
             return pb
 
-        self.stft = adopt(nets.StftPlan(ctx, B, L_, plan=self.plan, split_bf16=split_bf16)) if with_signal else None
+        self.frames_tab = self.valid_tab = None
+        if self.ragged:
+            # the length tables of the masked launches (with stft.lens): every utterance's own frames, and frames x 161 per (b, re|im) plane
+            self.frames_tab = torch.full((B,), T, dtype=torch.int32, device=self.device)
+            self.valid_tab = torch.full((2 * B,), T * F0, dtype=torch.int32, device=self.device)
+            ctx.keep += [self.frames_tab, self.valid_tab]
+        self.stft = adopt(nets.StftPlan(ctx, B, L_, plan=self.plan, split_bf16=split_bf16, reflect_own=self.ragged)) if with_signal else None
         pplanes = 1 if dtype == "bf16" else None     # bf16 mode: the priors' GEMM-shaped convolutions on plain bf16 operands too (korder 4)
         aplanes = pplanes if pplanes is not None else ((2 if split == "f16x2" else 3) if split_bf16 else None)   # DB-AIAT: dense blocks (np) and GEMM convolutions
         if prior_name == "GCRN":
@@ -122,7 +167,8 @@ class SamplerPipeline:
             self.prior = adopt(nets.GcrnPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", exclusive=exclusive,
                                              planes=gplanes))
         elif prior_name == "DiffUNet":
-            self.prior = adopt(nets.EpsNetPlan(ctx, prior_sd, B, T, time_cond=False, plan=self.plan, split_bf16=split_bf16, exclusive=exclusive))
+            self.prior = adopt(nets.EpsNetPlan(ctx, prior_sd, B, T, time_cond=False, plan=self.plan, split_bf16=split_bf16, exclusive=exclusive,
+                                               frames=self.frames_tab))
         elif prior_name == "aia_complex_trans_ri":
             self.prior = adopt(nets.AiaPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", planes=aplanes))
         elif prior_name == "dual_aia_trans_merge_crm":
@@ -134,12 +180,13 @@ class SamplerPipeline:
         self.eps = adopt(nets.EpsNetPlan(ctx, ddpm_sd, B, T, time_cond=True, nsteps=S, plan=self.plan,
                                          with_pre=not deltamu, split_bf16=split_bf16,
                                          planes=1 if dtype == "bf16" else (2 if split == "f16x2" else 3),
-                                         exclusive=exclusive))
+                                         exclusive=exclusive, frames=self.frames_tab))
         self.split_bf16 = self.eps.split_bf16
         self.deltamu = deltamu
         self.xT_plus_init = xT_plus_init = bool(deltamu if xT_plus_init is None else xT_plus_init)
         self.cond_feat = cond_feat = (cond == "feat") and not deltamu
-        self.istft = adopt(nets.IstftPlan(ctx, B, T, L_, plan=self.plan, split_bf16=split_bf16)) if with_signal else None
+        self.istft = adopt(nets.IstftPlan(ctx, B, T, L_, plan=self.plan, split_bf16=split_bf16, frames=self.frames_tab,
+                                          lens=self.stft.lens if self.ragged else None)) if with_signal else None
 
         self.feat = self.prior.x                     # prior input = compressed spectrogram
         # X_init / 11: the eps-net's conditioning input only in the pirorgrad parameterisation
@@ -216,6 +263,7 @@ class SamplerPipeline:
                 d.init, d.a, d.out = self.init.data_ptr(), src.data_ptr(), self.audio.data_ptr()
                 d.maxbuf = ctx.alloc(B * 2).data_ptr()
                 d.plane, d.nplanes = T * F0, B * 2
+                d.valid = nets.Ctx.ptr(self.valid_tab)
                 self.eps.add(d, nets.TAG_EW)
             elif not xT_plus_init:
                 ew(L.EW_COPY, self.xT_in, out=self.audio)
@@ -338,22 +386,40 @@ class SamplerPipeline:
             self.run("prior", "step0")
         return self.spec.clone(), self.prior.out.clone()
 
-    def enhance(self, wav, x_T, graph=False, lens=None):
+    def enhance(self, wav, x_T, graph=False, lens=None, exact=False):
         """wav [B,L], x_T [B,2,T,161] -> (enhanced wav [B,L], spectrogram [B,2,T,161]).
         lens: true lengths of zero-padded utterances (RMS normalisation over each utterance's own samples,
-        utils/dataset.py:45-58); default: every utterance fills L."""
+        utils/dataset.py:45-58); default: every utterance fills L.
+        exact (pipelines built with ``ragged=True``, and only those): every utterance as if enhanced alone - see ``ragged`` in
+        the constructor; samples behind ``lens[b]`` and frames behind ``1 + lens[b] // 160`` are zeros in both results.
+        False on a ragged pipeline: the padding takes part, as on a dense one (its tables are set to the full length)."""
         if self.stft is None:
             raise ValueError("pipeline was built without the signal front/back end (pass L_)")
         _expect(wav, self.stft.wav, "wav")
         _expect(x_T, self.xT_in, "x_T")
+        if exact:
+            if not self.ragged:
+                raise ValueError("exact=True needs a pipeline recorded with ragged=True (the dense plan has no length tables)")
+            lens_h, frames_h = ragged_tables(self.L if lens is None else lens, self.B, self.L)
         self.stft.wav.copy_(wav)
         self.xT_in.copy_(x_T)
         if lens is None:
             self.stft.lens.fill_(self.L)
         else:
             self.stft.lens.copy_(torch.as_tensor(lens, dtype=torch.int32))
+        if self.ragged:
+            if exact:
+                self.frames_tab.copy_(torch.from_numpy(frames_h))
+                self.valid_tab.copy_(torch.from_numpy(np.repeat(frames_h * F0, 2)))
+            else:
+                self.frames_tab.fill_(self.T)
+                self.valid_tab.fill_(self.T * F0)
         self.run(graph=graph)
-        return self.istft.wav.clone(), self.spec.clone()
+        wav_out, spec = self.istft.wav.clone(), self.spec.clone()
+        if exact:     # frames behind an utterance's own: zeros in the returned tensor (the overlap-add zeroed the samples itself)
+            dead = torch.arange(self.T, device=self.device)[None, :] >= self.frames_tab[:, None]
+            spec.masked_fill_(dead[:, None, :, None], 0.0)
+        return wav_out, spec
 
 
 class ConcurrentSampler:

@@ -128,6 +128,8 @@ def save_pipeline(path, pipe):
     (rows: ``pipe.range_rows`` in order, then unused ones up to the region's size), cleared and filled by every run."""
     if pipe.stft is None:
         raise ValueError("the pipeline was built without the signal front / back end (pass L_)")
+    if getattr(pipe, "ragged", False):
+        raise ValueError("plan files are dense (pdse_enhance has no length arguments): save a pipeline built without ragged=True")
     pipe.stft.lens.fill_(pipe.L)
     named = {"wav": pipe.stft.wav, "x_T": pipe.xT_in, "wav_out": pipe.istft.wav, "spec": pipe.spec}
     if getattr(pipe, "audited", False):

@@ -4,6 +4,7 @@
 entry points the reference lacks (it can only read wav files from a directory):
 
     enhance(wav[B,L], x_T=None)      -> wav[B,L]         whole path, batched
+    enhance_batch(wavs, exact=True)  -> [wav_b]          ragged batch, every utterance as if enhanced alone
     sample(feat[B,2,T,161], x_T)     -> spectrogram      :939-998 on a given spectrogram
 
 Training (train_ddpm/train_step/train/draw_audio) is out of scope.
@@ -22,9 +23,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import nets, ops, wavdev, wavio
+from . import nets, ops, raggedplan, wavdev, wavio
 from .params import PRIOR_SCALE_C, params as default_params
-from .pipeline import SamplerPipeline
+from .pipeline import SamplerPipeline, ragged_args
 from .schedule import inference_schedule as _inference_schedule
 
 
@@ -132,11 +133,11 @@ class ComplexDDPMTrainer(object):
         return _inference_schedule(self.params, fast_sampling)
 
     # ---- batched entry points ----------------------------------------------
-    def _pipe(self, B, T=None, L_=None):
+    def _pipe(self, B, T=None, L_=None, ragged=False):
         """The recorded plan of one geometry.  ``generate_wav`` meets a new utterance length with almost every file:
         a new plan re-records its descriptors (milliseconds) against the weights already packed in ``self.bank``;
         only ``MAX_PLANS`` geometries keep their activation buffers, the least recently used one is dropped."""
-        key = (B, T, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling))
+        key = (B, T, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling)) + ((True,) if ragged else ())
         pipe = self._pipes.get(key)
         self._hits[key] = self._hits.get(key, 0) + 1 if pipe is not None else 0
         if pipe is None:
@@ -146,7 +147,7 @@ class ComplexDDPMTrainer(object):
                 self.device, self.prior_name, self.prior_sd, self.ddpm_sd, B, T=T, L_=L_,
                 fast_sampling=self.params.fast_sampling, use_sigma=key[3], params=self.params, deltamu=self.deltamu,
                 cond=self.cond, bank=self.bank, xT_plus_init=self.xT_plus_init, exclusive=self.exclusive, dtype=self.dtype,
-                split="bf16x3" if key in self._range_fallback else self.split, audit=self.audit)
+                split="bf16x3" if key in self._range_fallback else self.split, audit=self.audit, ragged=ragged)
         else:
             self._pipes.move_to_end(key)
         return pipe
@@ -207,15 +208,25 @@ class ComplexDDPMTrainer(object):
             return run(self._pipe(B, L_=L_))
         return self._checked(run, B=B, L_=L_)
 
-    def enhance_batch(self, wavs, x_T=None, trim_to_frames=False):
-        """Ragged batch, the validation loop's convention: every utterance is RMS-normalised
+    def enhance_batch(self, wavs, x_T=None, trim_to_frames=False, exact=False):
+        """Ragged batch.  Returns a list of 1-D tensors (rescaled by c), each of its utterance's own length.
+        exact False (default), the validation loop's convention: every utterance is RMS-normalised
         over its own samples, zero-padded to the longest (utils/dataset.py:45-58), enhanced in one batch
-        (:408-494) and cut back — to its own length, or with ``trim_to_frames`` to ``(frame_num - 1) * 160``
-        samples as utils/metrics.py:562-563 does.  Returns a list of 1-D tensors (rescaled by c)."""
+        (:408-494) - the padding takes part - and cut back — to its own length, or with ``trim_to_frames`` to
+        ``(frame_num - 1) * 160`` samples as utils/metrics.py:562-563 does.
+        exact True: every utterance exactly as ``enhance(wav_b[None], x_T_b)`` gives it alone (``generate_wav``'s per-file
+        result) - the STFT reflects at, the TCM pads at and the ISTFT sums up to the utterance's own end, ``--sigma`` takes
+        the maximum over its own frames (``SamplerPipeline(ragged=True)``; priors GCRN and DiffUNet, ValueError for the
+        DB-AIAT priors, which attend over all frames of the batch).  x_T: one padded [B, 2, T, 161] tensor, or a list of
+        per-utterance [2, T_b, 161] (or [1, 2, T_b, 161]) tensors, T_b = 1 + len_b // 160; None: one draw per utterance at its
+        own shape, in list order - the draws of the B = 1 calls."""
         wavs = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in wavs]
         lens = [int(w.numel()) for w in wavs]
         if min(lens) < 161:
             raise ValueError("utterances must be longer than the reflect padding (160 samples)")
+        if exact:
+            out = self._enhance_ragged(wavs, x_T, max(lens))
+            return [o[:(n // 160) * 160].clone() if trim_to_frames else o for o, n in zip(out, lens)]
         batch = torch.nn.utils.rnn.pad_sequence(wavs, batch_first=True).to(self.device)
         B, L_ = batch.shape
         T = 1 + L_ // 160
@@ -223,6 +234,34 @@ class ComplexDDPMTrainer(object):
         out = self._checked(lambda pipe: pipe.enhance(batch, x_T, lens=lens)[0], B=B, L_=L_)
         cut = [(n // 160) * 160 if trim_to_frames else n for n in lens]
         return [out[i, :cut[i]].clone() for i in range(B)]
+
+    def _enhance_ragged(self, wavs, x_T, L_):
+        """``enhance_batch(exact=True)`` on 1-D utterances, padded to ``L_`` samples; returns the list of enhanced utterances."""
+        ragged_args(self.prior_name, L_)
+        lens = [int(w.numel()) for w in wavs]
+        B, T = len(wavs), 1 + L_ // 160
+        batch = torch.zeros(B, L_, dtype=torch.float32, device=self.device)
+        for b, w in enumerate(wavs):
+            batch[b, :lens[b]] = w.to(self.device)
+        if x_T is None:
+            x_T = [self._x_T((1, 2, 1 + n // 160, 161), None) for n in lens]          # :947-950, one draw per utterance
+        if isinstance(x_T, (list, tuple)):
+            if len(x_T) != B:
+                raise ValueError("x_T: expected %d per-utterance tensors, got %d" % (B, len(x_T)))
+            xp = torch.zeros(B, 2, T, 161, dtype=torch.float32, device=self.device)
+            for b, (x, n) in enumerate(zip(x_T, lens)):
+                x = torch.as_tensor(x, dtype=torch.float32)
+                x = x[0] if x.dim() == 4 else x
+                if tuple(x.shape) != (2, 1 + n // 160, 161):
+                    raise ValueError("x_T[%d]: expected (2, %d, 161) for an utterance of %d samples, got %s" % (b, 1 + n // 160, n, tuple(x.shape)))
+                xp[b, :, :x.shape[1]] = x.to(self.device)
+            x_T = xp
+        else:
+            x_T = x_T.to(self.device)
+        run = lambda pipe: pipe.enhance(batch, x_T, lens=lens, exact=True,                                # noqa: E731
+                                        graph=self._hits.get(next(reversed(self._pipes)), 0) >= 1)[0]
+        out = self._checked(run, B=B, L_=L_, ragged=True)
+        return [out[b, :lens[b]].clone() for b in range(B)]
 
     def evaluate_batch(self, noisy_wavs, clean_wavs, x_T=None):
         """The validation loop's enhancement and scoring in one call (:408-494 with utils/metrics.py: compare_complex, less
@@ -250,9 +289,15 @@ class ComplexDDPMTrainer(object):
         return enhanced, scores
 
     # ---- A2..A7: the reference's entry point --------------------------------
-    def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True):
+    def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True, batch=1):
         """Per-file B=1 enhancement of ``data_path/*.wav`` into ``args.generated_wav``
         (:903-1018).  Returns the list of written paths instead of calling exit().
+
+        batch (default 1: the loop below, one file per pass): N > 1 enhances N files per pass as exact ragged batches
+        (``enhance_batch(exact=True)``; ``raggedplan``): the sorted paths are taken in windows of 8 N, a window is decoded at
+        once, every file's x_T is drawn in path order at its own shape - followed by its ``rng_fidelity`` discards, exactly as
+        here - so file k's noise is the same whatever ``batch`` is; the window is then sorted by length and enhanced N at a
+        time, padded to a multiple of 2560 samples.  The same files are written under the same names, in path order.
 
         rng_fidelity: the reference draws ``randn_like(audio)`` after every reverse step n > 0 (:986-987) and multiplies
         it by ``newsigma == 0``; the draws change nothing in a file's output but advance the generator, so file k's
@@ -264,6 +309,8 @@ class ComplexDDPMTrainer(object):
         if load_pre_train and getattr(self.args, "retrain", False):
             self._load_checkpoint()
         os.makedirs(self.args.generated_wav, exist_ok=True)
+        if int(batch) > 1:
+            return self._generate_wav_batched(data_path, rng_fidelity, int(batch))
         written = []
         with torch.no_grad():
             for path in sorted(glob.glob(data_path + "/*.wav")):
@@ -282,6 +329,49 @@ class ComplexDDPMTrainer(object):
                 dst = os.path.join(self.args.generated_wav, path.split("/")[-1])
                 wavio.write_wav(dst, out, 16000)
                 written.append(dst)
+        print("success!")
+        return written
+
+    def _load_window(self, paths):
+        """[(path, wav [len] on the device)] of the readable files of ``paths``, in order; the others are logged and skipped."""
+        errors = (ValueError, EOFError, wavio.wave.Error)
+        try:
+            wav, lens = wavdev.load(paths, self.device, 16000)
+            return [(p, wav[i, :lens[i]]) for i, p in enumerate(paths)]
+        except errors:
+            pass                                     # at least one file cannot be read: find out which, one by one
+        out = []
+        for p in paths:
+            try:
+                wav, lens = wavdev.load([p], self.device, 16000)
+                out.append((p, wav[0, :lens[0]]))
+            except errors as e:
+                logging.warning("skipping %s: %s", p, e)
+        return out
+
+    def _generate_wav_batched(self, data_path, rng_fidelity, batch):
+        ragged_args(self.prior_name, 161)
+        paths = sorted(glob.glob(data_path + "/*.wav"))
+        ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0
+        written = []
+        with torch.no_grad():
+            for lo, hi in raggedplan.windows(len(paths), batch):
+                files = self._load_window(paths[lo:hi])
+                x_Ts = []
+                for _, wav in files:                 # path order: the generator sees what the B = 1 loop shows it
+                    shape = (1, 2, 1 + wav.numel() // 160, 161)
+                    x_Ts.append(self._x_T(shape, None))
+                    for _ in range(ndiscard):
+                        torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
+                outs = [None] * len(files)
+                for idx, L_pad in raggedplan.buckets([w.numel() for _, w in files], batch):
+                    res = self._enhance_ragged([files[i][1] for i in idx], [x_Ts[i] for i in idx], L_pad)
+                    for i, r in zip(idx, res):
+                        outs[i] = r
+                for (path, _), out in zip(files, outs):
+                    dst = os.path.join(self.args.generated_wav, path.split("/")[-1])
+                    wavio.write_wav(dst, out.cpu().numpy(), 16000)
+                    written.append(dst)
         print("success!")
         return written
 
