@@ -616,7 +616,9 @@ typedef struct pdse_tcm2s_desc {
 } pdse_tcm2s_desc;
 
 /* GroupNorm(1,C) statistics + the AIA layer update (dbaiat.py:142,147-148):
- *   out = base + k1 * gn(row) + k2 * gn(col);  stats scratch [B][4] (sum,sumsq of row | col). */
+ *   out = base + k1 * gn(row) + k2 * gn(col).
+ * stats is scratch of B * 64 * 4 floats: [B][64][4], one (sum, sum of squares) pair of row | col per partial-sum part of the
+ * statistics pass (GN_PARTS = 64 in csrc/aia.hip), taken about the item's first element; the apply pass folds the parts. */
 typedef struct pdse_gncomb_desc {
   const float* base;
   const float* row;
@@ -625,7 +627,7 @@ typedef struct pdse_gncomb_desc {
   const float* b_row;
   const float* g_col;
   const float* b_col;
-  float* stats; /* [B][4] scratch */
+  float* stats; /* [B][64][4] scratch (GN_PARTS parts per item) */
   float* out;
   int64_t plane; /* T*F */
   int32_t B, C;

@@ -96,6 +96,13 @@ int pdse_rowln_launch(const pdse_rowln_desc* d, hipStream_t s) {
 // ---------------------------------------------------------------------------------------
 // LayerNorm over the C (<= 64) channels of every position (the d_model axis of the
 // transformer layers, dbaiat.py:76,81,87).  One thread per position, coalesced across threads.
+// The channels are taken relative to channel 0 of the position, so the running sum stays of the size of the spread and
+// x_c - mean = (x_c - x_0) - mean(x - x_0) is never rounded at the size of the mean: a serial fp32 sum of 64 raw values put
+// ulp(64 mean) / 2 per addition into the mean (2.7e-5 of the output at mean 64, std 0.25, twice an fp32 CPU evaluation).
+// The price: x_c - x_0 is exact only where the two lie within a factor two of each other (mean >> spread).  For zero-mean
+// inputs - what the networks feed this kernel - it is one more rounding per element, of the size of ulp(spread): measured
+// 0.9 to 1.5e-7 of the output against float64 where an fp32 CPU evaluation gives 0.5 to 1.1e-7, up to 2.5 times as far
+// (profiles/aia_ops_margins.txt, the n01 cases).
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void chln_kernel(const pdse_chln_desc d) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -103,14 +110,15 @@ __global__ __launch_bounds__(256) void chln_kernel(const pdse_chln_desc d) {
   if (q >= d.plane) return;
   const float* x = d.in + (int64_t)b * d.C * d.plane + q;
   float* o = d.out + (int64_t)b * d.C * d.plane + q;
-  float v[64];
+  const float p = x[0];
+  float v[64];   // x_c - x_0
   float sum = 0.f;
 #pragma unroll
   for (int c = 0; c < 64; ++c) {
-    v[c] = c < d.C ? x[(int64_t)c * d.plane] : 0.f;
+    v[c] = c < d.C ? x[(int64_t)c * d.plane] - p : 0.f;
     sum += v[c];
   }
-  const float mean = sum / (float)d.C;
+  const float mean = sum / (float)d.C;   // mean(x) - x_0
   float sq = 0.f;
 #pragma unroll
   for (int c = 0; c < 64; ++c) {
@@ -142,7 +150,8 @@ int pdse_chln_launch(const pdse_chln_desc* d, hipStream_t s) {
 // second round of a 401-position line ran 56 % full.  Measured at B=32: S = 401 1.45 -> see profiles/r03_prior_per_launch.txt.)
 #define ATTN_THREADS 1024
 // HD = head dimension (8: d_model 32, 16: d_model 64; always 4 heads).
-// Sequences longer than one LDS image (S > 2048: never on this path) would be walked in key chunks of CH positions:
+// Sequences longer than one LDS image (the launcher's cap: 1024 keys at HD = 8, 512 at HD = 16) are walked in key chunks of
+// CH positions:
 // K and V of a chunk are staged, every thread advances the online softmax of its query over the chunk
 // and keeps (m, l, acc) in registers across chunks.  Chunks are multiples of four keys, so the rescale grouping - and
 // with it every rounding - is the one a single image would give.
@@ -254,16 +263,12 @@ int pdse_attn_launch(const pdse_attn_desc* d, hipStream_t s) {
   const int S = d->axis == 0 ? d->F : d->T, lines = d->axis == 0 ? d->T : d->F;
   const int HD = d->E / 4;
   // one LDS image of the head's K and V when the sequence fits, else key chunks (a multiple of four keys).  The chunk follows from
-  // the LDS budget: 2 CH HD floats <= 64 KB (two workgroups per CU at the least) - 2048 keys at head dimension 8 (d_model 32),
-  // 1024 at 16 (d_model 64: 2048 keys would ask for 256 KB, more than a CU has)
+  // the LDS budget: K and V of CH keys are 2 CH HD floats <= 64 KB (two workgroups per CU at the least) - 1024 keys at head
+  // dimension 8 (d_model 32), 512 at 16 (d_model 64).  A single image therefore never holds more keys than the workgroup has
+  // threads (one query round); the 10 s utterances (T = 1001) fit one image at d_model 32 and take two chunks at d_model 64
   const int cap = (int)((64 * 1024) / (2 * HD * sizeof(float))) & ~3;
   const int CH = S <= cap ? S : cap;
-  const size_t lds = (size_t)2 * CH * HD * sizeof(float);
-  REQ(lds <= 160 * 1024, "attention: LDS image of K and V exceeds the CU");
-  const void* fn = d->E == 32 ? (const void*)attn_kernel<8> : (const void*)attn_kernel<16>;
-  if (lds > 64 * 1024)
-    if (pdse_check_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "attention lds attribute"))
-      return 1;
+  const size_t lds = (size_t)2 * CH * HD * sizeof(float);   // <= 64 KB by the cap: within the default dynamic-LDS limit
   const int nt = S >= ATTN_THREADS ? ATTN_THREADS : (S + 63) / 64 * 64;   // one query per thread, whole waves
   const dim3 grid(lines, d->B, 4);
   if (d->E == 32)
@@ -447,7 +452,12 @@ int pdse_gru_launch(const pdse_gru_desc* d, hipStream_t s) {
 // ---------------------------------------------------------------------------------------
 // GroupNorm(1, C, eps 1e-8) of the row and column branches + the AIA layer update
 // (dbaiat.py:142,147-148).  Two launches: fixed-order partial sums (deterministic, no float
-// atomics), then every workgroup of the apply pass folds the 64 partials in double.
+// atomics), then every workgroup of the apply pass folds the GN_PARTS partials in double.
+// The moments are taken about a pivot p, the item's first element: sums of (x - p) and (x - p)^2, so that
+//   var = E[(x - p)^2] - (E[x - p])^2
+// loses only 1 + (mean - p)^2 / var of its digits - about one bit for a pivot drawn from the data - where the raw
+// E[x^2] - mean^2 lost 1 + mean^2 / var (5e-3 of the output at mean 64, std 0.25).  No third read of row / col.
+// stats: [B][GN_PARTS][4] = (sum, sum of squares) of row - p_row | of col - p_col per part.
 // ---------------------------------------------------------------------------------------
 #define GN_PARTS 64
 __global__ __launch_bounds__(256) void gn_stats_kernel(const pdse_gncomb_desc d) {
@@ -456,9 +466,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const pdse_gncomb_desc d)
   const int64_t n = (int64_t)d.C * d.plane;
   const float* r = d.row + (int64_t)b * n;
   const float* c = d.col + (int64_t)b * n;
+  const float pr = r[0], pc = c[0];
   float s[4] = {0.f, 0.f, 0.f, 0.f};
   for (int64_t i = (int64_t)part * 256 + threadIdx.x; i < n; i += (int64_t)GN_PARTS * 256) {
-    const float a = r[i], e = c[i];
+    const float a = r[i] - pr, e = c[i] - pc;
     s[0] += a;
     s[1] += a * a;
     s[2] += e;
@@ -476,19 +487,28 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const pdse_gncomb_desc d)
 }
 
 __global__ __launch_bounds__(256) void gn_apply_kernel(const pdse_gncomb_desc d) {
-  __shared__ float st[4];
+  __shared__ float st[4];   // mean, 1/std of row | of col
   const int b = blockIdx.y;
   const int64_t n = (int64_t)d.C * d.plane;
-  if (threadIdx.x < 4) {
+  const int64_t off = (int64_t)b * n;
+  if (threadIdx.x < 64) {
+    // wave 0: lane = 4 g + k folds parts 4 g .. 4 g + 3 of statistic k, then the 16 groups are folded by a fixed butterfly
+    const int k = threadIdx.x & 3, g = threadIdx.x >> 2;
     double acc = 0.0;
-    for (int p = 0; p < GN_PARTS; ++p) acc += (double)d.stats[((size_t)b * GN_PARTS + p) * 4 + threadIdx.x];
-    st[threadIdx.x] = (float)(acc / (double)n);
+#pragma unroll
+    for (int p = 0; p < GN_PARTS / 16; ++p) acc += (double)d.stats[((size_t)b * GN_PARTS + 4 * g + p) * 4 + k];
+    for (int o = 4; o < 64; o <<= 1) acc += __shfl_xor(acc, o);
+    const double s1 = __shfl(acc, threadIdx.x & 2), s2 = __shfl(acc, (threadIdx.x & 2) | 1);
+    if (threadIdx.x == 0 || threadIdx.x == 2) {
+      const double m = s1 / (double)n;                       // mean - pivot
+      const double var = fmax(s2 / (double)n - m * m, 0.0);
+      const double pv = (double)(threadIdx.x ? d.col : d.row)[off];
+      st[threadIdx.x] = (float)(pv + m);
+      st[threadIdx.x + 1] = (float)(1.0 / sqrt(var + (double)d.eps));
+    }
   }
   __syncthreads();
-  const float mr = st[0], mc = st[2];
-  const float rr = 1.0f / sqrtf(fmaxf(st[1] - mr * mr, 0.f) + d.eps);
-  const float rc = 1.0f / sqrtf(fmaxf(st[3] - mc * mc, 0.f) + d.eps);
-  const int64_t off = (int64_t)b * n;
+  const float mr = st[0], rr = st[1], mc = st[2], rc = st[3];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int c = (int)(i / d.plane);
     const float gr = (d.row[off + i] - mr) * rr * d.g_row[c] + d.b_row[c];

@@ -318,9 +318,10 @@ def test_masked_validation_loss_and_ragged_batch_vs_reference_fixture(L, weights
 
 
 def test_aia_prior_long_sequence_t1001(L, weights, R):
-    """DB-AIAT priors on 10 s utterances: the column attention walks its 1001 keys in LDS-sized chunks
-    (model/dbaiat.py:91-154 takes any T).  Oracle at T = 1001, and the attention core alone against a plain softmax
-    at a length that is neither a multiple of the chunk nor of four."""
+    """DB-AIAT priors on 10 s utterances (model/dbaiat.py:91-154 takes any T).  Oracle at T = 1001, where the column
+    attention's 1001 keys are one LDS image of K and V (at d_model 32 an image holds up to 1024 keys), and the attention
+    core alone against a plain softmax along the frames (axis 1) at T = 1103: that one walks its keys in LDS-sized
+    chunks, 1024 + 79 - a length that is neither a multiple of the chunk nor of four - with two query rounds."""
     x = seeded((1, 2, 1001, 161), 93)
     got = pkg("ops").AiaOp(weights("aia_complex_trans_ri"), DEV)(x.to(DEV)).cpu()
     assert_rows2_and_checksums(got, golden("full_aia_seed93_t1001"), "", 1e-4)     # the reference module at T = 1001
