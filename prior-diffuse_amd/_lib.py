@@ -3,6 +3,7 @@
 The product path has no CPU fallback: if the shared library is missing or does not
 match the header this module raises, and so does everything built on it.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -272,35 +273,53 @@ METRICS_OFF_WEPS = METRICS_OFF_CRIT + 25 * 512
 METRICS_OFF_BRANGE = METRICS_OFF_WEPS + 2 * 512
 METRICS_TABLE_DOUBLES = METRICS_OFF_BRANGE + 64
 
-DESC_TYPES = {OP_RANGE: RangeDesc, OP_RESAMPLE: ResampleDesc, OP_METRICS: MetricsDesc, OP_DENSE: DenseDesc, OP_ROWLNB: RowlnbDesc, OP_TCM2S: Tcm2sDesc, OP_GLSTMP: GlstmpDesc, OP_BGLU: BgluDesc, OP_PLANES: PlanesDesc, OP_TCM2: Tcm2Desc, OP_GLSTM: GlstmDesc, OP_MASKLOSS: MasklossDesc, OP_GCRNLAST: GcrnLastDesc, OP_CRM: CrmDesc, OP_TCM: TcmDesc, OP_TRANSPOSE: TransposeDesc, OP_QSAMPLE: QsampleDesc, OP_ROWLN: RowlnDesc, OP_CHLN: ChlnDesc, OP_ATTN: AttnDesc, OP_GRU: GruDesc, OP_GNCOMB: GncombDesc,
-              OP_AHAM: AhamDesc, OP_GCONV: GconvDesc, OP_TIME: TimeDesc, OP_EW: EwDesc, OP_COMPAND: CompandDesc,
-              OP_WAVPREP: WavprepDesc, OP_OLA: OlaDesc, OP_SIGMA: SigmaDesc, OP_LN: LnDesc,
-              OP_LSTM: LstmDesc}
-KIND_OF = {v: k for k, v in DESC_TYPES.items()}
+# The operator table, in kind order: (kind, descriptor mirror, direct entry of include/pdse.h).  Everything below that exists
+# once per operator is derived from it; tests/test_abi.py holds every row, and every mirror's layout, against the header.
+OPS = (
+    (OP_GCONV, GconvDesc, "pdse_gconv_f32"),
+    (OP_TIME, TimeDesc, "pdse_time_embed_f32"),
+    (OP_EW, EwDesc, "pdse_ew_f32"),
+    (OP_COMPAND, CompandDesc, "pdse_compand_f32"),
+    (OP_WAVPREP, WavprepDesc, "pdse_wavprep_f32"),
+    (OP_OLA, OlaDesc, "pdse_ola_f32"),
+    (OP_SIGMA, SigmaDesc, "pdse_sigma_mask_f32"),
+    (OP_LN, LnDesc, "pdse_layernorm_f32"),
+    (OP_LSTM, LstmDesc, "pdse_lstm_f32"),
+    (OP_ROWLN, RowlnDesc, "pdse_rowln_prelu_f32"),
+    (OP_CHLN, ChlnDesc, "pdse_chln_f32"),
+    (OP_ATTN, AttnDesc, "pdse_attention_f32"),
+    (OP_GRU, GruDesc, "pdse_bigru_f32"),
+    (OP_GNCOMB, GncombDesc, "pdse_gn_combine_f32"),
+    (OP_AHAM, AhamDesc, "pdse_aham_f32"),
+    (OP_QSAMPLE, QsampleDesc, "pdse_qsample_f32"),
+    (OP_TRANSPOSE, TransposeDesc, "pdse_transpose_f32"),
+    (OP_TCM, TcmDesc, "pdse_tcm_f32"),
+    (OP_CRM, CrmDesc, "pdse_crm_f32"),
+    (OP_GCRNLAST, GcrnLastDesc, "pdse_gcrnlast_f32"),
+    (OP_MASKLOSS, MasklossDesc, "pdse_masked_mse_f32"),
+    (OP_GLSTM, GlstmDesc, "pdse_glstm_f32"),
+    (OP_TCM2, Tcm2Desc, "pdse_tcm2_bf16x3"),
+    (OP_BGLU, BgluDesc, "pdse_bglu_planes"),
+    (OP_PLANES, PlanesDesc, "pdse_split_planes"),
+    (OP_GLSTMP, GlstmpDesc, "pdse_glstm_persistent_f32"),
+    (OP_TCM2S, Tcm2sDesc, "pdse_tcm2_stack_bf16x3"),
+    (OP_DENSE, DenseDesc, "pdse_dense_layer_bf16x3"),
+    (OP_ROWLNB, RowlnbDesc, "pdse_rowln_blocked_f32"),
+    (OP_METRICS, MetricsDesc, "pdse_quality_metrics_f32"),
+    (OP_RESAMPLE, ResampleDesc, "pdse_pcm_resample_f32"),
+    (OP_RANGE, RangeDesc, "pdse_range_hist"),
+)
+DESC_TYPES = {kind: typ for kind, typ, _ in OPS}
+KIND_OF = {typ: kind for kind, typ, _ in OPS}
+_DIRECT = {kind: name for kind, _, name in OPS}
 
 EXPORTS = [
-    "pdse_abi_version", "pdse_last_error", "pdse_desc_size",
-    "pdse_gconv_f32", "pdse_time_embed_f32", "pdse_ew_f32", "pdse_compand_f32", "pdse_wavprep_f32",
-    "pdse_ola_f32", "pdse_sigma_mask_f32", "pdse_layernorm_f32", "pdse_lstm_f32",
-    "pdse_rowln_prelu_f32", "pdse_chln_f32", "pdse_attention_f32", "pdse_bigru_f32", "pdse_gn_combine_f32",
-    "pdse_aham_f32", "pdse_qsample_f32", "pdse_transpose_f32", "pdse_tcm_f32", "pdse_crm_f32", "pdse_gcrnlast_f32",
-    "pdse_masked_mse_f32", "pdse_glstm_f32", "pdse_glstm_persistent_f32", "pdse_tcm2_bf16x3", "pdse_tcm2_stack_bf16x3", "pdse_bglu_planes", "pdse_split_planes", "pdse_dense_layer_bf16x3", "pdse_rowln_blocked_f32", "pdse_quality_metrics_f32", "pdse_pcm_resample_f32", "pdse_range_hist", "pdse_bglu_set_form",
+    "pdse_abi_version", "pdse_last_error", "pdse_desc_size", "pdse_bglu_set_form",
     "pdse_plan_create", "pdse_plan_add", "pdse_plan_size", "pdse_plan_set_device", "pdse_plan_clear", "pdse_plan_run",
     "pdse_plan_run_range",
     "pdse_plan_build_graph", "pdse_plan_launch_graph", "pdse_plan_time_ops", "pdse_plan_time_tag",
     "pdse_plan_destroy", "pdse_plan_load", "pdse_plan_region", "pdse_prior_forward", "pdse_eps_forward", "pdse_enhance",
-]
-
-_DIRECT = {OP_GCONV: "pdse_gconv_f32", OP_TIME: "pdse_time_embed_f32", OP_EW: "pdse_ew_f32",
-           OP_COMPAND: "pdse_compand_f32", OP_WAVPREP: "pdse_wavprep_f32", OP_OLA: "pdse_ola_f32",
-           OP_SIGMA: "pdse_sigma_mask_f32", OP_LN: "pdse_layernorm_f32", OP_LSTM: "pdse_lstm_f32",
-           OP_ROWLN: "pdse_rowln_prelu_f32", OP_CHLN: "pdse_chln_f32", OP_ATTN: "pdse_attention_f32",
-           OP_GRU: "pdse_bigru_f32", OP_GNCOMB: "pdse_gn_combine_f32", OP_AHAM: "pdse_aham_f32",
-           OP_QSAMPLE: "pdse_qsample_f32", OP_TRANSPOSE: "pdse_transpose_f32", OP_TCM: "pdse_tcm_f32", OP_CRM: "pdse_crm_f32", OP_GCRNLAST: "pdse_gcrnlast_f32",
-           OP_MASKLOSS: "pdse_masked_mse_f32", OP_GLSTM: "pdse_glstm_f32", OP_GLSTMP: "pdse_glstm_persistent_f32",
-           OP_TCM2: "pdse_tcm2_bf16x3", OP_TCM2S: "pdse_tcm2_stack_bf16x3", OP_BGLU: "pdse_bglu_planes", OP_PLANES: "pdse_split_planes",
-           OP_DENSE: "pdse_dense_layer_bf16x3", OP_ROWLNB: "pdse_rowln_blocked_f32",
-           OP_METRICS: "pdse_quality_metrics_f32", OP_RESAMPLE: "pdse_pcm_resample_f32", OP_RANGE: "pdse_range_hist"}
+] + [name for _, _, name in OPS]
 
 
 class PdseError(RuntimeError):
@@ -373,14 +392,14 @@ def check(rc, what=""):
 def launch(desc, stream=0, device=None):
     """Launch one operator directly (on ``device`` when given, else on the current device)."""
     lib = load()
-    kind = KIND_OF[type(desc)]
+    name = _DIRECT[KIND_OF[type(desc)]]
+    on = contextlib.nullcontext()
     if device is not None:
         import torch
 
-        with torch.cuda.device(device):
-            check(getattr(lib, _DIRECT[kind])(C.byref(desc), C.c_void_p(stream)), _DIRECT[kind])
-        return
-    check(getattr(lib, _DIRECT[kind])(C.byref(desc), C.c_void_p(stream)), _DIRECT[kind])
+        on = torch.cuda.device(device)
+    with on:
+        check(getattr(lib, name)(C.byref(desc), C.c_void_p(stream)), name)
 
 
 class Plan:

@@ -33,40 +33,20 @@ int pdse_lds_attr(const void* fn, unsigned long long* mask, const char* what) {
   return 0;
 }
 
+#define X(KIND, stem, entry) pdse_##stem##_desc stem;
 union pdse_any_desc {
-  pdse_gconv_desc gconv;
-  pdse_time_desc time;
-  pdse_ew_desc ew;
-  pdse_compand_desc compand;
-  pdse_wavprep_desc wavprep;
-  pdse_ola_desc ola;
-  pdse_sigma_desc sigma;
-  pdse_ln_desc ln;
-  pdse_lstm_desc lstm;
-  pdse_rowln_desc rowln;
-  pdse_chln_desc chln;
-  pdse_attn_desc attn;
-  pdse_gru_desc gru;
-  pdse_gncomb_desc gncomb;
-  pdse_aham_desc aham;
-  pdse_qsample_desc qsample;
-  pdse_transpose_desc transpose;
-  pdse_tcm_desc tcm;
-  pdse_tcm2_desc tcm2;
-  pdse_tcm2s_desc tcm2s;
-  pdse_dense_desc dense;
-  pdse_rowlnb_desc rowlnb;
-  pdse_crm_desc crm;
-  pdse_gcrnlast_desc gcrnlast;
-  pdse_maskloss_desc maskloss;
-  pdse_glstm_desc glstm;
-  pdse_glstmp_desc glstmp;
-  pdse_bglu_desc bglu;
-  pdse_planes_desc planes;
-  pdse_metrics_desc metrics;
-  pdse_resample_desc resample;
-  pdse_range_desc range;
+  PDSE_OPS(X)
 };
+#undef X
+
+// a row of PDSE_OPS in the wrong place, or a missing one, does not compile
+#define X(KIND, stem, entry) ROW_##KIND,
+enum { PDSE_OPS(X) ROW_COUNT };
+#undef X
+#define X(KIND, stem, entry) static_assert((int)ROW_##KIND == (int)PDSE_OP_##KIND, "PDSE_OPS: the row of " #KIND " is not at its enumerator's index");
+PDSE_OPS(X)
+#undef X
+static_assert(ROW_COUNT == 32, "PDSE_OPS: one row per operator kind of include/pdse.h");
 
 struct pdse_op {
   int kind;
@@ -108,79 +88,27 @@ struct device_guard {
 
 static int op_size(int kind) {
   switch (kind) {
-    case PDSE_OP_GCONV: return (int)sizeof(pdse_gconv_desc);
-    case PDSE_OP_TIME: return (int)sizeof(pdse_time_desc);
-    case PDSE_OP_EW: return (int)sizeof(pdse_ew_desc);
-    case PDSE_OP_COMPAND: return (int)sizeof(pdse_compand_desc);
-    case PDSE_OP_WAVPREP: return (int)sizeof(pdse_wavprep_desc);
-    case PDSE_OP_OLA: return (int)sizeof(pdse_ola_desc);
-    case PDSE_OP_SIGMA: return (int)sizeof(pdse_sigma_desc);
-    case PDSE_OP_LN: return (int)sizeof(pdse_ln_desc);
-    case PDSE_OP_LSTM: return (int)sizeof(pdse_lstm_desc);
-    case PDSE_OP_ROWLN: return (int)sizeof(pdse_rowln_desc);
-    case PDSE_OP_CHLN: return (int)sizeof(pdse_chln_desc);
-    case PDSE_OP_ATTN: return (int)sizeof(pdse_attn_desc);
-    case PDSE_OP_GRU: return (int)sizeof(pdse_gru_desc);
-    case PDSE_OP_GNCOMB: return (int)sizeof(pdse_gncomb_desc);
-    case PDSE_OP_AHAM: return (int)sizeof(pdse_aham_desc);
-    case PDSE_OP_QSAMPLE: return (int)sizeof(pdse_qsample_desc);
-    case PDSE_OP_TRANSPOSE: return (int)sizeof(pdse_transpose_desc);
-    case PDSE_OP_TCM: return (int)sizeof(pdse_tcm_desc);
-    case PDSE_OP_TCM2: return (int)sizeof(pdse_tcm2_desc);
-    case PDSE_OP_TCM2S: return (int)sizeof(pdse_tcm2s_desc);
-    case PDSE_OP_DENSE: return (int)sizeof(pdse_dense_desc);
-    case PDSE_OP_ROWLNB: return (int)sizeof(pdse_rowlnb_desc);
-    case PDSE_OP_CRM: return (int)sizeof(pdse_crm_desc);
-    case PDSE_OP_GCRNLAST: return (int)sizeof(pdse_gcrnlast_desc);
-    case PDSE_OP_MASKLOSS: return (int)sizeof(pdse_maskloss_desc);
-    case PDSE_OP_GLSTM: return (int)sizeof(pdse_glstm_desc);
-    case PDSE_OP_GLSTMP: return (int)sizeof(pdse_glstmp_desc);
-    case PDSE_OP_BGLU: return (int)sizeof(pdse_bglu_desc);
-    case PDSE_OP_PLANES: return (int)sizeof(pdse_planes_desc);
-    case PDSE_OP_METRICS: return (int)sizeof(pdse_metrics_desc);
-    case PDSE_OP_RESAMPLE: return (int)sizeof(pdse_resample_desc);
-    case PDSE_OP_RANGE: return (int)sizeof(pdse_range_desc);
+#define X(KIND, stem, entry) case PDSE_OP_##KIND: return (int)sizeof(pdse_##stem##_desc);
+    PDSE_OPS(X)
+#undef X
     default: return -1;
   }
 }
 
 static int launch_op(const pdse_op& op, hipStream_t s) {
   switch (op.kind) {
-    case PDSE_OP_GCONV: return pdse_gconv_launch(&op.d.gconv, s);
-    case PDSE_OP_TIME: return pdse_time_launch(&op.d.time, s);
-    case PDSE_OP_EW: return pdse_ew_launch(&op.d.ew, s);
-    case PDSE_OP_COMPAND: return pdse_compand_launch(&op.d.compand, s);
-    case PDSE_OP_WAVPREP: return pdse_wavprep_launch(&op.d.wavprep, s);
-    case PDSE_OP_OLA: return pdse_ola_launch(&op.d.ola, s);
-    case PDSE_OP_SIGMA: return pdse_sigma_launch(&op.d.sigma, s);
-    case PDSE_OP_LN: return pdse_ln_launch(&op.d.ln, s);
-    case PDSE_OP_LSTM: return pdse_lstm_launch(&op.d.lstm, s);
-    case PDSE_OP_ROWLN: return pdse_rowln_launch(&op.d.rowln, s);
-    case PDSE_OP_CHLN: return pdse_chln_launch(&op.d.chln, s);
-    case PDSE_OP_ATTN: return pdse_attn_launch(&op.d.attn, s);
-    case PDSE_OP_GRU: return pdse_gru_launch(&op.d.gru, s);
-    case PDSE_OP_GNCOMB: return pdse_gncomb_launch(&op.d.gncomb, s);
-    case PDSE_OP_AHAM: return pdse_aham_launch(&op.d.aham, s);
-    case PDSE_OP_QSAMPLE: return pdse_qsample_launch(&op.d.qsample, s);
-    case PDSE_OP_TRANSPOSE: return pdse_transpose_launch(&op.d.transpose, s);
-    case PDSE_OP_TCM: return pdse_tcm_launch(&op.d.tcm, s);
-    case PDSE_OP_CRM: return pdse_crm_launch(&op.d.crm, s);
-    case PDSE_OP_GCRNLAST: return pdse_gcrnlast_launch(&op.d.gcrnlast, s);
-    case PDSE_OP_MASKLOSS: return pdse_maskloss_launch(&op.d.maskloss, s);
-    case PDSE_OP_GLSTM: return pdse_glstm_launch(&op.d.glstm, s);
-    case PDSE_OP_GLSTMP: return pdse_glstmp_launch(&op.d.glstmp, s);
-    case PDSE_OP_TCM2: return pdse_tcm2_launch(&op.d.tcm2, s);
-    case PDSE_OP_TCM2S: return pdse_tcm2s_launch(&op.d.tcm2s, s);
-    case PDSE_OP_DENSE: return pdse_dense_launch(&op.d.dense, s);
-    case PDSE_OP_ROWLNB: return pdse_rowlnb_launch(&op.d.rowlnb, s);
-    case PDSE_OP_BGLU: return pdse_bglu_launch(&op.d.bglu, s);
-    case PDSE_OP_PLANES: return pdse_planes_launch(&op.d.planes, s);
-    case PDSE_OP_METRICS: return pdse_metrics_launch(&op.d.metrics, s);
-    case PDSE_OP_RESAMPLE: return pdse_resample_launch(&op.d.resample, s);
-    case PDSE_OP_RANGE: return pdse_range_launch(&op.d.range, s);
+#define X(KIND, stem, entry) case PDSE_OP_##KIND: return pdse_##stem##_launch(&op.d.stem, s);
+    PDSE_OPS(X)
+#undef X
     default: pdse_set_error("plan: unknown op kind"); return 1;
   }
 }
+
+// What a direct launch checks before the launcher's own argument checks: nothing, except for the range audit, whose row
+// table is device data (pdse_plan_add checks it at add time instead, so that a plan run is launches only).
+template <typename D>
+static int validate_desc(const D*) { return 0; }
+static int validate_desc(const pdse_range_desc* d) { return pdse_range_validate(d); }
 
 extern "C" {
 
@@ -188,38 +116,10 @@ int pdse_abi_version(void) { return PDSE_ABI_VERSION; }
 const char* pdse_last_error(void) { return g_err.c_str(); }
 int pdse_desc_size(int op_kind) { return op_size(op_kind); }
 
-int pdse_gconv_f32(const pdse_gconv_desc* d, pdse_stream_t s) { return pdse_gconv_launch(d, (hipStream_t)s); }
-int pdse_time_embed_f32(const pdse_time_desc* d, pdse_stream_t s) { return pdse_time_launch(d, (hipStream_t)s); }
-int pdse_ew_f32(const pdse_ew_desc* d, pdse_stream_t s) { return pdse_ew_launch(d, (hipStream_t)s); }
-int pdse_compand_f32(const pdse_compand_desc* d, pdse_stream_t s) { return pdse_compand_launch(d, (hipStream_t)s); }
-int pdse_wavprep_f32(const pdse_wavprep_desc* d, pdse_stream_t s) { return pdse_wavprep_launch(d, (hipStream_t)s); }
-int pdse_ola_f32(const pdse_ola_desc* d, pdse_stream_t s) { return pdse_ola_launch(d, (hipStream_t)s); }
-int pdse_sigma_mask_f32(const pdse_sigma_desc* d, pdse_stream_t s) { return pdse_sigma_launch(d, (hipStream_t)s); }
-int pdse_layernorm_f32(const pdse_ln_desc* d, pdse_stream_t s) { return pdse_ln_launch(d, (hipStream_t)s); }
-int pdse_lstm_f32(const pdse_lstm_desc* d, pdse_stream_t s) { return pdse_lstm_launch(d, (hipStream_t)s); }
-int pdse_rowln_prelu_f32(const pdse_rowln_desc* d, pdse_stream_t s) { return pdse_rowln_launch(d, (hipStream_t)s); }
-int pdse_chln_f32(const pdse_chln_desc* d, pdse_stream_t s) { return pdse_chln_launch(d, (hipStream_t)s); }
-int pdse_attention_f32(const pdse_attn_desc* d, pdse_stream_t s) { return pdse_attn_launch(d, (hipStream_t)s); }
-int pdse_bigru_f32(const pdse_gru_desc* d, pdse_stream_t s) { return pdse_gru_launch(d, (hipStream_t)s); }
-int pdse_gn_combine_f32(const pdse_gncomb_desc* d, pdse_stream_t s) { return pdse_gncomb_launch(d, (hipStream_t)s); }
-int pdse_aham_f32(const pdse_aham_desc* d, pdse_stream_t s) { return pdse_aham_launch(d, (hipStream_t)s); }
-int pdse_qsample_f32(const pdse_qsample_desc* d, pdse_stream_t s) { return pdse_qsample_launch(d, (hipStream_t)s); }
-int pdse_transpose_f32(const pdse_transpose_desc* d, pdse_stream_t s) { return pdse_transpose_launch(d, (hipStream_t)s); }
-int pdse_tcm_f32(const pdse_tcm_desc* d, pdse_stream_t s) { return pdse_tcm_launch(d, (hipStream_t)s); }
-int pdse_crm_f32(const pdse_crm_desc* d, pdse_stream_t s) { return pdse_crm_launch(d, (hipStream_t)s); }
-int pdse_gcrnlast_f32(const pdse_gcrnlast_desc* d, pdse_stream_t s) { return pdse_gcrnlast_launch(d, (hipStream_t)s); }
-int pdse_masked_mse_f32(const pdse_maskloss_desc* d, pdse_stream_t s) { return pdse_maskloss_launch(d, (hipStream_t)s); }
-int pdse_glstm_f32(const pdse_glstm_desc* d, pdse_stream_t s) { return pdse_glstm_launch(d, (hipStream_t)s); }
-int pdse_glstm_persistent_f32(const pdse_glstmp_desc* d, pdse_stream_t s) { return pdse_glstmp_launch(d, (hipStream_t)s); }
-int pdse_tcm2_bf16x3(const pdse_tcm2_desc* d, pdse_stream_t s) { return pdse_tcm2_launch(d, (hipStream_t)s); }
-int pdse_tcm2_stack_bf16x3(const pdse_tcm2s_desc* d, pdse_stream_t s) { return pdse_tcm2s_launch(d, (hipStream_t)s); }
-int pdse_dense_layer_bf16x3(const pdse_dense_desc* d, pdse_stream_t s) { return pdse_dense_launch(d, (hipStream_t)s); }
-int pdse_rowln_blocked_f32(const pdse_rowlnb_desc* d, pdse_stream_t s) { return pdse_rowlnb_launch(d, (hipStream_t)s); }
-int pdse_bglu_planes(const pdse_bglu_desc* d, pdse_stream_t s) { return pdse_bglu_launch(d, (hipStream_t)s); }
-int pdse_split_planes(const pdse_planes_desc* d, pdse_stream_t s) { return pdse_planes_launch(d, (hipStream_t)s); }
-int pdse_quality_metrics_f32(const pdse_metrics_desc* d, pdse_stream_t s) { return pdse_metrics_launch(d, (hipStream_t)s); }
-int pdse_pcm_resample_f32(const pdse_resample_desc* d, pdse_stream_t s) { return pdse_resample_launch(d, (hipStream_t)s); }
-int pdse_range_hist(const pdse_range_desc* d, pdse_stream_t s) { return pdse_range_validate(d) ? 1 : pdse_range_launch(d, (hipStream_t)s); }
+#define X(KIND, stem, entry) \
+  int entry(const pdse_##stem##_desc* d, pdse_stream_t s) { return validate_desc(d) ? 1 : pdse_##stem##_launch(d, (hipStream_t)s); }
+PDSE_OPS(X)
+#undef X
 
 int pdse_plan_create(pdse_plan** out) {
   if (!out) {
@@ -491,6 +391,16 @@ int pdse_plan_load(const char* path, pdse_plan** out) {
       if (pdse_check_hip(hipMemset(r.ptr, 0, r.bytes), "plan_load: memset")) return fail(pdse_last_error());
     }
   }
+  // a recorded address becomes the same offset into the region that held it; false when no region did
+  auto rebase = [&](uint64_t& v) {
+    for (uint32_t r = 0; r < nreg; ++r) {
+      if (v >= old_base[r] && v < old_base[r] + p->regions[r].bytes) {
+        v = reinterpret_cast<uint64_t>(p->regions[r].ptr) + (v - old_base[r]);
+        return true;
+      }
+    }
+    return false;
+  };
   std::vector<uint32_t> offs;
   for (uint32_t i = 0; i < nops; ++i) {
     pdse_op op;
@@ -512,14 +422,7 @@ int pdse_plan_load(const char* path, pdse_plan** out) {
       uint64_t v;
       memcpy(&v, base + offs[k], 8);
       if (!v) continue;
-      bool found = false;
-      for (uint32_t r = 0; r < nreg && !found; ++r) {
-        if (v >= old_base[r] && v < old_base[r] + p->regions[r].bytes) {
-          v = reinterpret_cast<uint64_t>(p->regions[r].ptr) + (v - old_base[r]);
-          found = true;
-        }
-      }
-      if (!found) return fail("plan_load: a descriptor points outside every recorded region");
+      if (!rebase(v)) return fail("plan_load: a descriptor points outside every recorded region");
       memcpy(base + offs[k], &v, 8);
     }
     p->ops.push_back(op);
@@ -539,14 +442,8 @@ int pdse_plan_load(const char* path, pdse_plan** out) {
     if (pdse_check_hip(hipMemcpy(rows.data(), rd_.rows, rows.size() * sizeof(pdse_range_row), hipMemcpyDeviceToHost), "plan_load: range table")) return fail(pdse_last_error());
     for (auto& row : rows) {
       uint64_t v = reinterpret_cast<uint64_t>(row.ptr);
-      bool found = false;
-      for (uint32_t r = 0; r < nreg && !found; ++r) {
-        if (v >= old_base[r] && v < old_base[r] + p->regions[r].bytes) {
-          row.ptr = reinterpret_cast<const void*>(reinterpret_cast<uint64_t>(p->regions[r].ptr) + (v - old_base[r]));
-          found = true;
-        }
-      }
-      if (!found) return fail("plan_load: a range-audit row points outside every recorded region");
+      if (!rebase(v)) return fail("plan_load: a range-audit row points outside every recorded region");
+      row.ptr = reinterpret_cast<const void*>(v);
     }
     if (pdse_check_hip(hipMemcpy(const_cast<pdse_range_row*>(rd_.rows), rows.data(), rows.size() * sizeof(pdse_range_row), hipMemcpyHostToDevice), "plan_load: range table")) return fail(pdse_last_error());
     tables_done.push_back(rd_.rows);

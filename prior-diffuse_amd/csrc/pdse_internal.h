@@ -22,41 +22,51 @@ int pdse_lds_attr(const void* fn, unsigned long long* mask, const char* what);
 #define PDSE_DIAG_ENV(name) ((const char*)nullptr)
 #endif
 
-int pdse_gconv_launch(const pdse_gconv_desc* d, hipStream_t s);
+// The operator table: one row X(KIND, stem, entry) per operator kind, in enumerator order.  A row names PDSE_OP_<KIND>, the
+// descriptor pdse_<stem>_desc, its launcher pdse_<stem>_launch (and the member <stem> of a plan's descriptor union), and the
+// public name of the direct launch, the one irregular part.  Everything that exists once per operator is generated from it:
+// the launcher prototypes below, and in capi.hip the union, the size and launch switches and the direct entries, with a
+// static_assert per row that it sits at its enumerator's index.  include/pdse.h, the ABI document, stays written out.
+#define PDSE_OPS(X)                                                                            \
+  X(GCONV, gconv, pdse_gconv_f32)                                                              \
+  X(TIME, time, pdse_time_embed_f32)                                                           \
+  X(EW, ew, pdse_ew_f32)                                                                       \
+  X(COMPAND, compand, pdse_compand_f32)                                                        \
+  X(WAVPREP, wavprep, pdse_wavprep_f32)                                                        \
+  X(OLA, ola, pdse_ola_f32)                                                                    \
+  X(SIGMA, sigma, pdse_sigma_mask_f32)                                                         \
+  X(LN, ln, pdse_layernorm_f32)                                                                \
+  X(LSTM, lstm, pdse_lstm_f32)                                                                 \
+  X(ROWLN, rowln, pdse_rowln_prelu_f32)                                                        \
+  X(CHLN, chln, pdse_chln_f32)                                                                 \
+  X(ATTN, attn, pdse_attention_f32)                                                            \
+  X(GRU, gru, pdse_bigru_f32)                                                                  \
+  X(GNCOMB, gncomb, pdse_gn_combine_f32)                                                       \
+  X(AHAM, aham, pdse_aham_f32)                                                                 \
+  X(QSAMPLE, qsample, pdse_qsample_f32)                                                        \
+  X(TRANSPOSE, transpose, pdse_transpose_f32)                                                  \
+  X(TCM, tcm, pdse_tcm_f32)                                                                    \
+  X(CRM, crm, pdse_crm_f32)                                                                    \
+  X(GCRNLAST, gcrnlast, pdse_gcrnlast_f32)                                                     \
+  X(MASKLOSS, maskloss, pdse_masked_mse_f32)                                                   \
+  X(GLSTM, glstm, pdse_glstm_f32)                                                              \
+  X(TCM2, tcm2, pdse_tcm2_bf16x3)                                                              \
+  X(BGLU, bglu, pdse_bglu_planes)                                                              \
+  X(PLANES, planes, pdse_split_planes)                                                         \
+  X(GLSTMP, glstmp, pdse_glstm_persistent_f32)   /* csrc/lstmp.hip */                          \
+  X(TCM2S, tcm2s, pdse_tcm2_stack_bf16x3)   /* csrc/tcm2.hip: the whole stack as one launch */ \
+  X(DENSE, dense, pdse_dense_layer_bf16x3)   /* csrc/dense.hip */                              \
+  X(ROWLNB, rowlnb, pdse_rowln_blocked_f32)                                                    \
+  X(METRICS, metrics, pdse_quality_metrics_f32)   /* csrc/metrics.hip */                       \
+  X(RESAMPLE, resample, pdse_pcm_resample_f32)   /* csrc/resample.hip */                       \
+  X(RANGE, range, pdse_range_hist)   /* csrc/range.hip */
+
+#define X(KIND, stem, entry) int pdse_##stem##_launch(const pdse_##stem##_desc* d, hipStream_t s);
+PDSE_OPS(X)
+#undef X
 int pdse_gconv2_launch(const pdse_gconv_desc* d, hipStream_t s);  // korder 1, validated by pdse_gconv_launch
 int pdse_gconv3_launch(const pdse_gconv_desc* d, hipStream_t s);  // korder 2 (split-bf16 BIGLU), validated there too
 int pdse_gconv4_launch(const pdse_gconv_desc* d, hipStream_t s);  // korder 3 (split-bf16 GEMM-shaped LINEAR / GLU)
-int pdse_time_launch(const pdse_time_desc* d, hipStream_t s);
-int pdse_ew_launch(const pdse_ew_desc* d, hipStream_t s);
-int pdse_compand_launch(const pdse_compand_desc* d, hipStream_t s);
-int pdse_wavprep_launch(const pdse_wavprep_desc* d, hipStream_t s);
-int pdse_ola_launch(const pdse_ola_desc* d, hipStream_t s);
-int pdse_sigma_launch(const pdse_sigma_desc* d, hipStream_t s);
-int pdse_ln_launch(const pdse_ln_desc* d, hipStream_t s);
-int pdse_lstm_launch(const pdse_lstm_desc* d, hipStream_t s);
-int pdse_rowln_launch(const pdse_rowln_desc* d, hipStream_t s);
-int pdse_chln_launch(const pdse_chln_desc* d, hipStream_t s);
-int pdse_attn_launch(const pdse_attn_desc* d, hipStream_t s);
-int pdse_gru_launch(const pdse_gru_desc* d, hipStream_t s);
-int pdse_gncomb_launch(const pdse_gncomb_desc* d, hipStream_t s);
-int pdse_aham_launch(const pdse_aham_desc* d, hipStream_t s);
-int pdse_qsample_launch(const pdse_qsample_desc* d, hipStream_t s);
-int pdse_transpose_launch(const pdse_transpose_desc* d, hipStream_t s);
-int pdse_tcm_launch(const pdse_tcm_desc* d, hipStream_t s);
-int pdse_crm_launch(const pdse_crm_desc* d, hipStream_t s);
-int pdse_gcrnlast_launch(const pdse_gcrnlast_desc* d, hipStream_t s);
-int pdse_maskloss_launch(const pdse_maskloss_desc* d, hipStream_t s);
-int pdse_glstm_launch(const pdse_glstm_desc* d, hipStream_t s);
-int pdse_glstmp_launch(const pdse_glstmp_desc* d, hipStream_t s);   /* csrc/lstmp.hip */
-int pdse_tcm2_launch(const pdse_tcm2_desc* d, hipStream_t s);
-int pdse_tcm2s_launch(const pdse_tcm2s_desc* d, hipStream_t s);   /* csrc/tcm2.hip: the whole stack as one launch */
-int pdse_bglu_launch(const pdse_bglu_desc* d, hipStream_t s);
-int pdse_planes_launch(const pdse_planes_desc* d, hipStream_t s);
-int pdse_dense_launch(const pdse_dense_desc* d, hipStream_t s);     /* csrc/dense.hip */
-int pdse_rowlnb_launch(const pdse_rowlnb_desc* d, hipStream_t s);
-int pdse_metrics_launch(const pdse_metrics_desc* d, hipStream_t s);   /* csrc/metrics.hip */
-int pdse_resample_launch(const pdse_resample_desc* d, hipStream_t s);   /* csrc/resample.hip */
-int pdse_range_launch(const pdse_range_desc* d, hipStream_t s);   /* csrc/range.hip */
-int pdse_range_validate(const pdse_range_desc* d);                 /* reads the row table back and checks it (direct launches, plan_add) */
 int pdse_gru3_launch(const pdse_gru_desc* d, hipStream_t s);   /* csrc/gru3.hip, reached through pdse_gru_launch */
+int pdse_range_validate(const pdse_range_desc* d);                 /* reads the row table back and checks it (direct launches, plan_add) */
 #endif

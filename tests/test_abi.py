@@ -37,6 +37,99 @@ def test_descriptor_sizes_match(lib):
     assert handle.pdse_desc_size(99) == -1
 
 
+def _header_text():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pdse.h")).read(), flags=re.S)
+
+
+def _mirror_key(name):
+    """pdse_xyz_desc and XyzDesc name the same struct: case and underscores do not count."""
+    name = name.lower().replace("_", "")
+    return name[4:] if name.startswith("pdse") else name
+
+
+def _mirrors(lib):
+    import ctypes as C
+
+    found = [v for v in vars(lib).values() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure]
+    table = {_mirror_key(v.__name__): v for v in found}
+    assert len(table) == len(found)
+    return table
+
+
+def _header_structs():
+    """Every struct typedef of include/pdse.h as a ctypes structure built from its declaration (a test helper, not a binding)."""
+    import ctypes as C
+
+    text = _header_text()
+    bounds = {k: int(v) for k, v in re.findall(r"^#define\s+(\w+)\s+(\d+)\s*$", text, flags=re.M)}
+    types = {"int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "unsigned long long": C.c_ulonglong}
+    item = r"\w+(?:\[\w+\])?"
+    structs = {}
+    for name, body in re.findall(r"typedef struct (\w+) \{(.*?)\} \1;", text, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            m = re.fullmatch(r"(?:const\s+)?([a-z]\w*(?: long long)?)\s*(\*?)\s*(%s(?:\s*,\s*%s)*)" % (item, item), decl)
+            assert m, (name, decl)
+            base, star, names = m.groups()
+            names = re.split(r"\s*,\s*", names)
+            assert not star or len(names) == 1, (name, decl)     # `T* a, b` would make only a a pointer
+            typ = C.c_void_p if star else types[base]
+            for n in names:
+                n, _, dim = n.partition("[")
+                dim = dim.rstrip("]")
+                fields.append((n, typ * (int(dim) if dim.isdigit() else bounds[dim]) if dim else typ))
+        types[name] = structs[name] = type(name, (C.Structure,), {"_fields_": fields})
+    return structs
+
+
+def test_operator_table_matches_header(lib):
+    """include/pdse.h names each operator three times - PDSE_OP_<KIND>, pdse_<kind>_desc and the direct entry that takes that
+    descriptor; a row of _lib.OPS must bind exactly those three together, with no row and no declaration left over."""
+    text = _header_text()
+    kinds = {k: int(n) for k, n in re.findall(r"\bPDSE_OP_(\w+)\s*=\s*(\d+)", text)}
+    entries = dict(re.findall(r"^int (pdse_\w+)\(const (pdse_\w+_desc)\* d, pdse_stream_t s\);", text, flags=re.M))
+    mirrors = _mirrors(lib)
+    assert len(kinds) == len(set(kinds.values())) == len(entries) == len(lib.OPS) == 32
+    rows = {}
+    for kind, typ, entry in lib.OPS:
+        assert kind not in rows, kind
+        rows[kind] = (typ, entry)
+    used = set()
+    for name, n in kinds.items():
+        assert getattr(lib, "OP_" + name) == n, name
+        typ, entry = rows.pop(n)
+        struct = "pdse_%s_desc" % name.lower()
+        assert entries.get(entry) == struct, (name, entry)
+        assert mirrors[_mirror_key(struct)] is typ, (name, typ.__name__)
+        used.add(entry)
+    assert not rows and used == set(entries)
+    assert [k for k, _, _ in lib.OPS] == sorted(kinds.values())
+    assert lib.DESC_TYPES == {k: t for k, t, _ in lib.OPS} and lib.KIND_OF == {t: k for k, t, _ in lib.OPS}
+    assert lib._DIRECT == {k: e for k, _, e in lib.OPS} and used <= set(lib.EXPORTS)
+
+
+def test_descriptor_layouts_match_header(lib):
+    """Field by field, not just sizeof: the same fields in the same order, each with the header's name (a trailing underscore
+    may be added: `in` is a Python keyword), offset and size, and a pointer exactly where the header has one."""
+    import ctypes as C
+
+    def is_pointer(t):
+        while hasattr(t, "_length_"):
+            t = t._type_
+        return t is C.c_void_p
+
+    structs, mirrors = _header_structs(), _mirrors(lib)
+    assert {_mirror_key(n) for n in structs} == set(mirrors) and len(structs) == len(mirrors) == 34
+    for name, want in structs.items():
+        have = mirrors[_mirror_key(name)]
+        assert len(have._fields_) == len(want._fields_) and C.sizeof(have) == C.sizeof(want), name
+        for (hn, ht), (wn, wt) in zip(have._fields_, want._fields_):
+            assert hn in (wn, wn + "_"), (name, hn, wn)
+            h, w = getattr(have, hn), getattr(want, wn)
+            assert (h.offset, h.size) == (w.offset, w.size), (name, hn)
+            assert is_pointer(ht) == is_pointer(wt), (name, hn)
+
+
 def test_argument_errors_do_not_need_a_device(lib):
     with pytest.raises(lib.PdseError, match="null"):
         lib.launch(lib.GconvDesc())
