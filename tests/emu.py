@@ -483,6 +483,12 @@ def run_glstmp(d, mem):
             yflat[idx] = h2[g]
 
 
+def _own_frames(d, mem):
+    """[B, 1, T] mask of an utterance's own frames (pdse_tcm_desc.frames / pdse_tcm2_desc.frames, clamped to 0..T; NULL: all)."""
+    fr = mem.arr(d.frames, d.B, np.int32) if d.frames else np.full(d.B, d.T)
+    return np.arange(d.T)[None, None, :] < np.clip(fr, 0, d.T)[:, None, None]
+
+
 def run_tcm(d, mem):
     """pdse_tcm_desc: fused TCM residual block + the next block's conv1, from the packed operands."""
     B, T, dil = d.B, d.T, d.dil
@@ -493,8 +499,10 @@ def run_tcm(d, mem):
     xf = mem.arr(d.xf, 256).reshape(2, 64, 2)
     xf2 = mem.arr(d.xf2, 128).reshape(64, 2)
     pre = []
+    own = _own_frames(d, mem)
     for which, slope in ((0, d.slope_main), (1, d.slope_mask)):
         v = np.where(h > 0, h, np.float32(slope) * h) * xf[which, :, 0][None, :, None] + xf[which, :, 1][None, :, None]
+        v = np.where(own, v, 0.0)                    # frames: the transformed h reads as zero from the utterance's own end on
         vp = np.zeros((B, 64, T + 4 * dil))
         vp[:, :, 2 * dil:2 * dil + T] = v
         cols = np.concatenate([vp[:, :, k * dil:k * dil + T] for k in range(5)], axis=1)   # [B, 320, T], row = tap*64 + c
@@ -553,6 +561,8 @@ def run_tcm2(d, mem):
         xn = par[576:].reshape(64, 4)
         vm = xn[:, 0][None, :, None] * np.where(ho > 0, ho, np.float32(d.slope_main_next) * ho) + xn[:, 1][None, :, None]
         vk = xn[:, 2][None, :, None] * np.where(ho > 0, ho, np.float32(d.slope_mask_next) * ho) + xn[:, 3][None, :, None]
+        own = _own_frames(d, mem)                     # frames: hs_out is stored as zeros from the utterance's own end on
+        vm, vk = np.where(own, vm, np.float32(0)), np.where(own, vk, np.float32(0))
         mem.arr(d.hs_out, int(np.prod(P.tcm2_hs_shape(B, T, npl))), np.int16)[:] = P.tcm2_split_h(vm.astype(np.float32), vk.astype(np.float32), npl).view(np.int16).reshape(-1)
 
 
