@@ -134,7 +134,13 @@ typedef struct pdse_gconv_desc {
   /* Dual-phase stride-(1,2) ConvTranspose2d (BIGLU only, korder 1): one launch computes the even
      output bins f_o = 2j (weights w0/w1 over all ntaps taps) AND the odd bins 2j+1 (weights w2/w3
      over the taps selected by p1mask, ksteps1 k-steps), stores them side by side (out_sf = 2 bin
-     strides).  w2 == NULL: single phase.  Fout1 = number of valid odd bins (j < Fout1). */
+     strides).  w2 == NULL: single phase.  Fout1 = number of valid odd bins (j < Fout1).
+     korder 5, GLU, w2 == NULL and p1mask == 1: this launch is complete by itself (p1mask / Fout1 change nothing in it), and the
+     NEXT operator of the plan is its odd phase - a descriptor of its own with the same sources, B, Tout and Cout and ONE tap,
+     this launch's tap 0, over Fout1 <= Fout bins, Cout <= 32.  pdse_plan_add (and pdse_plan_load) refuse any other operator behind
+     a marked one.  A plan that runs both in one call runs them as one launch that gathers the input once (csrc/gconv4.hip);
+     every output element is bit for bit that of the two launches.  Run alone (a direct launch, a range that ends between
+     the two) either descriptor is the launch it always was. */
   int32_t ksteps1;
   const float* w2;
   const float* w3;

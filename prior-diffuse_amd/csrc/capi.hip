@@ -104,6 +104,33 @@ static int launch_op(const pdse_op& op, hipStream_t s) {
   }
 }
 
+// A korder 5 GLU convolution whose descriptor names the next operator as its odd phase (pdse.h: p1mask with w2 == NULL).
+static bool names_odd_phase(const pdse_op& op) {
+  return op.kind == PDSE_OP_GCONV && op.d.gconv.korder == 5 && op.d.gconv.p1mask != 0 && op.d.gconv.w2 == nullptr;
+}
+
+// The operator about to follow the plan's last one: behind a descriptor that names its odd phase comes that phase and nothing
+// else, checked here, once (pdse_plan_add, pdse_plan_load), so that a run is launches only.
+static int check_follows(const pdse_plan* p, const pdse_op& op) {
+  if (p->ops.empty() || !names_odd_phase(p->ops.back())) return 0;
+  if (op.kind != PDSE_OP_GCONV) {
+    pdse_set_error("plan: the operator behind a gconv that names its odd phase (p1mask, korder 5) must be that phase");
+    return 1;
+  }
+  return pdse_gconv_pair_check(&p->ops.back().d.gconv, &op.d.gconv);
+}
+
+// Such a pair runs as one launch (csrc/gconv4.hip) when both operators lie in the range being run; *n: operators consumed.
+static int launch_at(const pdse_plan* p, const int i, const int end, hipStream_t s, int* n) {
+  const pdse_op& op = p->ops[i];
+  *n = 1;
+  if (names_odd_phase(op) && i + 1 < end) {
+    *n = 2;
+    return pdse_gconv4_pair_launch(&op.d.gconv, &p->ops[i + 1].d.gconv, s);
+  }
+  return launch_op(op, s);
+}
+
 // What a direct launch checks before the launcher's own argument checks: nothing, except for the range audit, whose row
 // table is device data (pdse_plan_add checks it at add time instead, so that a plan run is launches only).
 template <typename D>
@@ -152,6 +179,7 @@ int pdse_plan_add(pdse_plan* p, int op_kind, const void* desc, int tag) {
   op.kind = op_kind;
   op.tag = tag;
   memcpy(&op.d, desc, (size_t)sz);
+  if (check_follows(p, op)) return 1;
   p->ops.push_back(op);
   return 0;
 }
@@ -192,8 +220,8 @@ int pdse_plan_run_range(pdse_plan* p, int begin, int end, pdse_stream_t s) {
   }
   device_guard dg(p);
   if (!dg.ok) return 1;
-  for (int i = begin; i < end; ++i)
-    if (int rc = launch_op(p->ops[i], (hipStream_t)s)) return rc;
+  for (int i = begin, n = 1; i < end; i += n)
+    if (int rc = launch_at(p, i, end, (hipStream_t)s, &n)) return rc;
   return 0;
 }
 
@@ -251,9 +279,9 @@ int pdse_plan_time_ops(pdse_plan* p, int begin, int end, pdse_stream_t s, float*
     if (pdse_check_hip(hipEventCreate(&e), "event create")) return 1;
   int rc = 0;
   (void)hipEventRecord(ev[0], st);
-  for (int i = 0; i < n && !rc; ++i) {
-    rc = launch_op(p->ops[begin + i], st);
-    (void)hipEventRecord(ev[i + 1], st);
+  for (int i = 0, k = 1; i < n && !rc; i += k) {   // a phase pair is one launch: its time goes to the first operator, 0 to the second
+    rc = launch_at(p, begin + i, end, st, &k);
+    for (int q = 1; q <= k; ++q) (void)hipEventRecord(ev[i + q], st);
   }
   if (!rc) rc = pdse_check_hip(hipEventSynchronize(ev[n]), "event sync");
   for (int i = 0; i < n && !rc; ++i) rc = pdse_check_hip(hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]), "elapsed");
@@ -271,7 +299,8 @@ int pdse_plan_time_tag(pdse_plan* p, int tag, pdse_stream_t s, float* ms_out, in
   hipStream_t st = (hipStream_t)s;
   std::vector<hipEvent_t> ev;
   int rc = 0, cnt = 0;
-  for (size_t i = 0; i < p->ops.size() && !rc; ++i) {
+  const int nops = (int)p->ops.size();
+  for (int i = 0, k = 1; i < nops && !rc; i += k) {   // count_out counts launches: a phase pair is one
     const bool hit = p->ops[i].tag == tag;
     if (hit) {
       hipEvent_t a, b;
@@ -280,13 +309,13 @@ int pdse_plan_time_tag(pdse_plan* p, int tag, pdse_stream_t s, float* ms_out, in
         break;
       }
       (void)hipEventRecord(a, st);
-      rc = launch_op(p->ops[i], st);
+      rc = launch_at(p, i, nops, st, &k);
       (void)hipEventRecord(b, st);
       ev.push_back(a);
       ev.push_back(b);
       ++cnt;
     } else {
-      rc = launch_op(p->ops[i], st);
+      rc = launch_at(p, i, nops, st, &k);
     }
   }
   if (!rc) rc = pdse_check_hip(hipStreamSynchronize(st), "stream sync");
@@ -424,6 +453,10 @@ int pdse_plan_load(const char* path, pdse_plan** out) {
       if (!v) continue;
       if (!rebase(v)) return fail("plan_load: a descriptor points outside every recorded region");
       memcpy(base + offs[k], &v, 8);
+    }
+    if (check_follows(p, op)) {
+      const std::string why = pdse_last_error();
+      return fail(why.c_str());
     }
     p->ops.push_back(op);
   }

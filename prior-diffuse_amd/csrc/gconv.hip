@@ -149,8 +149,10 @@ __global__ __launch_bounds__(256) void gconv_kernel(const pdse_gconv_desc d) {
     }                              \
   } while (0)
 
-int pdse_gconv_launch(const pdse_gconv_desc* d, hipStream_t s) {
+// dry: the argument checks only, korder 5 (what pdse_gconv_pair_check asks of either descriptor of a pair)
+static int gconv_launch(const pdse_gconv_desc* d, hipStream_t s, const bool dry) {
   PDSE_REQUIRE(d != nullptr, "null descriptor");
+  PDSE_REQUIRE(!dry || d->korder == 5, "a phase pair is two korder 5 launches");
   PDSE_REQUIRE(d->in0.ptr && d->out && d->w0 && d->taps, "null pointer (in0/out/w0/taps)");
   PDSE_REQUIRE(d->B > 0 && d->B <= 65535 && d->Tout > 0 && d->Fout > 0, "bad output extents");
   PDSE_REQUIRE(d->Cout > 0 && d->ntaps > 0 && d->out_cr > 0, "bad Cout/ntaps/out_cr");
@@ -198,7 +200,7 @@ int pdse_gconv_launch(const pdse_gconv_desc* d, hipStream_t s) {
     PDSE_REQUIRE(!d->cin1, "korder 1 needs Cin >= 2");
     return pdse_gconv2_launch(d, s);
   }
-  if (d->korder >= 3 && d->korder <= 5) return pdse_gconv4_launch(d, s);   // split-bf16 (3) / plain bf16 (4) / f16x2 (5) GEMM-shaped convolutions (gconv4.hip)
+  if (d->korder >= 3 && d->korder <= 5) return dry ? 0 : pdse_gconv4_launch(d, s);   // split-bf16 (3) / plain bf16 (4) / f16x2 (5) GEMM-shaped convolutions (gconv4.hip)
   if (d->korder == 2) {   // split-bf16 BIGLU blocks (gconv3.hip)
     PDSE_REQUIRE(d->resid == nullptr, "BIGLU has no residual input");
     PDSE_REQUIRE(d->act == PDSE_ACT_NONE || d->act == PDSE_ACT_PRELU, "BIGLU stages end in PReLU or no activation");
@@ -250,4 +252,14 @@ int pdse_gconv_launch(const pdse_gconv_desc* d, hipStream_t s) {
   }
 #undef LAUNCH
   return pdse_check_launch("gconv");
+}
+
+int pdse_gconv_launch(const pdse_gconv_desc* d, hipStream_t s) { return gconv_launch(d, s, false); }
+
+// d: a korder 5 GLU launch marked as the even output bins of a transposed convolution (pdse.h: p1mask with w2 == NULL), e: the
+// operator behind it in a plan.  Both descriptors by themselves, then that e is d's odd phase in a form csrc/gconv4.hip runs as
+// one launch.  No launch: a plan checks a pair once, when its second operator is added.
+int pdse_gconv_pair_check(const pdse_gconv_desc* d, const pdse_gconv_desc* e) {
+  if (gconv_launch(d, nullptr, true) || gconv_launch(e, nullptr, true)) return 1;
+  return pdse_gconv4_pair_check(d, e);
 }

@@ -398,7 +398,7 @@ static int launch4(const pdse_gconv_desc* d, hipStream_t s, const int mtiles) {
 }
 
 // korder 3: LINEAR / GLU, one or two sources of a multiple of 16 channels, no load transform; validated by pdse_gconv_launch
-int pdse_gconv4_launch(const pdse_gconv_desc* d, hipStream_t s) {
+static int check4(const pdse_gconv_desc* d) {
   const bool two = d->in1.C > 0;
   // lane offsets are 32-bit BYTE offsets from a scalar channel base
   const long long span0 = 4 * ((long long)d->B * d->in0.sb + 40ll * d->in0.sc), span1 = two ? 4 * ((long long)d->B * d->in1.sb + 40ll * d->in1.sc) : 0;
@@ -417,9 +417,244 @@ int pdse_gconv4_launch(const pdse_gconv_desc* d, hipStream_t s) {
                    "no load transform / pad row, 32-bit gather offsets");
     return 1;
   }
+  return 0;
+}
+
+int pdse_gconv4_launch(const pdse_gconv_desc* d, hipStream_t s) {
+  if (check4(d)) return 1;
   const int mtiles = (d->Cout + 31) / 32;
   if (d->epi == PDSE_EPI_GLU) return mtiles >= 2 ? launch4<PDSE_EPI_GLU, 2>(d, s, mtiles) : launch4<PDSE_EPI_GLU, 1>(d, s, mtiles);
   if (mtiles >= 4) return launch4<PDSE_EPI_LINEAR, 4>(d, s, mtiles);
   if (mtiles >= 2) return launch4<PDSE_EPI_LINEAR, 2>(d, s, mtiles);
   return launch4<PDSE_EPI_LINEAR, 1>(d, s, mtiles);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Phase pair of a stride-(1,2) transposed convolution (GLU, f16x2) as one launch.  d: the even output bins 2j (taps {j, j-1}),
+// e: the odd bins 2j+1 (tap {j}, which is d's tap 0).  The workgroup walks d's chunks; in the chunks of tap 0 the ring also
+// carries e's fragments of the same K blocks, and the split B operand the wave holds for d's products is multiplied by them
+// as well: one gather and three product sets where the two launches gathered 2 + 1 times.  e's accumulators see their K
+// blocks in the order of e's own launch ((source, channel block), the order d's tap-0 chunks come in) and each product is
+// the same instruction on the same operands, so every element equals the separate launch bit for bit.  Positions are d's;
+// the odd bin of a lane exists while j < e.Fout (one bin fewer when the output row length is odd) and is masked on the
+// store.  Ring: [2 buffers][G4_CH blocks][2 phases x 2 branches x MT][2 planes x 64] uint4.
+// ---------------------------------------------------------------------------------------------------------------
+template <int MT, bool BLK>
+__global__ __launch_bounds__(512, 2) void gconv4_pair_kernel(const pdse_gconv_desc d, const pdse_gconv_desc e) {
+  constexpr int NP = 2, FB = 64 * NP;
+  constexpr int FR = 2 * MT, FR2 = 2 * FR;   // fragments per K block: d's alone, d's and e's
+  extern __shared__ uint4 ring[];
+  const unsigned ring_base = (unsigned)(uintptr_t)ring;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 31, h = lane >> 5;
+  const int b = blockIdx.y;
+  const int P = d.Tout * d.Fout;
+  const int p = (blockIdx.x * 8 + wave) * 32 + col;
+  const bool pvalid = p < P;
+  const int t = pvalid ? p / d.Fout : 0;
+  const int j = pvalid ? p - t * d.Fout : 0;
+  const int mtiles = (d.Cout + 31) >> 5;
+  const int mt0 = blockIdx.z * MT;
+
+  const int cbn0 = d.in0.C >> 4, cbn1 = d.in1.C >> 4;
+  const int cps0 = (cbn0 + G4_CH - 1) / G4_CH, cps1 = (cbn1 + G4_CH - 1) / G4_CH;
+  const int nch0 = d.ntaps * cps0, nch = nch0 + d.ntaps * cps1;
+
+  auto uni = [](const int v) { return __builtin_amdgcn_readfirstlane(v); };
+  auto decode = [&](const int ci) {
+    g4_chunk c;
+    c.s = uni(ci >= nch0);
+    const int q = c.s ? ci - nch0 : ci, cps = c.s ? cps1 : cps0, cbn = c.s ? cbn1 : cbn0;
+    c.tap = uni(q / cps);
+    c.cb0 = uni((q - c.tap * cps) * G4_CH);
+    c.n = uni(min(G4_CH, cbn - c.cb0));
+    c.kb0 = uni((c.s ? d.ntaps * cbn0 : 0) + c.tap * cbn + c.cb0);
+    return c;
+  };
+  // fragments f < FR: d's (branch f / MT, tile f % MT); FR <= f < FR2, in the chunks of tap 0 only: e's, K block
+  // (source, channel block) of its one-tap weights
+  auto dma = [&](const g4_chunk& c, const int buf) {
+    const int nf = c.tap == 0 ? FR2 : FR;
+    const int kb1 = (c.s ? cbn0 : 0) + c.cb0;
+    const int npieces = c.n * nf * NP;
+    for (int pc = __builtin_amdgcn_readfirstlane(wave); pc < npieces; pc += 8) {
+      const int i = pc / (nf * NP), rem = pc - i * (nf * NP), f = rem / NP, part = rem - f * NP;
+      const bool odd = f >= FR;
+      const int g = odd ? f - FR : f, br = g / MT, m = g - br * MT;
+      if (mt0 + m < mtiles) {
+        const float* const w = odd ? (br ? e.w1 : e.w0) : (br ? d.w1 : d.w0);
+        const uint4* src = reinterpret_cast<const uint4*>(w) + ((size_t)((odd ? kb1 : c.kb0) + i) * mtiles + mt0 + m) * FB + part * 64 + lane;
+        glds16_g4(src, ring + ((buf * G4_CH + i) * FR2 + f) * FB + part * 64);
+      }
+    }
+  };
+  auto gather = [&](const g4_chunk& c, g4_raw<BLK>& raw, bool& inb) {
+    const bool s1 = c.s != 0;
+    const float* const sptr = s1 ? d.in1.ptr : d.in0.ptr;
+    const int64_t ssb = s1 ? d.in1.sb : d.in0.sb, ssc = s1 ? d.in1.sc : d.in0.sc, sst = s1 ? d.in1.st : d.in0.st,
+                  ssf = s1 ? d.in1.sf : d.in0.sf;
+    int dt = 0, df = 0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      dt = c.tap == k ? d.tap_dt[k] : dt;
+      df = c.tap == k ? d.tap_df[k] : df;
+    }
+    const int tin = t + dt, fin = j * d.sf_in + df;
+    inb = pvalid && fin >= 0 && fin < d.Fin && tin >= 0 && tin < d.Tin;
+    if constexpr (BLK) {
+      const unsigned off = 4u * (unsigned)((inb ? (int64_t)b * ssb + (int64_t)tin * sst + (int64_t)fin * ssf : 0) + (int64_t)h * ssc);
+#pragma unroll
+      for (int i = 0; i < G4_CH; ++i) {
+        if (i < c.n) {
+          const float* base = sptr + (int64_t)(2 * (c.cb0 + i)) * ssc;
+          raw.v[i][0] = g4_load16(base, off);
+          raw.v[i][1] = g4_load16(base + 4, off);
+        }
+      }
+    } else {
+      const unsigned off = 4u * (unsigned)((inb ? (int64_t)b * ssb + (int64_t)tin * sst + (int64_t)fin * ssf : 0) + (int64_t)(8 * h) * ssc);
+#pragma unroll
+      for (int i = 0; i < G4_CH; ++i) {
+        if (i < c.n) {
+          const float* base = sptr + (int64_t)(16 * (c.cb0 + i)) * ssc;
+#pragma unroll
+          for (int e_ = 0; e_ < 8; ++e_) raw.v[i][e_] = g4_load(base + (int64_t)e_ * ssc, off);
+        }
+      }
+    }
+  };
+
+  f32x16 acc[FR2];   // [phase][branch][tile]
+#pragma unroll
+  for (int f = 0; f < FR2; ++f)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[f][r] = 0.f;
+
+  // NF = FR2: a chunk of tap 0 (both phases); NF = FR: any other chunk.  Two instantiations instead of a run-time
+  // fragment count: which registers a ring read writes, and which are live across a K block, stays a compile-time fact
+  // (see compute() of gconv4_kernel on reads into dead registers).  The fragment registers hold ONE phase's FR fragments: d's
+  // products of a K block are followed by the reads of e's fragments of the same block into the registers they free, and
+  // e's products by the reads of d's fragments of the next block.
+  auto compute = [&](auto nf_tag, const g4_chunk& c, const g4_raw<BLK>& raw, const bool inb, const int buf) {
+    constexpr int NF = decltype(nf_tag)::value;
+    const bool elu = uni((c.s ? d.in1.act : d.in0.act) == PDSE_ACT_ELU) != 0;
+    u32x4 af[FR][NP];
+    const unsigned wa0 = ring_base + (unsigned)((((buf * G4_CH) * FR2) * FB + lane) * 16);
+#pragma unroll
+    for (int f = 0; f < FR; ++f) g4_lds_read3(wa0 + f * (FB * 16), af[f]);
+#pragma unroll
+    for (int i = 0; i < G4_CH; ++i) {
+      if (i < c.n) {
+        float x[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = inb ? raw.get(i, q) : 0.f;
+        if (elu) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) x[q] = x[q] < 0.f ? fast_exp(x[q]) - 1.0f : x[q];
+        }
+        uint4 bp[NP];
+        g4_split(x, bp);
+        g4_lds_wait(af);
+        const bool more = i + 1 < c.n;
+        const unsigned wi = ring_base + (unsigned)((((buf * G4_CH + i) * FR2) * FB + lane) * 16);
+        const unsigned wn = wi + FR2 * FB * 16;
+        if constexpr (NF == FR2) {
+#pragma unroll
+          for (int f = 0; f < FR; ++f) {
+            acc[f] = g4_mfma6(af[f], bp, acc[f]);
+            g4_lds_read3(wi + (FR + f) * (FB * 16), af[f]);
+          }
+          g4_lds_wait(af);
+        }
+#pragma unroll
+        for (int f = 0; f < FR; ++f) {
+          acc[NF - FR + f] = g4_mfma6(af[f], bp, acc[NF - FR + f]);
+          if (i + 1 < G4_CH && more) g4_lds_read3(wn + f * (FB * 16), af[f]);
+        }
+      }
+    }
+  };
+  auto compute_chunk = [&](const g4_chunk& c, const g4_raw<BLK>& raw, const bool inb, const int buf) {
+    if (c.tap == 0) compute(std::integral_constant<int, FR2>{}, c, raw, inb, buf);
+    else compute(std::integral_constant<int, FR>{}, c, raw, inb, buf);
+  };
+
+  g4_raw<BLK> rawA, rawB;
+  bool inbA = false, inbB = false;
+  g4_chunk cA = decode(0), cB = cA;
+  gather(cA, rawA, inbA);
+  dma(cA, 0);
+  __syncthreads();
+  g4_landed(rawA);
+  for (int ci = 0; ci < nch; ci += 2) {
+    const bool hasB = ci + 1 < nch;
+    if (hasB) {
+      cB = decode(ci + 1);
+      gather(cB, rawB, inbB);
+      dma(cB, 1);
+    }
+    compute_chunk(cA, rawA, inbA, 0);
+    __syncthreads();
+    if (!hasB) break;
+    g4_landed(rawB);
+    if (ci + 2 < nch) {
+      cA = decode(ci + 2);
+      gather(cA, rawA, inbA);
+      dma(cA, 0);
+    }
+    compute_chunk(cB, rawB, inbB, 1);
+    __syncthreads();
+    g4_landed(rawA);
+  }
+  const float us0 = pow2i(-(PDSE_F16_ACT_EXP + d.wexp)), us1 = pow2i(-(PDSE_F16_ACT_EXP + e.wexp));
+#pragma unroll
+  for (int f = 0; f < FR2; ++f)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[f][r] *= f < FR ? us0 : us1;
+  gconv_epilogue<PDSE_EPI_GLU, MT>(d, tail_from_desc(d), acc, acc + MT, b, t, j, pvalid, lane, h, mt0, mtiles);
+  gconv_epilogue<PDSE_EPI_GLU, MT>(e, tail_from_desc(e), acc + FR, acc + FR + MT, b, t, j, pvalid && j < e.Fout, lane, h, mt0, mtiles);
+}
+
+template <int MT, bool BLK>
+static int launch4p(const pdse_gconv_desc* d, const pdse_gconv_desc* e, hipStream_t s, const int mtiles) {
+  const int P = d->Tout * d->Fout;
+  const dim3 grid(((P + 31) / 32 + 7) / 8, d->B, (mtiles + MT - 1) / MT), block(512);
+  const size_t lds = (size_t)2 * G4_CH * 4 * MT * 64 * 2 * sizeof(uint4);
+  static unsigned long long attr_mask = 0;
+  if (lds > 64 * 1024 && pdse_lds_attr((const void*)gconv4_pair_kernel<MT, BLK>, &attr_mask, "gconv4 pair lds attribute")) return 1;
+  hipLaunchKernelGGL((gconv4_pair_kernel<MT, BLK>), grid, block, lds, s, *d, *e);
+  return pdse_check_launch("gconv4 pair");
+}
+
+// That d and e are the two phases of one transposed convolution this kernel takes (each validated by itself before:
+// pdse_gconv_pair_check).  Checked once, when the pair enters a plan.
+int pdse_gconv4_pair_check(const pdse_gconv_desc* d, const pdse_gconv_desc* e) {
+  if (check4(d) || check4(e)) return 1;
+  auto same_src = [](const pdse_src& x, const pdse_src& y) {
+    return x.ptr == y.ptr && x.sb == y.sb && x.sc == y.sc && x.st == y.st && x.sf == y.sf && x.C == y.C && x.act == y.act && x.blk == y.blk;
+  };
+  const bool ok = d->korder == 5 && e->korder == 5 && d->epi == PDSE_EPI_GLU && e->epi == PDSE_EPI_GLU && d->w2 == nullptr &&
+                  e->w2 == nullptr && d->p1mask == 1 && d->Fout1 == e->Fout && same_src(d->in0, e->in0) && same_src(d->in1, e->in1) &&
+                  d->Tin == e->Tin && d->Fin == e->Fin && d->sf_in == e->sf_in && d->ntaps >= 1 && e->ntaps == 1 &&
+                  d->tap_dt[0] == e->tap_dt[0] && d->tap_df[0] == e->tap_df[0] && d->B == e->B && d->Tout == e->Tout &&
+                  d->Cout == e->Cout && e->Fout >= 1 && e->Fout <= d->Fout;
+  if (!ok) {
+    pdse_set_error("gconv4: p1mask on a korder 5 GLU launch says that the next launch is its odd phase: the same sources, batch, frames and "
+                   "channels, one tap that is this launch's tap 0, Fout1 bins (at most this launch's)");
+    return 1;
+  }
+  // One channel tile per workgroup only: with two (eight accumulators) the kernel needs more than the 256 registers a wave of a
+  // 512-thread workgroup can have and spills, and one tile per workgroup over several tiles would gather MORE often than the two
+  // launches do.  Stages of more than 32 channels stay two launches (nets.GcrnPlan marks none of them).
+  if (d->Cout > 32) {
+    pdse_set_error("gconv4: a phase pair runs as one launch for Cout <= 32 only");
+    return 1;
+  }
+  return 0;
+}
+
+// a pair that passed pdse_gconv4_pair_check
+int pdse_gconv4_pair_launch(const pdse_gconv_desc* d, const pdse_gconv_desc* e, hipStream_t s) {
+  return d->in0.blk ? launch4p<1, true>(d, e, s, 1) : launch4p<1, false>(d, e, s, 1);
 }

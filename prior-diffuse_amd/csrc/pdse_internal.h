@@ -67,6 +67,11 @@ PDSE_OPS(X)
 int pdse_gconv2_launch(const pdse_gconv_desc* d, hipStream_t s);  // korder 1, validated by pdse_gconv_launch
 int pdse_gconv3_launch(const pdse_gconv_desc* d, hipStream_t s);  // korder 2 (split-bf16 BIGLU), validated there too
 int pdse_gconv4_launch(const pdse_gconv_desc* d, hipStream_t s);  // korder 3 (split-bf16 GEMM-shaped LINEAR / GLU)
+// korder 5 GLU: the even (d) and odd (e) output bins of a transposed convolution as one launch (pdse.h: p1mask with w2 == NULL).
+// A plan checks the pair when e is added (capi.hip) and launches it unchecked afterwards.
+int pdse_gconv_pair_check(const pdse_gconv_desc* d, const pdse_gconv_desc* e);     // both descriptors, then:
+int pdse_gconv4_pair_check(const pdse_gconv_desc* d, const pdse_gconv_desc* e);    // that e is d's odd phase
+int pdse_gconv4_pair_launch(const pdse_gconv_desc* d, const pdse_gconv_desc* e, hipStream_t s);
 int pdse_gru3_launch(const pdse_gru_desc* d, hipStream_t s);   /* csrc/gru3.hip, reached through pdse_gru_launch */
 int pdse_range_validate(const pdse_range_desc* d);                 /* reads the row table back and checks it (direct launches, plan_add) */
 #endif

@@ -372,6 +372,8 @@ class PlanBase:
         d.epi, d.act, d.act_slope = epi, act, float(act_slope)
         if phase1 is not None and d.korder in (1, 2):
             d.p1mask, d.Fout1 = phase1["mask"], phase1["Fout1"]
+        elif phase1 is not None and d.korder == 5 and epi == L.EPI_GLU:    # no w2 / w3: the NEXT launch is the odd phase (include/pdse.h)
+            d.p1mask, d.Fout1 = phase1["mask"], phase1["Fout1"]
         if nx is not None:
             tiles = nx["tiles"]
             d.nx_n, d.nx_keep, d.nx_row0 = len(tiles), 1 if nx.get("keep") else 0, nx.get("row0", -1)
@@ -1266,6 +1268,9 @@ class GcrnPlan(PlanBase):
     split_bf16 = True       # gated (transposed) convolutions and the LSTM input projection as split-operand GEMMs (csrc/gconv4.hip)
     gemm_planes = 2         # ... in the f16x2 form (korder 5; 3: the three-plane bf16 split, korder 3 - both fp32-equivalent)
     block8 = True           # tensors between those GEMMs in blocks of 8 channels (16-byte gathers and stores)
+    fuse_phases = True      # (f16x2 GEMMs, stages of <= 32 channels) a decoder stage's even and odd output bins as ONE launch: the
+                            # even-bin descriptor names the next one as its odd phase and a plan runs the two together
+                            # (csrc/gconv4.hip, bit-identical); False: the descriptors carry no mark - two launches per stage
     persist_lstm = True     # B <= PERSIST_MAX_B and a plan that owns the GPU while it runs: the grouped LSTM as ONE persistent
                             # launch with register-resident weights (pdse_glstmp_desc, csrc/lstmp.hip) instead of T + 2 launches
     PERSIST_MAX_B = 4       # measured (tools/time_glstm.py --persist): 3.9 / 6.0 / 9.0 / 21.8 us per step at B = 1 / 2 / 4 / 8 against 11.4-12.0 for the wavefront
@@ -1539,6 +1544,7 @@ class GcrnPlan(PlanBase):
                     self.add(g, TAG_PRIOR)
                     break
                 dblk = blk and k >= 3          # d5, d4, d3 (read by the next decoder stage only)
+                fuse = self.fuse_phases and self.split_bf16 and self.gemm_planes == 2 and not self.force_generic   # korder 5 only
                 ist, (osb, osc, olo, ost, osf), ocr = lay(dblk, co, Fout)
                 for phase in (0, 1):
                     kk, taps = P.convT_phase_taps(1, 3, phase)
@@ -1549,7 +1555,7 @@ class GcrnPlan(PlanBase):
                                    bias1=self.w(p + ".conv2.bias"), post=P.bn_fold(self.sd, "bn%d_t_%d" % (k, br))),
                                out=self.d[n], out_strides=(osb, osc, olo, ost, 2 * osf), out_off=phase * osf, out_cr=ocr, B=B,
                                Tout=T, Fout=(Fout - phase + 1) // 2, tag=TAG_PRIOR, label="%s.ph%d" % (p, phase),
-                               s3g=self.split_bf16)
+                               s3g=self.split_bf16, phase1=dict(mask=1, Fout1=Fout // 2) if phase == 0 and fuse and co <= 32 else None)
                 Fin = Fout
                 if k > 1:
                     in0 = self.src(self.d[n], co, *ist, blk=8 if dblk else 0)
