@@ -103,16 +103,19 @@ int pdse_lstm_launch(const pdse_lstm_desc* d, hipStream_t s) {
 // h_t -> h_{t+1} inside a layer; layer 2 can work on frame t-2 while layer 1 works on frame t.  One launch
 // per wavefront step s = 0 .. T+1 carries three stages, each a 32-row x K=512 x 32-item matvec per workgroup:
 //   A  layer 1, frame s:        gates = gx1[s] + W_hh1 h1[s-1]           -> h1[s], LayerNorm partial sums
-//   B  layer-2 input, frame s-1: gx2 = rs_b (W'_ih2 h1[s-1] - mu_b R) + C  (LayerNorm 1 folded, below)
+//   B  layer-2 input, frame s-1: gx2 = rs_b (W'_ih2 (h1[s-1] - k_b) - (mu_b - k_b) R) + C  (LayerNorm 1 folded, below)
 //   C  layer 2, frame s-2:      gates = gx2 + W_hh2 h2[s-3]               -> h2[s-2] -> y
 // so the chain is T + 2 launches instead of 2 T, the [B,T,1024] LayerNorm output, the layer-2 input projection
 // GEMMs and their 210 MB gate buffer disappear (gx2 lives for two frames), and all 256 CUs have work
 // (3 x 128 workgroups at B = 32).
 //
-// LayerNorm folded into stage B:  W_ih LN(y) = rs (W' y) - rs mu (W' 1) + (W_ih beta),  W' = W_ih diag(gamma),
+// LayerNorm folded into stage B:  W_ih LN(y) = rs (W' y) - rs mu (W' 1) + (W_ih beta),  W' = W_ih diag(gamma), evaluated as
+// rs (W' (y - k) - (mu - k) W' 1) with k = the item's own first feature (exact for any k; with y near one value the plain form
+// subtracts two numbers of the size of the mean to get one of the size of the deviations),
 // with mu_b, rs_b = rsqrt(var_b + eps) over the 1024 interleaved outputs of both groups (stack(dim=-1) + flatten:
-// feature j = 2 u + g).  Stage A writes, per workgroup, the sums of h and h^2 over its 8 units for every batch
-// item; stage B adds the 128 partials in a fixed order (no atomics: results do not depend on scheduling).
+// feature j = 2 u + g).  Stage A writes, per slice, the sum of h and of (h - slice mean)^2 over its 8 units for every batch
+// item; stage B adds the 128 partials in a fixed order (no atomics: results do not depend on scheduling).  The second moment
+// travels as the sum of squared deviations from the slice's mean and is combined by Chan's formula.
 //
 // Operand layout: the state h is kept [H/8][2][Bp][4] (unit 8 kq + 2 i + hh at [kq][hh][b][i]), so that the B
 // operand of four consecutive k-steps is ONE 16-byte load per lane (the per-frame kernel issues four 4-byte loads),
@@ -199,6 +202,10 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
     const float* hs = q0 < 32 ? hsrc0 : hsrc1;
     const int kq = (q0 < 32 ? kq0 : kq1) + (q0 & 31);
     const float4* B4 = reinterpret_cast<const float4*>(hs) + ((size_t)kq * 2 + h) * Bp + bt * 32 + col;
+    // stage B, LayerNorm fold without its cancellation: W' (y - k) - (mu - k) W' 1 for ANY k; with k = the item's own first feature
+    // (within a few deviations of mu) both terms are of the size of the deviations, not of the mean.  Requested first: the
+    // subtraction from operand i then waits for operand i alone
+    const float k0 = stage == 1 ? hsrc0[(size_t)(bt * 32 + col) * 4] : 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
 #pragma unroll
@@ -206,6 +213,10 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
       bv[i] = B4[(size_t)i * 2 * Bp];
     }
     __builtin_amdgcn_sched_barrier(0);
+    if (stage == 1) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) bv[i].x -= k0, bv[i].y -= k0, bv[i].z -= k0, bv[i].w -= k0;
+    }
     if (trace) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       LSTAMP(2);
@@ -246,19 +257,28 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
       if (t > 0) c_old = d.cst2[ci];
     }
   }
+  float k0e = 0.f;                                   // stage B: the k of the fold, for the epilogue's item
   if (stage == 1) {
-    // LayerNorm statistics of frame t: 2 groups x H/8 slices partial (sum, sumsq) pairs per batch item, fixed order
+    k0e = hsrc0[(size_t)b * 4];
+    // LayerNorm statistics of frame t: 2 groups x H/8 slices partial (sum, sum of squared deviations from the slice's own mean)
+    // pairs per batch item, fixed order; a part's 8 entries are combined about the part's mean (Chan): no raw squares anywhere
     const int p = threadIdx.x >> 5;                  // 16 parts of 8 entries
     const float2* P2 = reinterpret_cast<const float2*>(d.part) + ((size_t)par * G * (H / 8)) * Bp + b;
-    float s1 = 0.f, s2 = 0.f;
+    float2 pv[8];
+    float s1 = 0.f, m2 = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float2 v = P2[(size_t)(p * 8 + e) * Bp];
-      s1 += v.x;
-      s2 += v.y;
+      pv[e] = P2[(size_t)(p * 8 + e) * Bp];
+      s1 += pv[e].x;
+    }
+    const float mp = s1 * (1.0f / 64.0f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float dv = pv[e].x * 0.125f - mp;
+      m2 += pv[e].y + 8.0f * (dv * dv);
     }
     stat[p][bb][0] = s1;
-    stat[p][bb][1] = s2;
+    stat[p][bb][1] = m2;
   }
   LSTAMP(3);
 #pragma unroll
@@ -289,21 +309,26 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
   }
   if (stage == 1) {
     if (!fin) return;                               // no further barrier in this stage
-    double s1 = 0.0, s2 = 0.0;
+    double s1 = 0.0;
 #pragma unroll
-    for (int p = 0; p < 16; ++p) {
-      s1 += (double)stat[p][bb][0];
-      s2 += (double)stat[p][bb][1];
-    }
+    for (int p = 0; p < 16; ++p) s1 += (double)stat[p][bb][0];
     const double n = (double)(G * H);
     const double mu = s1 / n;
-    const double var = fmax(s2 / n - mu * mu, 0.0);                // biased variance, like nn.LayerNorm
-    const float rs = (float)(1.0 / sqrt(var + (double)d.eps)), muf = (float)mu;
+    const float muf = (float)mu;
+    float m2 = 0.f;
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {                                  // the 16 parts of 64 about the mean (fp32: differences of means, no raw squares)
+      const float dv = stat[p][bb][0] * (1.0f / 64.0f) - muf;
+      m2 += stat[p][bb][1] + 64.0f * (dv * dv);
+    }
+    const double var = (double)m2 / n;                              // biased variance, like nn.LayerNorm
+    const float rs = (float)(1.0 / sqrt(var + (double)d.eps));
+    const float muk = (float)(mu - (double)k0e);                    // mu - k, k as subtracted from the operand above
     float* out = d.gx2 + (((size_t)par * G + g) * (4 * H)) * Bp;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const size_t row = (size_t)q * H + hu;
-      out[row * Bp + b] = rs * (gate[q] - muf * d.r2[(size_t)g * 4 * H + row]) + d.c2[(size_t)g * 4 * H + row];
+      out[row * Bp + b] = rs * (gate[q] - muk * d.r2[(size_t)g * 4 * H + row]) + d.c2[(size_t)g * 4 * H + row];
     }
     return;
   }
@@ -329,15 +354,22 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
   // LayerNorm partial sums over the 8 units of each slice (the same summation order at every batch size and for every NS)
   if (threadIdx.x < 32 * NS) {
     const int ps = threadIdx.x >> 5;
-    float s1 = 0.f, s2 = 0.f;
+    float v[8];
+    float s1 = 0.f, m2 = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const float v = stat[8 * ps + k][bb][0];
-      s1 += v;
-      s2 += v * v;
+      v[k] = stat[8 * ps + k][bb][0];
+      s1 += v[k];
+    }
+    // deviations from the slice's own mean: E[x^2] - mu^2 in fp32 loses the variance of a layer whose outputs sit near one value
+    const float m = s1 * 0.125f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float e = v[k] - m;
+      m2 += e * e;
     }
     float2* P2 = reinterpret_cast<float2*>(d.part) + (((size_t)par * G + g) * (H / 8) + slice + ps) * Bp + b;
-    *P2 = make_float2(s1, s2);
+    *P2 = make_float2(s1, m2);
   }
 }
 

@@ -8,7 +8,9 @@
 //   * 256 workgroups, each owning 4 hidden units of layer 1 and 4 of layer 2 of one group: their 16 + 16 + 16 gate rows
 //     (W_hh1 | W_ih2 diag(gamma_ln1) | W_hh2, K = 512 each = 96 KB) live in registers for all frames (48 per thread);
 //   * two-stage wavefront: at step s layer 1 works on frame s, layer 2 on frame s - 1 (LayerNorm 1 folded into its input
-//     projection exactly as in glstm_wave_kernel: W_ih LN(y) = rs (W' y - mu W' 1) + W_ih beta);
+//     projection exactly as in glstm_wave_kernel: W_ih LN(y) = rs (W' (y - k) - (mu - k) W' 1) + W_ih beta, k = the item's
+//     own feature 0, so that both terms are of the size of the deviations; the moments travel up one fixed tree as
+//     (sum, sum of squared deviations) pairs, combined by Chan's formula - no raw squares);
 //   * every step ends with each workgroup publishing its 8 x B new state values as 8-byte {tag = step + 1, value}
 //     granules (one sc1 store each: the data is the flag, MI355X_MICROARCH.md "R2"), and begins with every thread polling
 //     its share of the 1536 x B granules the workgroup needs (all of h1 for the LayerNorm and both matvecs, h2 of its
@@ -53,6 +55,20 @@ __device__ __forceinline__ float row_sum(float v) {
   v = dpp_add<0x140>(v);   // row_mirror
   return v;
 }
+// LayerNorm moments as (sum S, sum of squared deviations M) of n values each: two such sets combine to
+// S = Sa + Sb, M = Ma + Mb + (Sa - Sb)^2 / (2 n) (Chan) - no raw squares, so a layer whose outputs sit near one value keeps its
+// variance; symmetric in a and b, so both partners of an exchange end with the same bits.  inv2n = 1 / (2 n).
+__device__ __forceinline__ void mom_add(float& S, float& M, const float So, const float Mo, const float inv2n) {
+  const float dl = S - So;
+  M = (M + Mo) + (dl * dl) * inv2n;
+  S = S + So;
+}
+template <int CTRL>
+__device__ __forceinline__ void mom_dpp(float& S, float& M, const float inv2n) {
+  const float So = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, S), CTRL, 0xf, 0xf, false));
+  const float Mo = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, M), CTRL, 0xf, 0xf, false));
+  mom_add(S, M, So, Mo, inv2n);
+}
 __device__ __forceinline__ float rl(const float v, const int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
 
 __device__ __forceinline__ u64 gran_load(const u64* p) {
@@ -70,6 +86,7 @@ __global__ __launch_bounds__(512, BQ == 1 ? 4 : 2) void glstm_persist_kernel(con
   __shared__ __attribute__((aligned(16))) float x2[H * BQ];       // h2 of this group two frames back, [u][b]
   __shared__ float red[3][16][BQ];                                // gate-row sums: W_hh1 h1 | W'_ih2 y1 | W_hh2 h2
   __shared__ float lnp[8][BQ][2];                                 // LayerNorm partial sums per wave
+  __shared__ float kfold[BQ];                                     // the k of the LayerNorm fold (feature 0 of every item) for the gate threads
   __shared__ int dead;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wg = blockIdx.x, g = wg >> 7, u0 = (wg & 127) * UPW;
@@ -159,15 +176,22 @@ __global__ __launch_bounds__(512, BQ == 1 ? 4 : 2) void glstm_persist_kernel(con
 #pragma unroll
       for (int e = 0; e < BQ; ++e) v2[e] = 0.f;
     }
-    // LayerNorm 1 partial sums of this thread's two features, per item; fixed order: lanes by xor tree, waves 0..7
+    // LayerNorm 1 moments of this thread's two features, per item; one fixed tree: lanes by xor tree, rows, then the waves
 #pragma unroll
     for (int b = 0; b < BQ; ++b) {
       const float a = v1[b], c = v1[BQ + b];
-      const float s1 = row_sum(a + c), s2 = row_sum(a * a + c * c);
-      const float t1 = (rl(s1, 0) + rl(s1, 16)) + (rl(s1, 32) + rl(s1, 48)), t2 = (rl(s2, 0) + rl(s2, 16)) + (rl(s2, 32) + rl(s2, 48));
+      float S = a + c, M = 0.5f * ((a - c) * (a - c));       // n = 2
+      mom_dpp<0xB1>(S, M, 1.0f / 4.0f);                      // quad_perm [1,0,3,2]
+      mom_dpp<0x4E>(S, M, 1.0f / 8.0f);                      // quad_perm [2,3,0,1]
+      mom_dpp<0x141>(S, M, 1.0f / 16.0f);                    // row_half_mirror
+      mom_dpp<0x140>(S, M, 1.0f / 32.0f);                    // row_mirror: n = 32 per row
+      float Sa = rl(S, 0), Ma = rl(M, 0), Sb = rl(S, 32), Mb = rl(M, 32);
+      mom_add(Sa, Ma, rl(S, 16), rl(M, 16), 1.0f / 64.0f);
+      mom_add(Sb, Mb, rl(S, 48), rl(M, 48), 1.0f / 64.0f);
+      mom_add(Sa, Ma, Sb, Mb, 1.0f / 128.0f);                // n = 128 per wave
       if (lane == 0) {
-        lnp[wave][b][0] = t1;
-        lnp[wave][b][1] = t2;
+        lnp[wave][b][0] = Sa;
+        lnp[wave][b][1] = Ma;
       }
     }
 #pragma unroll
@@ -180,16 +204,18 @@ __global__ __launch_bounds__(512, BQ == 1 ? 4 : 2) void glstm_persist_kernel(con
       return;
     }
     // ---- the three matvecs of this workgroup's 16 gate rows per layer
-    float a1[BQ], aI[BQ], aH[BQ];
+    // LayerNorm fold without its cancellation: W' (y - k) - (mu - k) W' 1 for ANY k; k = the item's own feature 0
+    float a1[BQ], aI[BQ], aH[BQ], k0[BQ];
 #pragma unroll
-    for (int b = 0; b < BQ; ++b) a1[b] = aI[b] = aH[b] = 0.f;
+    for (int b = 0; b < BQ; ++b) a1[b] = aI[b] = aH[b] = 0.f, k0[b] = x1[b];
+    if (tid < BQ) kfold[tid] = x1[tid];   // x1 is rewritten before the next barrier; kfold only behind it
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
       const int k = l + 32 * m;
 #pragma unroll
       for (int b = 0; b < BQ; ++b) {
         a1[b] = fmaf(w1[m], x1[(2 * k + g) * BQ + b], a1[b]);          // h1 of this group: features 2 u + g
-        aI[b] = fmaf(w2i[m], x1[(H * g + k) * BQ + b], aI[b]);         // chunk g of the interleaved layer-1 output
+        aI[b] = fmaf(w2i[m], x1[(H * g + k) * BQ + b] - k0[b], aI[b]);   // chunk g of the interleaved layer-1 output
         aH[b] = fmaf(w2h[m], x2[k * BQ + b], aH[b]);
       }
       // one k-step at a time: hipcc otherwise keeps the LDS values of every k-step live and finishes the items one after the other
@@ -225,18 +251,21 @@ __global__ __launch_bounds__(512, BQ == 1 ? 4 : 2) void glstm_persist_kernel(con
       } else {
         float hv = 0.f;
         if (s > 0) {
-          float s1 = 0.f, s2 = 0.f;                                       // the 8 wave partials in a fixed order
+          float S[4], M[4];                                                // the 8 wave partials up a fixed tree
 #pragma unroll
-          for (int w = 0; w < 8; ++w) {
-            s1 += lnp[w][gb][0];
-            s2 += lnp[w][gb][1];
+          for (int w = 0; w < 4; ++w) {
+            S[w] = lnp[2 * w][gb][0], M[w] = lnp[2 * w][gb][1];
+            mom_add(S[w], M[w], lnp[2 * w + 1][gb][0], lnp[2 * w + 1][gb][1], 1.0f / 256.0f);
           }
-          const float muf = s1 * (1.0f / (G * H));
-          const float var = fmaxf(s2 * (1.0f / (G * H)) - muf * muf, 0.f);   // biased variance, like nn.LayerNorm
+          mom_add(S[0], M[0], S[1], M[1], 1.0f / 512.0f);
+          mom_add(S[2], M[2], S[3], M[3], 1.0f / 512.0f);
+          mom_add(S[0], M[0], S[2], M[2], 1.0f / 1024.0f);
+          const float muk = S[0] * (1.0f / (G * H)) - kfold[gb];             // mu - k, k as subtracted from the operand above
+          const float var = M[0] * (1.0f / (G * H));                         // biased variance, like nn.LayerNorm
           const float rs = __builtin_amdgcn_rsqf(var + d.eps);
           float pre[4];
 #pragma unroll
-          for (int q = 0; q < 4; ++q) pre[q] = (rs * (red[1][gui * 4 + q][gb] - muf * r2v[q]) + c2v[q]) + red[2][gui * 4 + q][gb];
+          for (int q = 0; q < 4; ++q) pre[q] = (rs * (red[1][gui * 4 + q][gb] - muk * r2v[q]) + c2v[q]) + red[2][gui * 4 + q][gb];
           const float c = sigm_p(pre[1]) * c_state + sigm_p(pre[0]) * tanh_p(pre[2]);
           hv = sigm_p(pre[3]) * tanh_p(c);
           c_state = c;

@@ -1355,14 +1355,7 @@ class GcrnPlan(PlanBase):
                        tag=TAG_PRIOR, label=p + "ih", s3g=self.split_bf16)
 
         def pack_whh():
-            whh = np.empty((2, 64, 256, 64), np.float32)
-            for g in range(2):
-                W = self.w("glstm.%s.%d.weight_hh_l0" % (layer, g))          # [2048, 512], gate order i,f,g,o
-                # slice s owns hidden units 8s..8s+7: tile row i = q*8 + u  <->  W row q*512 + 8s + u
-                rows = (np.arange(4)[:, None] * 512 + np.arange(8)[None, :]).reshape(-1)   # [32]
-                for s in range(64):
-                    whh[g, s] = P.pack_a(W[rows + 8 * s, :].T)[0]
-            return whh
+            return P.pack_lstm_whh([self.w("glstm.%s.%d.weight_hh_l0" % (layer, g)) for g in range(2)])   # [2048, 512], gate order i,f,g,o
 
         d = L.LstmDesc()
         d.gx, d.whh = self.gx.data_ptr(), self.upw(layer + ".whh", pack_whh).data_ptr()
@@ -1370,6 +1363,12 @@ class GcrnPlan(PlanBase):
         d.y_sb, d.y_st, d.y_su, d.y_sg = T * 1024, 1024, y_su, y_sg
         d.B, d.Bp, d.T, d.H, d.G = B, Bp, T, 512, 2
         self.add(d, TAG_LSTM)
+
+    def _glstm_natural(self):
+        """The natural weights the fused forms pack (packing.pack_glstm_wavefront / pack_glstm_persistent)."""
+        per = lambda key: [self.w("glstm.%s" % (key % g)) for g in range(2)]   # noqa: E731
+        return (per("lstm_list1.%d.weight_hh_l0"), per("lstm_list2.%d.weight_ih_l0"), per("lstm_list2.%d.bias_ih_l0"),
+                per("lstm_list2.%d.bias_hh_l0"), per("lstm_list2.%d.weight_hh_l0"), self.w("glstm.ln1.weight"), self.w("glstm.ln1.bias"))
 
     def _glstm_wavefront(self, proj1):
         """gcrn.py:22-35 as one operator (csrc/lstm.hip, glstm_wave_kernel): layer 1 at frame s, LayerNorm 1 + the
@@ -1386,19 +1385,7 @@ class GcrnPlan(PlanBase):
                        tag=TAG_PRIOR, label=p + "ih", s3g=self.split_bf16)      # gx1 [G][T][Bp][4H] (pdse_glstm_desc)
 
         def pack():
-            up = lambda a: self.ctx.up(a).data_ptr()   # noqa: E731
-            gam, bet = self.w("glstm.ln1.weight"), self.w("glstm.ln1.bias")
-            whh1 = np.stack([P.pack_lstm_slices(self.w("glstm.lstm_list1.%d.weight_hh_l0" % g)) for g in range(2)], 0)
-            whh2 = np.stack([P.pack_lstm_slices(self.w("glstm.lstm_list2.%d.weight_hh_l0" % g)) for g in range(2)], 0)
-            wih2, r2, c2 = [], [], []
-            for g in range(2):
-                p = "glstm.lstm_list2.%d." % g
-                Wih = self.w(p + "weight_ih_l0")                                     # [2048, 512] over chunk g of LN1's output
-                Wf = Wih * gam[512 * g:512 * g + 512][None, :]                       # LayerNorm scale folded in
-                wih2.append(P.pack_lstm_slices(Wf, P.glstm_ih2_korder(g)))
-                r2.append(Wf.sum(1))
-                c2.append(Wih @ bet[512 * g:512 * g + 512] + self.w(p + "bias_ih_l0") + self.w(p + "bias_hh_l0"))
-            return dict(whh1=up(whh1), whh2=up(whh2), wih2=up(np.stack(wih2, 0)), r2=up(np.stack(r2, 0)), c2=up(np.stack(c2, 0)))
+            return {k: self.ctx.up(v).data_ptr() for k, v in P.pack_glstm_wavefront(*self._glstm_natural()).items()}
 
         d = L.GlstmDesc()
         for k, v in self.memo("glstm.wavefront", pack).items():
@@ -1424,20 +1411,7 @@ class GcrnPlan(PlanBase):
                        tag=TAG_PRIOR, label=p + "ih", s3g=self.split_bf16)      # gx1 [G][T][Bp][4H]
 
         def pack():
-            up = lambda a: self.ctx.up(a).data_ptr()   # noqa: E731
-            gam, bet = self.w("glstm.ln1.weight"), self.w("glstm.ln1.bias")
-            rows = lambda W: np.ascontiguousarray(np.asarray(W, np.float32).reshape(4, 512, 512).transpose(1, 0, 2))   # noqa: E731  [u][q][k]
-            w1 = np.stack([rows(self.w("glstm.lstm_list1.%d.weight_hh_l0" % g)) for g in range(2)], 0)
-            w2h = np.stack([rows(self.w("glstm.lstm_list2.%d.weight_hh_l0" % g)) for g in range(2)], 0)
-            w2i, r2, c2 = [], [], []
-            for g in range(2):
-                p = "glstm.lstm_list2.%d." % g
-                Wih = self.w(p + "weight_ih_l0")                                     # [2048, 512] over chunk g of LN1's output
-                Wf = Wih * gam[512 * g:512 * g + 512][None, :]                       # LayerNorm scale folded in
-                w2i.append(rows(Wf))
-                r2.append(Wf.sum(1))
-                c2.append(Wih @ bet[512 * g:512 * g + 512] + self.w(p + "bias_ih_l0") + self.w(p + "bias_hh_l0"))
-            return dict(w1=up(w1), w2h=up(w2h), w2i=up(np.stack(w2i, 0)), r2=up(np.stack(r2, 0)), c2=up(np.stack(c2, 0)))
+            return {k: self.ctx.up(v).data_ptr() for k, v in P.pack_glstm_persistent(*self._glstm_natural()).items()}
 
         d = L.GlstmpDesc()
         for k, v in self.memo("glstm.persistent", pack).items():

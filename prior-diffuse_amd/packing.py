@@ -234,6 +234,58 @@ def glstm_ih2_korder(g, H=512):
     return order
 
 
+def pack_lstm_whh(whh):
+    """One layer's recurrent weights for the per-frame kernel (csrc/lstm.hip: lstm_step_kernel; pdse_lstm_desc.whh).
+    whh: per group W_hh [4H, H] (gate order i,f,g,o) -> float32 [G][H/8][H/2][64]: slice s owns hidden units 8s..8s+7,
+    tile row i = q*8 + u  <->  W row q*H + 8s + u, each slice in pack_a's fragment order."""
+    G = len(whh)
+    H = _np(whh[0]).shape[1]
+    out = np.empty((G, H // 8, H // 2, 64), np.float32)
+    rows = (np.arange(4)[:, None] * H + np.arange(8)[None, :]).reshape(-1)   # [32]
+    for g in range(G):
+        W = _np(whh[g])
+        for s in range(H // 8):
+            out[g, s] = pack_a(W[rows + 8 * s, :].T)[0]
+    return out
+
+
+def glstm_ln_fold(wih, bih, bhh, gamma, beta, g):
+    """LayerNorm 1 folded into group g's layer-2 input projection: W_ih LN(y) = rs (W' y) - rs mu (W' 1) + (W_ih beta + b),
+    over chunk g of the LayerNorm's output.  wih [4H, H], gamma / beta [G H] -> (W' = W_ih diag(gamma_g) [4H, H],
+    r2 = W' 1 [4H], c2 = W_ih beta_g + b_ih + b_hh [4H]), float64."""
+    wih, gamma, beta = _np(wih), _np(gamma), _np(beta)
+    H = wih.shape[1]
+    Wf = wih * gamma[H * g:H * g + H][None, :]
+    return Wf, Wf.sum(1), wih @ beta[H * g:H * g + H] + _np(bih) + _np(bhh)
+
+
+def pack_glstm_wavefront(whh1, wih2, bih2, bhh2, whh2, gamma, beta):
+    """Operands of pdse_glstm_desc (csrc/lstm.hip: glstm_wave_kernel) from the natural weights, every argument but gamma /
+    beta (LayerNorm 1, [G H]) a per-group sequence: whh1 / whh2 [4H, H] of layers 1 / 2, wih2 [4H, H] and its two biases."""
+    G = len(whh1)
+    folds = [glstm_ln_fold(wih2[g], bih2[g], bhh2[g], gamma, beta, g) for g in range(G)]
+    return dict(whh1=np.stack([pack_lstm_slices(_np(whh1[g])) for g in range(G)], 0),
+                whh2=np.stack([pack_lstm_slices(_np(whh2[g])) for g in range(G)], 0),
+                wih2=np.stack([pack_lstm_slices(folds[g][0], glstm_ih2_korder(g, folds[g][0].shape[1])) for g in range(G)], 0),
+                r2=np.stack([f[1] for f in folds], 0), c2=np.stack([f[2] for f in folds], 0))
+
+
+def pack_glstm_persistent(whh1, wih2, bih2, bhh2, whh2, gamma, beta):
+    """Operands of pdse_glstmp_desc (csrc/lstmp.hip) from the natural weights (arguments as pack_glstm_wavefront):
+    w1 / w2i / w2h [G][H units][4 gates][H], natural K order."""
+    G = len(whh1)
+
+    def rows(W):
+        W = np.asarray(W, np.float32)
+        H = W.shape[1]
+        return np.ascontiguousarray(W.reshape(4, H, H).transpose(1, 0, 2))   # [u][q][k]
+
+    folds = [glstm_ln_fold(wih2[g], bih2[g], bhh2[g], gamma, beta, g) for g in range(G)]
+    return dict(w1=np.stack([rows(_np(whh1[g])) for g in range(G)], 0), w2h=np.stack([rows(_np(whh2[g])) for g in range(G)], 0),
+                w2i=np.stack([rows(f[0]) for f in folds], 0),
+                r2=np.stack([f[1] for f in folds], 0), c2=np.stack([f[2] for f in folds], 0))
+
+
 # ------------------------------------------------------------------------------------------
 # fused TCM residual block (csrc/tcm.hip, include/pdse.h: pdse_tcm_desc)
 # ------------------------------------------------------------------------------------------

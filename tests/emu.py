@@ -401,13 +401,63 @@ def _unpack_lstm_slices(w, H, K):
     w = w.reshape(H // 8, K // 8, 2, 32, 4)                  # [s, q, h, col, i]
     W = np.zeros((4 * H, K), np.float32)
     col = np.arange(32)
-    for s_ in range(H // 8):
-        rows = (col // 8) * H + 8 * s_ + (col % 8)
-        for q in range(K // 8):
-            for h in range(2):
-                for i in range(4):
-                    W[rows, 2 * (4 * q + i) + h] = w[s_, q, h, :, i]
+    rows = (col // 8)[None, :] * H + 8 * np.arange(H // 8)[:, None] + (col % 8)[None, :]          # [s, col]
+    q, h, i = np.arange(K // 8)[:, None, None], np.arange(2)[None, :, None], np.arange(4)[None, None, :]
+    k = 2 * (4 * q + i) + h                                                                         # [q, h, i]
+    W[rows[:, None, None, :, None], k[None, :, :, None, :]] = w
     return W
+
+
+def _wave_moments(h1, eps):
+    """LayerNorm 1's moments as glstm_wave_kernel forms them.  h1 [G, B, H] float32 -> (mu float64, rs float32) [B].
+    Stage A: per slice of 8 units the fp32 sum and the fp32 sum of squared deviations from the slice's own mean; stage B: the
+    128 partials in 16 parts of 8 (fp32, Chan's combine about the part's mean), the 16 parts about the mean (the mean in double)."""
+    G, B, H = h1.shape
+    f = np.float32
+    v = h1.reshape(G, B, H // 8, 8).transpose(0, 2, 1, 3).reshape(G * (H // 8), B, 8)          # [128 partials][B][8]
+    s1 = np.zeros(v.shape[:2], f)
+    for k in range(8):
+        s1 = s1 + v[..., k]
+    m = s1 * f(0.125)
+    m2 = np.zeros_like(s1)
+    for k in range(8):
+        d = v[..., k] - m
+        m2 = m2 + d * d
+    s1, m2 = s1.reshape(16, 8, B), m2.reshape(16, 8, B)
+    S = np.zeros((16, B), f)
+    for e in range(8):
+        S = S + s1[:, e]
+    mp = S * f(1.0 / 64)
+    M = np.zeros((16, B), f)
+    for e in range(8):
+        d = s1[:, e] * f(0.125) - mp
+        M = M + (m2[:, e] + f(8) * (d * d))
+    mean = S.astype(np.float64).sum(0) / (G * H)
+    var = np.zeros(B, f)
+    for p_ in range(16):
+        d = S[p_] * f(1.0 / 64) - mean.astype(f)
+        var = var + (M[p_] + f(64) * (d * d))
+    var = var.astype(np.float64) / (G * H)
+    return mean, (1.0 / np.sqrt(var + eps)).astype(f)
+
+
+def _tree_moments(x, eps):
+    """LayerNorm 1's moments as glstm_persist_kernel forms them: x [B, 2H] float32 (feature 2 u + g) -> (mu, rs) float32 [B].
+    (sum, sum of squared deviations) pairs combined up one fixed binary tree of neighbours - the thread's two features, the
+    DPP row tree, the four rows, the eight waves - each level by M2 = M2a + M2b + (Sa - Sb)^2 / (2 n), all fp32."""
+    f = np.float32
+    a, c = x[:, 0::2], x[:, 1::2]
+    S, d = a + c, a - c
+    M = f(0.5) * (d * d)
+    n = 2
+    while S.shape[1] > 1:
+        d = S[:, 0::2] - S[:, 1::2]
+        M = (M[:, 0::2] + M[:, 1::2]) + (d * d) * f(1.0 / (2 * n))
+        S = S[:, 0::2] + S[:, 1::2]
+        n *= 2
+    mu = S[:, 0] * f(1.0 / x.shape[1])
+    var = M[:, 0] * f(1.0 / x.shape[1])
+    return mu, (f(1) / np.sqrt(var + f(eps))).astype(f)
 
 
 def run_glstm(d, mem):
@@ -433,9 +483,7 @@ def run_glstm(d, mem):
     for t in range(T):
         for g in range(G):
             h1[g], c1[g] = cell(gx1[g, t, :B, :] + h1[g] @ W1[g].T, c1[g])
-        allh = np.stack([h1[0], h1[1]], -1).reshape(B, -1).astype(np.float64)       # feature 2u + g'
-        mu, var = allh.mean(1), allh.var(1)
-        rs = 1.0 / np.sqrt(var + d.eps)
+        mu, rs = _wave_moments(h1, d.eps)
         for g in range(G):
             xk = np.zeros((B, H), np.float32)                                       # B operand in stage B's K order
             for gq in range(H // 8):
@@ -443,7 +491,10 @@ def run_glstm(d, mem):
                 for i in range(4):
                     for hh in range(2):
                         xk[:, 2 * (4 * gq + i) + hh] = h1[gs][:, 8 * kq + 2 * i + hh]
-            gx2 = rs[:, None] * (xk @ Wi[g].T - mu[:, None] * r2[g][None, :]) + c2[g][None, :]
+            # the fold about k = the item's own first feature: W' (y - k) - (mu - k) W' 1 (csrc/lstm.hip, stage B)
+            k0 = h1[0][:, 0]
+            muk = (mu - k0.astype(np.float64)).astype(np.float32)
+            gx2 = rs[:, None] * ((xk - k0[:, None]) @ Wi[g].T - muk[:, None] * r2[g][None, :]) + c2[g][None, :]
             h2[g], c2s[g] = cell(gx2.astype(np.float32) + h2[g] @ W2[g].T, c2s[g])
             idx = (yoff + np.arange(B)[:, None] * d.y_sb + t * d.y_st + np.arange(H)[None, :] * d.y_su + g * d.y_sg)
             yflat[idx] = h2[g]
@@ -473,11 +524,11 @@ def run_glstmp(d, mem):
         for g in range(G):
             h1[g], c1[g] = cell(gx1[g, t, :B, :] + h1[g] @ W1[g].T, c1[g])
         allh = np.stack([h1[0], h1[1]], -1).reshape(B, -1)                           # feature 2u + g'
-        mu, var = allh.astype(np.float64).mean(1), allh.astype(np.float64).var(1)
-        rs = 1.0 / np.sqrt(var + d.eps)
+        mu, rs = _tree_moments(allh, d.eps)
         for g in range(G):
-            xk = allh[:, H * g:H * g + H]
-            gx2 = rs[:, None] * (xk @ Wi[g].T - mu[:, None] * r2[g][None, :]) + c2[g][None, :]
+            k0 = allh[:, 0]                                                          # the fold about the item's own feature 0
+            xk = allh[:, H * g:H * g + H] - k0[:, None]
+            gx2 = rs[:, None] * (xk @ Wi[g].T - (mu - k0)[:, None] * r2[g][None, :]) + c2[g][None, :]
             h2[g], c2s[g] = cell(gx2.astype(np.float32) + h2[g] @ W2[g].T, c2s[g])
             idx = (yoff + np.arange(B)[:, None] * d.y_sb + t * d.y_st + np.arange(H)[None, :] * d.y_su + g * d.y_sg)
             yflat[idx] = h2[g]
