@@ -9,6 +9,11 @@
 Every tensor lives in HBM for the lifetime of the plan (weights packed once, workspaces
 allocated once per (B, T)); a plan run is a pure sequence of kernel launches with no
 allocation and no host synchronisation, so it can be captured into a hipGraph.
+
+The builders here record descriptors: strides, offsets and buffers of one (B, T).  What a descriptor's weight operands hold -
+BatchNorm folds, composed convolutions, f16x2 exponents, fragment layouts - is derived in ``packing.py`` by pure functions from
+natural weights to ``{descriptor field: array | scalar}``; ``PlanBase.fields`` uploads such a dict once per weight bank and
+``PlanBase.apply`` sets it on a descriptor.
 """
 import ctypes as C
 
@@ -124,9 +129,30 @@ class PlanBase:
             raise RuntimeError("weight bank: builder call sequence diverged at %r (bank holds %r)" % (label, hit[0]))
         return hit[1]
 
-    def upw(self, label, fn, dtype=np.float32):
-        """Device tensor of a weight-derived array (``fn`` -> numpy), memoised in the bank."""
-        return self.memo(label, lambda: self.ctx.up(fn(), dtype))
+    def _up(self, a):
+        """Upload one weight-derived array.  The one dtype convention of everything ``packing`` returns: uint16 arrays are
+        operand planes (bf16 / fp16 bit patterns) and travel as int16 views, int32 stays int32, every other array is fp32."""
+        if a.dtype == np.uint16:
+            return self.ctx.up(np.ascontiguousarray(a).view(np.int16), np.int16)
+        return self.ctx.up(a, np.int32 if a.dtype == np.int32 else np.float32)
+
+    def upw(self, label, fn):
+        """Device tensor of a weight-derived array (``fn`` -> numpy, uploaded as ``_up`` states), memoised in the bank."""
+        return self.memo(label, lambda: self._up(fn()))
+
+    def fields(self, label, fn):
+        """``fn`` -> {descriptor field: array | scalar | tuple} (the pure functions of packing.py), memoised in the bank with every
+        array uploaded (``_up``) and replaced by its device pointer; scalars and tuples pass through."""
+        return self.memo(label, lambda: {k: self._up(v).data_ptr() if isinstance(v, np.ndarray) else v for k, v in fn().items()})
+
+    @staticmethod
+    def apply(d, fields):
+        """Set a ``fields`` dict on a descriptor; a key (name, i) is element i of the array field ``name`` (nx_bias)."""
+        for k, v in fields.items():
+            if isinstance(k, tuple):
+                getattr(d, k[0])[k[1]] = v
+            else:
+                setattr(d, k, v)
 
     def add(self, desc, tag=TAG_NONE):
         self.descs.append((desc, tag))
@@ -207,117 +233,12 @@ class PlanBase:
     def src(self, t, C_, sb, sc, st, sf, off=0, act=L.ACT_NONE, blk=0):
         return L.Src(Ctx.ptr(t, off), sb, sc, st, sf, C_, act, blk, 0)
 
-    def _gconv_weights_s3(self, w, ntaps, cin=32):
-        """korder 2 (csrc/gconv3.hip): exact three-way bf16 splits of a BIGLU block's weights, MFMA bf16 fragment order.
-        cin 4: the composed encoder stage 1 (K = 10 taps x 4 channels = 40, zero-padded to three 16-deep blocks)."""
-        ctx = self.ctx
-        up = lambda a: ctx.up(a).data_ptr()   # noqa: E731
-        up16 = lambda a: ctx.up(np.ascontiguousarray(a).view(np.int16), np.int16).data_ptr()   # noqa: E731
-        f = {"korder": 2, "ksteps": ntaps * cin // 2}
-        if cin == 4:
-            pad = lambda wk: np.concatenate([np.asarray(wk, np.float64), np.zeros((8, 32))], 0)   # noqa: E731  [48, 32]
-            f["w0"], f["w1"] = up16(P.pack_s3_gather(pad(w["wk0"]), 3, 16)), up16(P.pack_s3_gather(pad(w["wk1"]), 3, 16))
-        else:
-            f["w0"], f["w1"] = up16(P.pack_s3_gather(w["wk0"], ntaps)), up16(P.pack_s3_gather(w["wk1"], ntaps))
-        if w.get("wk2") is not None:
-            f["w2"], f["w3"] = up16(P.pack_s3_gather(w["wk2"], w["ntaps1"])), up16(P.pack_s3_gather(w["wk3"], w["ntaps1"]))
-            f["ksteps1"] = w["ntaps1"] * 16
-        for k in ("bias0", "bias1"):                           # time-conditioned launches get device biases instead
-            if w.get(k) is not None:
-                f[k] = up(w[k])
-        if w.get("post") is not None:
-            f["post_scale"], f["post_shift"] = up(w["post"][0]), up(w["post"][1])
-        chain = w["chain"]
-        f["C2"] = chain["C2"]
-        f["wlc"], f["wrc"] = up16(P.pack_s3_chain(chain["wlc"])), up16(P.pack_s3_chain(chain["wrc"]))
-        f["blc"], f["brc"], f["bc2"] = up(chain["blc"]), up(chain["brc"]), up(chain["bc2"])
-        f["wc2"] = up(np.asarray(chain["wc2"], np.float64).reshape(32)) if chain["C2"] == 1 else up16(P.pack_s3_chain(chain["wc2"]))
-        nx = w.get("nx")
-        if nx:
-            for i, tl in enumerate(nx):
-                if tl.get("bias") is not None:
-                    f[("nx_bias", i)] = up(tl["bias"])
-            f["nx_w"] = up16(np.stack([P.pack_s3_chain(tl["w"])[0] for tl in nx], 0))
-        return f
-
-    def _gconv_weights_s3g(self, w, ntaps, c0, c1):
-        """korder 3 (csrc/gconv4.hip): LINEAR / GLU convolutions as split-bf16 GEMMs, weights streamed through LDS."""
-        ctx = self.ctx
-        up = lambda a: ctx.up(a).data_ptr()   # noqa: E731
-        up16 = lambda a: ctx.up(np.ascontiguousarray(a).view(np.int16), np.int16).data_ptr()   # noqa: E731
-        npl = self.gemm_planes
-        qe = P.f16_wexp(*[w[k_] for k_ in ("wk0", "wk1") if w.get(k_) is not None]) if npl == 2 else 0     # f16x2: one exponent per launch
-        f = {"korder": {3: 3, 1: 4, 2: 5}[npl], "ksteps": ntaps * (c0 + c1) // 2, "w0": up16(P.pack_s3_gemm(w["wk0"], ntaps, c0, c1, npl, qe)),
-             "wexp": qe}
-        if w.get("wk1") is not None:
-            f["w1"] = up16(P.pack_s3_gemm(w["wk1"], ntaps, c0, c1, npl, qe))
-        for k in ("bias0", "bias1"):
-            if w.get(k) is not None:
-                f[k] = up(w[k])
-        if w.get("post") is not None:
-            f["post_scale"], f["post_shift"] = up(w["post"][0]), up(w["post"][1])
-        return f
-
-    def _gconv_weights(self, w, ntaps, c0, c1, epi, cin1, pipelined_ok):
-        """Pack and upload the weight side of one gather-GEMM launch; returns {descriptor field: value}.
-        w: dict with wk0 [K, Cout] (k-major float64), optional wk1, wk2/wk3 (odd phase), bias0/bias1, post (scale, shift),
-        xf, chain, nx (list of dict(w [32,64], bias or None))."""
-        ctx = self.ctx
-        up = lambda a: ctx.up(a).data_ptr()   # noqa: E731
-        f = {}
-        xf = w.get("xf")
-        xf_mode = 0
-        if xf is not None:
-            xf_mode = f["xf_mode"] = xf["mode"]
-            f["xf_scale0"], f["xf_shift0"], f["xf_slope0"] = up(xf["scale0"]), up(xf["shift0"]), float(xf["slope0"])
-            if xf["mode"] == 2:
-                f["xf_scale1"], f["xf_shift1"], f["xf_slope1"] = up(xf["scale1"]), up(xf["shift1"]), float(xf["slope1"])
-        wk0 = np.asarray(w["wk0"])
-        wk1 = w.get("wk1")
-        key = (epi, ntaps, c1 > 0, xf_mode)
-        if P.v2_supported(*key, cin1) and pipelined_ok:
-            rows = P.korder1_rows(ntaps, c0, c1, P.V2_CP[key])                 # pipelined kernel order
-            f["w0"], f["ksteps"], f["korder"] = up(P.pack_a4(wk0, rows)), len(rows) // 2, 1
-            if wk1 is not None:
-                f["w1"] = up(P.pack_a4(wk1, rows))
-            if w.get("wk2") is not None:
-                rows1 = P.korder1_rows(w["ntaps1"], c0, 0, P.V2_CP[key])
-                f["w2"], f["w3"] = up(P.pack_a4(w["wk2"], rows1)), up(P.pack_a4(w["wk3"], rows1))
-                f["ksteps1"] = len(rows1) // 2
-        else:
-            w0 = P.pack_a(wk0)
-            f["w0"], f["ksteps"] = up(w0), w0.shape[1]
-            if wk1 is not None:
-                f["w1"] = up(P.pack_a(wk1))
-        for k in ("bias0", "bias1"):
-            if w.get(k) is not None:
-                f[k] = up(w[k])
-        if w.get("post") is not None:
-            f["post_scale"], f["post_shift"] = up(w["post"][0]), up(w["post"][1])
-        chain = w.get("chain")
-        if chain is not None:
-            f["C2"] = chain["C2"]
-            f["wlc"], f["wrc"] = up(P.pack_chain(chain["wlc"])), up(P.pack_chain(chain["wrc"]))
-            f["blc"], f["brc"] = up(chain["blc"]), up(chain["brc"])
-            f["wc2"] = up(np.asarray(chain["wc2"], np.float64).reshape(32)) if chain["C2"] == 1 else up(P.pack_chain(chain["wc2"]))
-            f["bc2"] = up(chain["bc2"])
-        nx = w.get("nx")
-        if nx:
-            packs = []
-            for i, tl in enumerate(nx):
-                wn = np.asarray(tl["w"], np.float64)                       # [32 out, 64 in]
-                packs.append(np.concatenate([P.pack_chain(wn[:, :32]), P.pack_chain(wn[:, 32:])], 0))   # [2,16,64]
-                if tl.get("bias") is not None:
-                    f[("nx_bias", i)] = up(tl["bias"])
-            f["nx_w"] = up(np.stack(packs, 0))
-        return f
-
     def gconv(self, *, in0, in1=None, Tin, Fin, taps, sf_in, W, Cout, bias0=None, bias0_sb=0,
               bias1=None, bias1_sb=0, epi=L.EPI_LINEAR, act=L.ACT_NONE, act_slope=0.0,
               padrow=None, padrow_sb=0, padrow_off=0, cin1=False, resid=None, out,
               out_strides, out_off=0, out_cr=1, B, Tout, Fout, tag=TAG_NONE, bias0_off=0, phase1=None, nx=None,
               bias1_off=0, bias_t0=None, label="gconv", s3=False, s3g=False, has_xf=False):
-        """W: callable -> dict of the launch's weight-derived operands (see ``_gconv_weights``); evaluated only when the
+        """W: callable -> dict of the launch's natural weight operands (see ``packing.gconv_fields``); evaluated only when the
         weight bank does not hold this launch yet.  bias0 / bias1 / padrow / bias_t0 here are per-plan DEVICE tensors
         (time-conditioned biases); constant biases travel inside W.
         phase1 (dual-phase transposed conv, BIGLU): dict(mask, Fout1) - its weights wk2 / wk3 / ntaps1 come from W.
@@ -335,7 +256,7 @@ class PlanBase:
         tp = ctx.bank.items.get(tkey)
         if tp is None:
             ctx._banking += 1
-            tp = ctx.bank.items[tkey] = ctx.up(P.taps_array(ttaps), np.int32)
+            tp = ctx.bank.items[tkey] = self._up(P.taps_array(ttaps))
             ctx._banking -= 1
         d.taps, d.ntaps, d.sf_in = tp.data_ptr(), len(ttaps), sf_in
         for i, (dt_, df_) in enumerate(ttaps[:12]):             # by-value copy for the unrolled-tap kernels
@@ -351,16 +272,12 @@ class PlanBase:
                and c0 > 0 and c0 % 16 == 0 and c1 % 16 == 0 and len(ttaps) <= 12)
         site = "%s:%d:%d:%d:%d:%d:%d:%d:%d" % (label, epi, len(ttaps), c0, c1, Cout, pipelined_ok, s3, s3g)
         if s3g:
-            f = self.memo(site, lambda: self._gconv_weights_s3g(W(), len(ttaps), c0, c1))
+            pack = lambda: P.gconv_gemm_fields(W(), len(ttaps), c0, c1, self.gemm_planes)   # noqa: E731
         elif s3:
-            f = self.memo(site, lambda: self._gconv_weights_s3(W(), len(ttaps), c0 + c1))
+            pack = lambda: P.gconv_s3_fields(W(), len(ttaps), c0 + c1)   # noqa: E731
         else:
-            f = self.memo(site, lambda: self._gconv_weights(W(), len(ttaps), c0, c1, epi, cin1, pipelined_ok))
-        for k, v in f.items():
-            if isinstance(k, tuple):
-                d.nx_bias[k[1]] = v
-            else:
-                setattr(d, k, v)
+            pack = lambda: P.gconv_fields(W(), len(ttaps), c0, c1, epi, cin1, pipelined_ok)   # noqa: E731
+        self.apply(d, self.fields(site, pack))
         d.Cout = Cout
         if bias0 is not None:
             d.bias0 = Ctx.ptr(bias0, bias0_off)
@@ -628,13 +545,9 @@ class EpsNetPlan(PlanBase):
             bias = {}
 
         def W():
-            W1 = self.w(p + ".conv1.weight")[:, :, 0, 0]                       # [32, Cin]
-            if self.with_pre:
-                W1 = W1 @ self.w("preprocess.conv.weight")[:, :, 0, 0]          # [32, 4] over (x, x_init)
-            comp = {br: np.einsum("ockf,ci->oikf", self.w("%s.%s.weight" % (p, br)).astype(np.float64), W1.astype(np.float64))
-                    for br in ("l", "r")}
-            w = dict(wk0=P.conv_kmat(comp["l"], kk), wk1=P.conv_kmat(comp["r"], kk), post=P.bn_fold(self.sd, "en.en1.0"),
-                     chain=self._chain(p, 64, False), nx=self._nx_weights(nx))
+            wk0, wk1 = P.compose_stage1(self.sd, p, kk, self.with_pre)
+            w = dict(wk0=wk0, wk1=wk1, post=P.bn_fold(self.sd, "en.en1.0"), chain=P.biglu_chain(self.sd, p, 64, False),
+                     nx=self._nx_weights(nx))
             if not self.time_cond:
                 b1 = self.w(p + ".conv1.bias")                                  # pad frame = conv1(0) = b1 as well
                 for key, br in (("bias0", "l"), ("bias1", "r")):
@@ -649,13 +562,6 @@ class EpsNetPlan(PlanBase):
 
     def _slope(self, key):
         return self.memo("slope:" + key, lambda: float(self.w(key)[0]))
-
-    def _chain(self, p, C2, transposed):
-        """BIGLU chain operands of a BiConvGLU (Conv2d weights [out, in]) / BiConvTransGLU (ConvTranspose2d [in, out])."""
-        tr = (lambda m: m.T) if transposed else (lambda m: m)
-        return dict(C2=C2, wlc=tr(self.w(p + ".l_conv.weight")[:, :, 0, 0]), blc=self.w(p + ".l_conv.bias"),
-                    wrc=tr(self.w(p + ".r_conv.weight")[:, :, 0, 0]), brc=self.w(p + ".r_conv.bias"),
-                    wc2=tr(self.w(p + ".conv2.weight")[:, :, 0, 0]), bc2=self.w(p + ".conv2.bias"))
 
     @staticmethod
     def _nx_weights(nx):
@@ -714,7 +620,7 @@ class EpsNetPlan(PlanBase):
         def W():
             return dict(wk0=P.conv_kmat(self.sd[p + ".l.weight"], kk), wk1=P.conv_kmat(self.sd[p + ".r.weight"], kk),
                         bias0=self.w(p + ".l.bias"), bias1=self.w(p + ".r.bias"), post=P.bn_fold(self.sd, "en.en%d.0" % k),
-                        chain=self._chain(p, 64, False), nx=self._nx_weights(nx))
+                        chain=P.biglu_chain(self.sd, p, 64, False), nx=self._nx_weights(nx))
 
         self.gconv(in0=self.src(H, 32, *nchw(32, HT, Fin)), Tin=HT, Fin=Fin, taps=taps, sf_in=2, W=W,
                    Cout=32, epi=L.EPI_BIGLU, act=L.ACT_PRELU, act_slope=self._slope("en.en%d.1.weight" % k),
@@ -758,7 +664,7 @@ class EpsNetPlan(PlanBase):
             def W():
                 w = dict(wk0=P.convT_kmat(self.sd[p + ".l.weight"], kk), wk1=P.convT_kmat(self.sd[p + ".r.weight"], kk),
                          bias0=self.w(p + ".l.bias"), bias1=self.w(p + ".r.bias"),
-                         post=P.bn_fold(self.sd, bn_prefix) if bn_prefix else None, chain=self._chain(p, C2, True),
+                         post=P.bn_fold(self.sd, bn_prefix) if bn_prefix else None, chain=P.biglu_chain(self.sd, p, C2, True),
                          nx=self._nx_weights(nx_))
                 if with_odd:
                     w.update(wk2=P.convT_kmat(self.sd[p + ".l.weight"], kk1), wk3=P.convT_kmat(self.sd[p + ".r.weight"], kk1),
@@ -786,12 +692,6 @@ class EpsNetPlan(PlanBase):
                    W=lambda: dict(wk0=self.w(p + ".conv1.weight")[:, :, 0].T, bias0=self.w(p + ".conv1.bias")), Cout=64,
                    out=hout, out_strides=(64 * T, T, 0, 0, 1), B=B, Tout=1, Fout=T, tag=TAG_TCM, label=p + ".conv1")
 
-    def _tcm_branch_mats(self, p):
-        def km(br):
-            w = self.w(p + "." + br + ".2.weight")                          # [64, 64, 5]
-            return np.concatenate([w[:, :, k].T for k in range(5)], axis=0)
-        return km("mainbranch"), km("maskbranch")
-
     def _residual(self, p, dil, xin, xout):
         """TCM residual block (model/diff3.py:215-257) over [B,256,T] (T on the lanes): three launches."""
         B, T = self.B, self.T
@@ -802,7 +702,7 @@ class EpsNetPlan(PlanBase):
         taps = [(0, (k - 2) * dil) for k in range(5)]
 
         def Wbr():
-            kmain, kmask = self._tcm_branch_mats(p)
+            kmain, kmask = P.tcm_branch_kmats(self.sd, p)
             sm, hm = P.bn_fold(self.sd, p + ".mainbranch.1")
             sk, hk = P.bn_fold(self.sd, p + ".maskbranch.1")
             xf = dict(mode=2, scale0=sm, shift0=hm, slope0=self.w(p + ".mainbranch.0.weight")[0],
@@ -822,28 +722,9 @@ class EpsNetPlan(PlanBase):
 
     def _residual_fused(self, p, dil, xin, xout, hin, hout, p_next):
         """The same block as ONE launch (csrc/tcm.hip): dilated branches + gate + conv2 + residual, and the next
-        block's conv1 (``p_next``; None for the last block) chained onto the fresh x in registers."""
-        def make():
-            up = lambda a: self.ctx.up(a).data_ptr()   # noqa: E731
-            kmain, kmask = self._tcm_branch_mats(p)
-            sm, hm = P.bn_fold(self.sd, p + ".mainbranch.1")
-            sk, hk = P.bn_fold(self.sd, p + ".maskbranch.1")
-            s2, h2 = P.bn_fold(self.sd, p + ".conv2.1")
-            f = dict(wbr=up(P.pack_tcm_branch(kmain, kmask)), bmain=up(self.w(p + ".mainbranch.2.bias")),
-                     bmask=up(self.w(p + ".maskbranch.2.bias")),
-                     xf=up(np.stack([np.stack([sm, hm], 1), np.stack([sk, hk], 1)], 0).astype(np.float32)),
-                     wc2=up(P.pack_tcm_conv2(self.w(p + ".conv2.2.weight")[:, :, 0].T)), bc2=up(self.w(p + ".conv2.2.bias")),
-                     xf2=up(np.stack([s2, h2], 1).astype(np.float32)),
-                     slope_main=float(self.w(p + ".mainbranch.0.weight")[0]),
-                     slope_mask=float(self.w(p + ".maskbranch.0.weight")[0]), slope2=float(self.w(p + ".conv2.0.weight")[0]))
-            if p_next is not None:
-                f["wn1"] = up(P.pack_tcm_next(self.w(p_next + ".conv1.weight")[:, :, 0]))
-                f["bn1"] = up(self.w(p_next + ".conv1.bias"))
-            return f
-
+        block's conv1 (``p_next``; None for the last block) chained onto the fresh x in registers (packing.tcm_fields)."""
         d = L.TcmDesc()
-        for k, v in self.memo(p + ".fused", make).items():
-            setattr(d, k, v)
+        self.apply(d, self.fields(p + ".fused", lambda: P.tcm_fields(self.sd, p, p_next)))
         d.x, d.h, d.x_out = xin.data_ptr(), hin.data_ptr(), xout.data_ptr()
         if p_next is not None:
             d.h_out = hout.data_ptr()
@@ -853,53 +734,23 @@ class EpsNetPlan(PlanBase):
 
     def _residual_split(self, p, dil, xin, xout, hin, hout, p_next, mode=0):
         """``_residual_fused`` in split-bf16 arithmetic (csrc/tcm2.hip): the bottleneck tensor travels as the split
-        planes of both branches' BN(PReLU(.)), so a block also carries the NEXT block's input transforms.
-        mode 1: only ``p_next``'s conv1 on ``xin`` (the first block of the stack)."""
-        def make():
-            up16 = lambda a: self.ctx.up(np.asarray(a).view(np.int16), np.int16).data_ptr()   # noqa: E731
-            par = np.zeros(832, np.float32)
-            f = dict(slope2=0.0, slope_main_next=0.0, slope_mask_next=0.0)
-            npl = self.tcm_planes
-            qof = (lambda *m: P.f16_wexp(*m)) if npl == 2 else (lambda *m: 0)     # f16x2: one power-of-two exponent per weight group
-            qA = q2 = qN = 0
-            if mode == 0:
-                kmain, kmask = self._tcm_branch_mats(p)
-                s2, h2 = P.bn_fold(self.sd, p + ".conv2.1")
-                par[:256] = np.stack([self.w(p + ".mainbranch.2.bias"), self.w(p + ".maskbranch.2.bias"), s2, h2], 1).reshape(-1)
-                par[256:512] = self.w(p + ".conv2.2.bias")
-                k2 = self.w(p + ".conv2.2.weight")[:, :, 0].T
-                qA, q2 = qof(kmain, kmask), qof(k2)
-                f.update(wbr=up16(P.pack_tcm2_branch(kmain, kmask, npl, qA)), wc2=up16(P.pack_tcm2_conv2(k2, npl, q2)),
-                         slope2=float(self.w(p + ".conv2.0.weight")[0]))
-            if p_next is not None:
-                sm, hm = P.bn_fold(self.sd, p_next + ".mainbranch.1")
-                sk, hk = P.bn_fold(self.sd, p_next + ".maskbranch.1")
-                par[512:576] = self.w(p_next + ".conv1.bias")
-                par[576:] = np.stack([sm, hm, sk, hk], 1).reshape(-1)
-                wn1 = self.w(p_next + ".conv1.weight")[:, :, 0]
-                qN = qof(wn1)
-                f.update(wn1=up16(P.pack_bglu_chain(wn1, npl, qN)),
-                         slope_main_next=float(self.w(p_next + ".mainbranch.0.weight")[0]),
-                         slope_mask_next=float(self.w(p_next + ".maskbranch.0.weight")[0]))
-            f["par"] = self.ctx.up(par).data_ptr()
-            f["qexp"] = (qA, q2, qN)
-            return f
-
+        planes of both branches' BN(PReLU(.)), so a block also carries the NEXT block's input transforms
+        (packing.tcm2_fields).  mode 1: only ``p_next``'s conv1 on ``xin`` (the first block of the stack)."""
+        npl = self.tcm_planes
         d = L.Tcm2Desc()
-        for k, v in self.memo("%s.split%d.np%d" % (p if mode == 0 else p_next, mode, self.tcm_planes), make).items():
-            setattr(d, k, v)
+        self.apply(d, self.fields("%s.split%d.np%d" % (p if mode == 0 else p_next, mode, npl),
+                                  lambda: P.tcm2_fields(self.sd, p, p_next, npl, mode)))
         d.x = xin.data_ptr()
         if mode == 0:
             d.x_out, d.hs = xout.data_ptr(), hin.data_ptr()
         if p_next is not None:
             d.hs_out = hout.data_ptr()
-        d.dil, d.B, d.T, d.mode, d.np = dil, self.B, self.T, mode, self.tcm_planes
+        d.dil, d.B, d.T, d.mode, d.np = dil, self.B, self.T, mode, npl
         d.frames = Ctx.ptr(self.frames)
         if mode == 0 and self._tcm_stack is not None:
             self._tcm_stack.append(d)          # collected: one pdse_tcm2s_desc for the whole stack (build_step)
         else:
             self.add(d, TAG_TCM)
-
 
     # ---- the plane path (csrc/bglu.hip) ------------------------------------------------------------------------
     def _plane_stage(self, kind):
@@ -907,50 +758,13 @@ class EpsNetPlan(PlanBase):
         halves in the layout of the kernel that reads them (csrc/bglu.hip: groups of four channels)."""
         return self.plane_h is True
 
-    def _bglu_weights(self, p, transposed, C2, bn_prefix, gather, nx_w):
-        """Weight side of one pdse_bglu_desc: gather = dict(w0, w1[, w2, w3]) of k-major matrices (ntaps x 32 rows; the
-        composed stage 1: 40 rows); folds -log2 e into l_conv / r_conv and the BatchNorm behind the block into conv2
-        (float64), packs the gather weights and the chained tiles.  Plane count 2 (f16x2): every weight group is scaled by its
-        own power of two before the split (packing.f16_wexp; pdse_bglu_desc.qexp)."""
-        npl = self.planes
-        ctx = self.ctx
-        up = lambda a_: ctx.up(a_).data_ptr()   # noqa: E731
-        up16 = lambda a_: ctx.up(np.ascontiguousarray(a_).view(np.int16), np.int16).data_ptr()   # noqa: E731
-        qof = (lambda *m: P.f16_wexp(*m)) if npl == 2 else (lambda *m: 0)
-        ch = self._chain(p, C2, transposed)
-        qG = qof(*gather.values())
-        f = {k: up16(P.pack_bglu_in4(v, npl, qG) if v.shape[0] == 40 else P.pack_bglu_gather(v, v.shape[0] // 32, npl, qG))
-             for k, v in gather.items()}
-        wlc, wrc = (-P.LOG2E * np.asarray(ch[k_], np.float64) for k_ in ("wlc", "wrc"))
-        qLC = qof(wlc, wrc)
-        f["wlc"] = up16(P.pack_bglu_chain(wlc, npl, qLC))
-        f["wrc"] = up16(P.pack_bglu_chain(wrc, npl, qLC))
-        f["blc"] = up(-P.LOG2E * np.asarray(ch["blc"], np.float64))
-        f["brc"] = up(-P.LOG2E * np.asarray(ch["brc"], np.float64))
-        wc2, bc2 = np.asarray(ch["wc2"], np.float64), np.asarray(ch["bc2"], np.float64)
-        if bn_prefix is not None:                       # y = (Wc2 g + bc2) s + t = (diag(s) Wc2) g + (s bc2 + t)
-            sc, sh = (np.asarray(v, np.float64) for v in P.bn_fold(self.sd, bn_prefix))
-            wc2, bc2 = wc2 * sc[:, None], bc2 * sc + sh
-        qC2 = qNX = 0
-        if C2 == 1:
-            f["wc2v"], f["bc2"] = up(wc2.reshape(32)), up(np.concatenate([bc2.reshape(1), np.zeros(63)]))
-        else:
-            qC2 = qof(wc2)
-            f["wc2"], f["bc2"] = up16(P.pack_bglu_chain(wc2, npl, qC2)), up(bc2)
-        if nx_w:
-            qNX = qof(*nx_w)
-            f["nx_w"] = up16(np.stack([P.pack_bglu_chain(w, npl, qNX)[0] for w in nx_w], 0))
-        f["qexp"] = (qG, qLC, qC2, qNX)
-        return f
-
     def _bglu(self, label, make, *, hp=None, F_in=None, x0=None, x1=None, taps, sf_in, Fout, p1mask=0, Fout1=0, slope, C2,
               bias, out=None, out_strides=None, out_off=0, nx_hp=None, nx_F=None, nx_row0=False, nx_add=None,
               nx_out=(), nx_bias=(), hp_par=False, nx_par=False, skip_F=0):
-        """Record one pdse_bglu_desc.  make(): -> dict of packed device pointers (memoised in the weight bank)."""
+        """Record one pdse_bglu_desc.  make(): -> its weight side (packing.bglu_fields; uploaded once per weight bank)."""
         B, T, npl = self.B, self.T, self.planes
         d = L.BgluDesc()
-        for k, v in self.memo("bglu:%s:%d" % (label, npl), make).items():
-            setattr(d, k, v)
+        self.apply(d, self.fields("bglu:%s:%d" % (label, npl), make))
         if hp is not None:
             shp = P.hp_shape(B + 1, T, F_in, npl)
             d.hp, d.hp_sb, d.hp_Tp, d.hp_Fp, d.hp_t0, d.hp_f0 = hp.data_ptr(), int(np.prod(shp[1:])), shp[1], shp[4], P.HP_T0, P.HP_F0
@@ -1022,19 +836,14 @@ class EpsNetPlan(PlanBase):
 
             if k == 1:
                 def make(p=p, kk=kk, nx_weights=nx_weights):
-                    W1 = self.w(p + ".conv1.weight")[:, :, 0, 0] @ self.w("preprocess.conv.weight")[:, :, 0, 0]   # [32, 4]
-                    comp = {br: np.einsum("ockf,ci->oikf", self.w("%s.%s.weight" % (p, br)).astype(np.float64), W1.astype(np.float64))
-                            for br in ("l", "r")}
-                    g = dict(w0=P.conv_kmat(comp["l"], kk), w1=P.conv_kmat(comp["r"], kk))
-                    return self._bglu_weights(p, False, 64, "en.en1.0", g, nx_weights())
+                    g = dict(zip(("w0", "w1"), P.compose_stage1(self.sd, p, kk)))
+                    return P.bglu_fields(self.sd, p, False, 64, "en.en1.0", g, nx_weights(), npl, False)
                 bias = (tb, slot(16), slot(18), slot(17), slot(19), sbb)
                 src = dict(x0=self.src(x, 2, *nchw(2, T, F0)), x1=self.src(x_init, 2, *nchw(2, T, F0)), F_in=F0)
             else:
                 def make(p=p, kk=kk, k=k, nx_weights=nx_weights):
                     g = dict(w0=P.conv_kmat(self.sd[p + ".l.weight"], kk), w1=P.conv_kmat(self.sd[p + ".r.weight"], kk))
-                    f = self._bglu_weights(p, False, 64, "en.en%d.0" % k, g, nx_weights())
-                    f["bias0"], f["bias1"] = self.ctx.up(self.w(p + ".l.bias")).data_ptr(), self.ctx.up(self.w(p + ".r.bias")).data_ptr()
-                    return f
+                    return P.bglu_fields(self.sd, p, False, 64, "en.en%d.0" % k, g, nx_weights(), npl, True)
                 bias = None
                 src = dict(hp=self.hp_en[k], F_in=Fin, hp_par=self.parity_planes)
             kwargs = dict(taps=taps, sf_in=2, Fout=Fo, slope=self._slope("en.en%d.1.weight" % k), C2=64, **src)
@@ -1080,9 +889,7 @@ class EpsNetPlan(PlanBase):
                     g = dict(w0=P.convT_kmat(self.sd[p + ".l.weight"], kk0), w1=P.convT_kmat(self.sd[p + ".r.weight"], kk0),
                              w2=P.convT_kmat(self.sd[p + ".l.weight"], kk1), w3=P.convT_kmat(self.sd[p + ".r.weight"], kk1))
                     nxw = [self.w("%s.de%d.0.conv1.weight" % (de, k - 1))[:, :, 0, 0].T[:, :64]] if k > 1 else []
-                    f = self._bglu_weights(p, True, C2, bn, g, nxw)
-                    f["bias0"], f["bias1"] = self.ctx.up(self.w(p + ".l.bias")).data_ptr(), self.ctx.up(self.w(p + ".r.bias")).data_ptr()
-                    return f
+                    return P.bglu_fields(self.sd, p, True, C2, bn, g, nxw, npl, True)
 
                 kwargs = dict(hp=self.hp_de5b if (k == 5 and di == 1) else self.hp_de[k], F_in=Fin, taps=taps0, sf_in=1, Fout=(Fo + 1) // 2, p1mask=mask, Fout1=Fo // 2,
                               slope=self._slope("%s.de%d.3.weight" % (de, k)) if k > 1 else 1.0, C2=C2,
@@ -1343,16 +1150,23 @@ class GcrnPlan(PlanBase):
         """The grouped LSTM's output after LayerNorm 2 as [B, 256, T, 4]."""
         return self._nchw(self.glstm, True)
 
-    def _lstm_layer(self, layer, xproj_src_fn, y_su, y_sg):
+    def _lstm_proj(self, layer, proj, gx_lay):
+        """The input projections of one LSTM layer's two groups as batched GEMMs into gx.  proj(g) -> (source, Tin, Fin, taps,
+        W_ih -> k-major matrix, Tout, Fout, frame stride, bin stride of gx); gx_lay: (batch, gate-row) strides of gx -
+        (1, Bp): [G][T][4H][Bp] for the per-frame kernel, (2048, 1): [G][T][Bp][4H] for the fused forms (pdse_glstm_desc.gx1)."""
         B, T, Bp = self.B, self.T, self.Bp
         for g in range(2):
             p = "glstm.%s.%d." % (layer, g)
-            in0, Tin, Fin, taps, wk_fn, Tout, Fout, ost, osf = xproj_src_fn(g)
+            in0, Tin, Fin, taps, wk_fn, Tout, Fout, ost, osf = proj(g)
             self.gconv(in0=in0, Tin=Tin, Fin=Fin, taps=taps, sf_in=1, Cout=2048,
                        W=lambda p=p, wk_fn=wk_fn: dict(wk0=wk_fn(self.w(p + "weight_ih_l0")),
                                                        bias0=self.w(p + "bias_ih_l0") + self.w(p + "bias_hh_l0")),
-                       out=self.gx, out_strides=(1, Bp, 0, ost, osf), out_off=g * T * 2048 * Bp, B=B, Tout=Tout, Fout=Fout,
+                       out=self.gx, out_strides=gx_lay + (0, ost, osf), out_off=g * T * 2048 * Bp, B=B, Tout=Tout, Fout=Fout,
                        tag=TAG_PRIOR, label=p + "ih", s3g=self.split_bf16)
+
+    def _lstm_layer(self, layer, xproj_src_fn, y_su, y_sg):
+        B, T, Bp = self.B, self.T, self.Bp
+        self._lstm_proj(layer, xproj_src_fn, (1, Bp))
 
         def pack_whh():
             return P.pack_lstm_whh([self.w("glstm.%s.%d.weight_hh_l0" % (layer, g)) for g in range(2)])   # [2048, 512], gate order i,f,g,o
@@ -1375,21 +1189,9 @@ class GcrnPlan(PlanBase):
         layer-2 input projection at frame s-1, layer 2 at frame s-2, T + 2 launches.  Only the layer-1 input projection
         stays a batched GEMM in front of it."""
         B, T, Bp = self.B, self.T, self.Bp
-        for g in range(2):
-            p = "glstm.lstm_list1.%d." % g
-            in0, Tin, Fin, taps, wk_fn, Tout, Fout, ost, osf = proj1(g)
-            self.gconv(in0=in0, Tin=Tin, Fin=Fin, taps=taps, sf_in=1, Cout=2048,
-                       W=lambda p=p, wk_fn=wk_fn: dict(wk0=wk_fn(self.w(p + "weight_ih_l0")),
-                                                       bias0=self.w(p + "bias_ih_l0") + self.w(p + "bias_hh_l0")),
-                       out=self.gx, out_strides=(2048, 1, 0, ost, osf), out_off=g * T * 2048 * Bp, B=B, Tout=Tout, Fout=Fout,
-                       tag=TAG_PRIOR, label=p + "ih", s3g=self.split_bf16)      # gx1 [G][T][Bp][4H] (pdse_glstm_desc)
-
-        def pack():
-            return {k: self.ctx.up(v).data_ptr() for k, v in P.pack_glstm_wavefront(*self._glstm_natural()).items()}
-
+        self._lstm_proj("lstm_list1", proj1, (2048, 1))
         d = L.GlstmDesc()
-        for k, v in self.memo("glstm.wavefront", pack).items():
-            setattr(d, k, v)
+        self.apply(d, self.fields("glstm.wavefront", lambda: P.pack_glstm_wavefront(*self._glstm_natural())))
         d.gx1, d.gx2, d.part = self.gx.data_ptr(), self.gx2.data_ptr(), self.part.data_ptr()
         d.hT1, d.cst1, d.hT2, d.cst2 = self.hT.data_ptr(), self.cst.data_ptr(), self.hT2.data_ptr(), self.cst2.data_ptr()
         d.y, d.y_sb, d.y_st, d.y_su, d.y_sg = self.y.data_ptr(), T * 1024, 1024, 1, 512     # cat: index g*512 + u
@@ -1401,21 +1203,9 @@ class GcrnPlan(PlanBase):
         """gcrn.py:22-35 as ONE persistent launch (csrc/lstmp.hip, pdse_glstmp_desc): layer 1 at frame s, LayerNorm 1 +
         layer 2 at frame s - 1, weights in registers, the state exchanged between the 256 workgroups every step."""
         B, T, Bp = self.B, self.T, self.Bp
-        for g in range(2):
-            p = "glstm.lstm_list1.%d." % g
-            in0, Tin, Fin, taps, wk_fn, Tout, Fout, ost, osf = proj1(g)
-            self.gconv(in0=in0, Tin=Tin, Fin=Fin, taps=taps, sf_in=1, Cout=2048,
-                       W=lambda p=p, wk_fn=wk_fn: dict(wk0=wk_fn(self.w(p + "weight_ih_l0")),
-                                                       bias0=self.w(p + "bias_ih_l0") + self.w(p + "bias_hh_l0")),
-                       out=self.gx, out_strides=(2048, 1, 0, ost, osf), out_off=g * T * 2048 * Bp, B=B, Tout=Tout, Fout=Fout,
-                       tag=TAG_PRIOR, label=p + "ih", s3g=self.split_bf16)      # gx1 [G][T][Bp][4H]
-
-        def pack():
-            return {k: self.ctx.up(v).data_ptr() for k, v in P.pack_glstm_persistent(*self._glstm_natural()).items()}
-
+        self._lstm_proj("lstm_list1", proj1, (2048, 1))
         d = L.GlstmpDesc()
-        for k, v in self.memo("glstm.persistent", pack).items():
-            setattr(d, k, v)
+        self.apply(d, self.fields("glstm.persistent", lambda: P.pack_glstm_persistent(*self._glstm_natural())))
         d.gx1, d.gran, d.status = self.gx.data_ptr(), self.gran.data_ptr(), self.status.data_ptr()
         d.y, d.y_sb, d.y_st, d.y_su, d.y_sg = self.y.data_ptr(), T * 1024, 1024, 1, 512     # cat: index g*512 + u
         d.B, d.Bp, d.T, d.H, d.G, d.eps = B, Bp, T, 512, 2, 1e-5
@@ -1499,19 +1289,8 @@ class GcrnPlan(PlanBase):
                 Fout = 2 * (Fin - 1) + 3 + (1 if k == 2 else 0)
                 if k == 1 and self.fused_last and not self.force_generic:
                     # last stage (one output channel) + Linear(161,161) in one persistent launch (csrc/misc.hip)
-                    def last(p=p, br=br):
-                        up = lambda a: self.ctx.up(a).data_ptr()   # noqa: E731
-                        sc, sh = P.bn_fold(self.sd, "bn1_t_%d" % br)
-                        return dict(w1=up(self.w(p + ".conv1.weight")[:, 0, 0, :]),          # [32, 3]
-                                    w2=up(self.w(p + ".conv2.weight")[:, 0, 0, :]),
-                                    fcT=up(self.w("fc%d.weight" % br).T), fcb=up(self.w("fc%d.bias" % br)),
-                                    fcp=up(P.pack_a4(self.w("fc%d.weight" % br).T, np.where(np.arange(168) < 161, np.arange(168), -1))),
-                                    b1=float(self.w(p + ".conv1.bias")[0]), b2=float(self.w(p + ".conv2.bias")[0]),
-                                    bn_scale=float(sc[0]), bn_shift=float(sh[0]))
-
                     g = L.GcrnLastDesc()
-                    for kf, v in self.memo(p + ".last", last).items():
-                        setattr(g, kf, v)
+                    self.apply(g, self.fields(p + ".last", lambda p=p, br=br: P.gcrn_last_fields(self.sd, p, br)))
                     g.in0, g.in1 = self.d[3].data_ptr(), self.e[0].data_ptr()
                     g.out, g.out_sb = Ctx.ptr(out, (br - 1) * T * F0), 2 * T * F0
                     g.B, g.T = B, T
@@ -1778,7 +1557,7 @@ class AiaPlan(PlanBase):
             d.D = D.data_ptr()
             wk = P.conv_kmat(self.sd["%s.conv%d.weight" % (p, i)], kk)
             qe = P.f16_wexp(wk) if npl == 2 else 0
-            d.w = self.upw("%s.conv%d.dense%d" % (p, i, npl), lambda wk=wk, cin=cin, qe=qe: P.pack_dense(wk, cin, npl, qe).view(np.int16), np.int16).data_ptr()
+            d.w = self.upw("%s.conv%d.dense%d" % (p, i, npl), lambda wk=wk, cin=cin, qe=qe: P.pack_dense(wk, cin, npl, qe)).data_ptr()
             d.wexp = qe
             d.bias = self._wp("%s.conv%d.bias" % (p, i))
             d.gamma, d.beta = self._wp("%s.norm%d.weight" % (p, i)), self._wp("%s.norm%d.bias" % (p, i))
@@ -1861,7 +1640,7 @@ class AiaPlan(PlanBase):
 
             gd.split = 1
             gd.x = gx_in.data_ptr()
-            gd.wih = self.upw(g + "wih3", lambda: tiles("weight_ih_l0", dm).view(np.int16), np.int16).data_ptr()
+            gd.wih = self.upw(g + "wih3", lambda: tiles("weight_ih_l0", dm)).data_ptr()
             gd.bih = self.upw(g + "bih", lambda: np.stack([self.w(g + "bias_ih_l0"),
                                                            self.w(g + "bias_ih_l0_reverse")], 0)).data_ptr()
         elif self.fused_gru_input and dm == 32:
@@ -1878,7 +1657,7 @@ class AiaPlan(PlanBase):
                 self.gx, 12 * dm, FH, in_layout=lay, out_layout=lay, label=g + "ih")
         gd.gx, gd.y = self.gx.data_ptr(), self.gy.data_ptr()
         if split_gru:
-            gd.whh = self.upw(g + "whh3", lambda: tiles("weight_hh_l0", 2 * dm).view(np.int16), np.int16).data_ptr()
+            gd.whh = self.upw(g + "whh3", lambda: tiles("weight_hh_l0", 2 * dm)).data_ptr()
         else:
             gd.whh = self.upw(g + "whh", lambda: np.stack([P.pack_a(self.w(g + "weight_hh_l0" + suf).T)
                                                            for suf in ("", "_reverse")], 0)).data_ptr()   # [2, 3H/32, H/2, 64]

@@ -289,9 +289,6 @@ def pack_glstm_persistent(whh1, wih2, bih2, bhh2, whh2, gamma, beta):
 # ------------------------------------------------------------------------------------------
 # fused TCM residual block (csrc/tcm.hip, include/pdse.h: pdse_tcm_desc)
 # ------------------------------------------------------------------------------------------
-_RHO = np.array([[(r & 3) + 8 * (r >> 2) + 4 * h for h in (0, 1)] for r in range(16)])
-
-
 def pack_tcm_branch(k_main, k_mask):
     """k_* [320, 64] (row = tap*64 + channel) -> [2 mi][2 kh][20 g][2][64 lanes][4]."""
     out = np.zeros((2, 2, 20, 2, 64, 4), np.float32)
@@ -315,7 +312,7 @@ def pack_tcm_next(w1):
     for g in range(4):
         for e in range(4):
             for h in (0, 1):
-                rows = _RHO[4 * g + e, h]
+                rows = RHO[4 * g + e, h]
                 for w in range(4):
                     for q in range(2):
                         cin = 64 * w + 32 * q + rows
@@ -731,3 +728,226 @@ def unpack_bglu_chain(packed, M, K, q=0):
             for j in range(8):
                 out[:, 32 * (s >> 1) + rho_bf16(s & 1, j, h)] = f[:, s, h, :, j].reshape(-1)
     return out[:M]
+
+
+# ------------------------------------------------------------------------------------------
+# Descriptor fields: natural weights (numpy, or a state_dict and a prefix as bn_fold takes them) -> {descriptor field: array |
+# float | int | tuple}; a key (field, i) is element i of an array field.  No device and no pointer: nets.PlanBase.fields uploads
+# the arrays (nets.PlanBase._up states the one dtype convention) and PlanBase.apply sets them on the descriptor.
+# ------------------------------------------------------------------------------------------
+def _qof(npl):
+    """f16x2 (two planes): one power-of-two exponent per weight group (f16_wexp); every other plane count: 0."""
+    return f16_wexp if npl == 2 else (lambda *m: 0)
+
+
+def _bias_post(f, w):
+    """Constant biases (time-conditioned launches get device biases instead) and the BatchNorm folded behind a launch."""
+    for k in ("bias0", "bias1"):
+        if w.get(k) is not None:
+            f[k] = np.asarray(w[k])
+    if w.get("post") is not None:
+        f["post_scale"], f["post_shift"] = np.asarray(w["post"][0]), np.asarray(w["post"][1])
+
+
+def gconv_fields(w, ntaps, c0, c1, epi, cin1, pipelined_ok):
+    """The weight side of one gather-GEMM launch (korder 0: csrc/gconv.hip, korder 1: the pipelined csrc/gconv2.hip).
+    w: dict with wk0 [K, Cout] (k-major float64), optional wk1, wk2 / wk3 / ntaps1 (odd phase), bias0 / bias1, post (scale,
+    shift), xf (load transform), chain (biglu_chain), nx (list of dict(w [32, 64], bias or None))."""
+    f = {}
+    xf = w.get("xf")
+    xf_mode = 0
+    if xf is not None:
+        xf_mode = f["xf_mode"] = xf["mode"]
+        f["xf_scale0"], f["xf_shift0"], f["xf_slope0"] = np.asarray(xf["scale0"]), np.asarray(xf["shift0"]), float(xf["slope0"])
+        if xf["mode"] == 2:
+            f["xf_scale1"], f["xf_shift1"], f["xf_slope1"] = np.asarray(xf["scale1"]), np.asarray(xf["shift1"]), float(xf["slope1"])
+    wk0 = np.asarray(w["wk0"])
+    wk1 = w.get("wk1")
+    key = (epi, ntaps, c1 > 0, xf_mode)
+    if v2_supported(*key, cin1) and pipelined_ok:
+        rows = korder1_rows(ntaps, c0, c1, V2_CP[key])                 # pipelined kernel order
+        f["w0"], f["ksteps"], f["korder"] = pack_a4(wk0, rows), len(rows) // 2, 1
+        if wk1 is not None:
+            f["w1"] = pack_a4(wk1, rows)
+        if w.get("wk2") is not None:
+            rows1 = korder1_rows(w["ntaps1"], c0, 0, V2_CP[key])
+            f["w2"], f["w3"] = pack_a4(w["wk2"], rows1), pack_a4(w["wk3"], rows1)
+            f["ksteps1"] = len(rows1) // 2
+    else:
+        f["w0"] = pack_a(wk0)
+        f["ksteps"] = f["w0"].shape[1]
+        if wk1 is not None:
+            f["w1"] = pack_a(wk1)
+    _bias_post(f, w)
+    chain = w.get("chain")
+    if chain is not None:
+        f["C2"] = chain["C2"]
+        f["wlc"], f["wrc"] = pack_chain(chain["wlc"]), pack_chain(chain["wrc"])
+        f["blc"], f["brc"] = np.asarray(chain["blc"]), np.asarray(chain["brc"])
+        f["wc2"] = np.asarray(chain["wc2"], np.float64).reshape(32) if chain["C2"] == 1 else pack_chain(chain["wc2"])
+        f["bc2"] = np.asarray(chain["bc2"])
+    nx = w.get("nx")
+    if nx:
+        packs = []
+        for i, tl in enumerate(nx):
+            wn = np.asarray(tl["w"], np.float64)                       # [32 out, 64 in]
+            packs.append(np.concatenate([pack_chain(wn[:, :32]), pack_chain(wn[:, 32:])], 0))   # [2,16,64]
+            if tl.get("bias") is not None:
+                f[("nx_bias", i)] = np.asarray(tl["bias"])
+        f["nx_w"] = np.stack(packs, 0)
+    return f
+
+
+def gconv_s3_fields(w, ntaps, cin=32):
+    """korder 2 (csrc/gconv3.hip): exact three-way bf16 splits of a BIGLU block's weights (w as gconv_fields takes it), MFMA
+    bf16 fragment order.  cin 4: the composed encoder stage 1 (K = 10 taps x 4 channels = 40, zero-padded to three 16-deep blocks)."""
+    f = {"korder": 2, "ksteps": ntaps * cin // 2}
+    if cin == 4:
+        pad = lambda wk: np.concatenate([np.asarray(wk, np.float64), np.zeros((8, 32))], 0)   # noqa: E731  [48, 32]
+        f["w0"], f["w1"] = pack_s3_gather(pad(w["wk0"]), 3, 16), pack_s3_gather(pad(w["wk1"]), 3, 16)
+    else:
+        f["w0"], f["w1"] = pack_s3_gather(w["wk0"], ntaps), pack_s3_gather(w["wk1"], ntaps)
+    if w.get("wk2") is not None:
+        f["w2"], f["w3"] = pack_s3_gather(w["wk2"], w["ntaps1"]), pack_s3_gather(w["wk3"], w["ntaps1"])
+        f["ksteps1"] = w["ntaps1"] * 16
+    _bias_post(f, w)
+    chain = w["chain"]
+    f["C2"] = chain["C2"]
+    f["wlc"], f["wrc"] = pack_s3_chain(chain["wlc"]), pack_s3_chain(chain["wrc"])
+    f["blc"], f["brc"], f["bc2"] = np.asarray(chain["blc"]), np.asarray(chain["brc"]), np.asarray(chain["bc2"])
+    f["wc2"] = np.asarray(chain["wc2"], np.float64).reshape(32) if chain["C2"] == 1 else pack_s3_chain(chain["wc2"])
+    nx = w.get("nx")
+    if nx:
+        for i, tl in enumerate(nx):
+            if tl.get("bias") is not None:
+                f[("nx_bias", i)] = np.asarray(tl["bias"])
+        f["nx_w"] = np.stack([pack_s3_chain(tl["w"])[0] for tl in nx], 0)
+    return f
+
+
+def gconv_gemm_fields(w, ntaps, c0, c1, npl):
+    """csrc/gconv4.hip: LINEAR / GLU convolutions as GEMMs on split operands, weights streamed through LDS.  npl 3: korder 3
+    (bf16x3), 1: korder 4 (bf16 mode), 2: korder 5 (f16x2, one exponent per launch: wexp)."""
+    qe = _qof(npl)(*[w[k_] for k_ in ("wk0", "wk1") if w.get(k_) is not None])
+    f = {"korder": {3: 3, 1: 4, 2: 5}[npl], "ksteps": ntaps * (c0 + c1) // 2, "w0": pack_s3_gemm(w["wk0"], ntaps, c0, c1, npl, qe),
+         "wexp": qe}
+    if w.get("wk1") is not None:
+        f["w1"] = pack_s3_gemm(w["wk1"], ntaps, c0, c1, npl, qe)
+    _bias_post(f, w)
+    return f
+
+
+def biglu_chain(sd, p, C2, transposed):
+    """BIGLU chain operands of a BiConvGLU (Conv2d weights [out, in]) / BiConvTransGLU (ConvTranspose2d [in, out])."""
+    tr = (lambda m: m.T) if transposed else (lambda m: m)
+    return dict(C2=C2, wlc=tr(_np(sd[p + ".l_conv.weight"])[:, :, 0, 0]), blc=_np(sd[p + ".l_conv.bias"]),
+                wrc=tr(_np(sd[p + ".r_conv.weight"])[:, :, 0, 0]), brc=_np(sd[p + ".r_conv.bias"]),
+                wc2=tr(_np(sd[p + ".conv2.weight"])[:, :, 0, 0]), bc2=_np(sd[p + ".conv2.bias"]))
+
+
+def compose_stage1(sd, p, kk, with_pre=True):
+    """Encoder stage 1 with its 1x1 conv1 (and the folded Preprocess) composed into the two gather convolutions: conv1 -> l / r
+    is linear, so l(conv1(u)) is one convolution over the input channels with W'[o, i] = sum_c Wl[o, c] W1[c, i] (float64).
+    -> the k-major matrices of l and r (conv_kmat over the taps ``kk``)."""
+    W1 = _np(sd[p + ".conv1.weight"])[:, :, 0, 0]                          # [32, Cin]
+    if with_pre:
+        W1 = W1 @ _np(sd["preprocess.conv.weight"])[:, :, 0, 0]             # [32, 4] over (x, x_init)
+    return tuple(conv_kmat(np.einsum("ockf,ci->oikf", _np(sd["%s.%s.weight" % (p, br)]), W1), kk) for br in ("l", "r"))
+
+
+def bglu_fields(sd, p, transposed, C2, bn_prefix, gather, nx_w, npl, with_bias):
+    """The weight side of one pdse_bglu_desc (csrc/bglu.hip): gather = dict(w0, w1[, w2, w3]) of k-major matrices (ntaps x 32
+    rows; the composed stage 1: 40 rows), nx_w the natural matrices of the chained tiles; folds -log2 e into l_conv / r_conv and
+    the BatchNorm behind the block (bn_prefix) into conv2 (float64).  npl 2 (f16x2): every weight group is scaled by its own power
+    of two before the split (f16_wexp; pdse_bglu_desc.qexp).  with_bias: the constant gather biases of l / r."""
+    qof = _qof(npl)
+    ch = biglu_chain(sd, p, C2, transposed)
+    qG = qof(*gather.values())
+    f = {k: pack_bglu_in4(v, npl, qG) if v.shape[0] == 40 else pack_bglu_gather(v, v.shape[0] // 32, npl, qG) for k, v in gather.items()}
+    wlc, wrc = (-LOG2E * np.asarray(ch[k_], np.float64) for k_ in ("wlc", "wrc"))
+    qLC = qof(wlc, wrc)
+    f["wlc"], f["wrc"] = pack_bglu_chain(wlc, npl, qLC), pack_bglu_chain(wrc, npl, qLC)
+    f["blc"], f["brc"] = -LOG2E * np.asarray(ch["blc"], np.float64), -LOG2E * np.asarray(ch["brc"], np.float64)
+    wc2, bc2 = np.asarray(ch["wc2"], np.float64), np.asarray(ch["bc2"], np.float64)
+    if bn_prefix is not None:                       # y = (Wc2 g + bc2) s + t = (diag(s) Wc2) g + (s bc2 + t)
+        sc, sh = (np.asarray(v, np.float64) for v in bn_fold(sd, bn_prefix))
+        wc2, bc2 = wc2 * sc[:, None], bc2 * sc + sh
+    qC2 = qNX = 0
+    if C2 == 1:
+        f["wc2v"], f["bc2"] = wc2.reshape(32), np.concatenate([bc2.reshape(1), np.zeros(63)])
+    else:
+        qC2 = qof(wc2)
+        f["wc2"], f["bc2"] = pack_bglu_chain(wc2, npl, qC2), bc2
+    if nx_w:
+        qNX = qof(*nx_w)
+        f["nx_w"] = np.stack([pack_bglu_chain(w, npl, qNX)[0] for w in nx_w], 0)
+    f["qexp"] = (qG, qLC, qC2, qNX)
+    if with_bias:
+        f["bias0"], f["bias1"] = _np(sd[p + ".l.bias"]), _np(sd[p + ".r.bias"])
+    return f
+
+
+def tcm_branch_kmats(sd, p):
+    """The two dilated branches of a TCM residual block as k-major matrices [320, 64], row = tap * 64 + input channel."""
+    def km(br):
+        w = _np(sd[p + "." + br + ".2.weight"])                          # [64, 64, 5]
+        return np.concatenate([w[:, :, k].T for k in range(5)], axis=0)
+    return km("mainbranch"), km("maskbranch")
+
+
+def tcm_fields(sd, p, p_next):
+    """Operands and slopes of a pdse_tcm_desc (csrc/tcm.hip): block ``p`` and the conv1 of the next block (None: the last)."""
+    w = lambda k: _np(sd[k])   # noqa: E731
+    kmain, kmask = tcm_branch_kmats(sd, p)
+    sm, hm = bn_fold(sd, p + ".mainbranch.1")
+    sk, hk = bn_fold(sd, p + ".maskbranch.1")
+    s2, h2 = bn_fold(sd, p + ".conv2.1")
+    f = dict(wbr=pack_tcm_branch(kmain, kmask), bmain=w(p + ".mainbranch.2.bias"), bmask=w(p + ".maskbranch.2.bias"),
+             xf=np.stack([np.stack([sm, hm], 1), np.stack([sk, hk], 1)], 0).astype(np.float32),
+             wc2=pack_tcm_conv2(w(p + ".conv2.2.weight")[:, :, 0].T), bc2=w(p + ".conv2.2.bias"),
+             xf2=np.stack([s2, h2], 1).astype(np.float32), slope_main=float(w(p + ".mainbranch.0.weight")[0]),
+             slope_mask=float(w(p + ".maskbranch.0.weight")[0]), slope2=float(w(p + ".conv2.0.weight")[0]))
+    if p_next is not None:
+        f["wn1"], f["bn1"] = pack_tcm_next(w(p_next + ".conv1.weight")[:, :, 0]), w(p_next + ".conv1.bias")
+    return f
+
+
+def tcm2_fields(sd, p, p_next, npl, mode=0):
+    """Operands, slopes and exponents of a pdse_tcm2_desc (csrc/tcm2.hip): the bottleneck tensor travels as the split planes of
+    both branches' BN(PReLU(.)), so a block also carries the NEXT block's input transforms (par[512:]).  mode 1: only
+    ``p_next``'s conv1 (the launch in front of the stack; p is unused).  par [832]: (bmain, bmask, s2, h2) x 64, bc2 [256],
+    bn1 [64], (sm, hm, sk, hk) x 64 of the next block."""
+    w = lambda k: _np(sd[k])   # noqa: E731
+    qof = _qof(npl)
+    par = np.zeros(832, np.float32)
+    f = dict(slope2=0.0, slope_main_next=0.0, slope_mask_next=0.0)
+    qA = q2 = qN = 0
+    if mode == 0:
+        kmain, kmask = tcm_branch_kmats(sd, p)
+        s2, h2 = bn_fold(sd, p + ".conv2.1")
+        par[:256] = np.stack([w(p + ".mainbranch.2.bias"), w(p + ".maskbranch.2.bias"), s2, h2], 1).reshape(-1)
+        par[256:512] = w(p + ".conv2.2.bias")
+        k2 = w(p + ".conv2.2.weight")[:, :, 0].T
+        qA, q2 = qof(kmain, kmask), qof(k2)
+        f.update(wbr=pack_tcm2_branch(kmain, kmask, npl, qA), wc2=pack_tcm2_conv2(k2, npl, q2), slope2=float(w(p + ".conv2.0.weight")[0]))
+    if p_next is not None:
+        sm, hm = bn_fold(sd, p_next + ".mainbranch.1")
+        sk, hk = bn_fold(sd, p_next + ".maskbranch.1")
+        par[512:576] = w(p_next + ".conv1.bias")
+        par[576:] = np.stack([sm, hm, sk, hk], 1).reshape(-1)
+        wn1 = w(p_next + ".conv1.weight")[:, :, 0]
+        qN = qof(wn1)
+        f.update(wn1=pack_bglu_chain(wn1, npl, qN), slope_main_next=float(w(p_next + ".mainbranch.0.weight")[0]),
+                 slope_mask_next=float(w(p_next + ".maskbranch.0.weight")[0]))
+    f["par"], f["qexp"] = par, (qA, q2, qN)
+    return f
+
+
+def gcrn_last_fields(sd, p, br):
+    """pdse_gcrnlast_desc (csrc/misc.hip): decoder ``br``'s last stage ``p`` (one output channel) + Linear(161, 161)."""
+    w = lambda k: _np(sd[k])   # noqa: E731
+    sc, sh = bn_fold(sd, "bn1_t_%d" % br)
+    fcT = w("fc%d.weight" % br).T
+    return dict(w1=w(p + ".conv1.weight")[:, 0, 0, :], w2=w(p + ".conv2.weight")[:, 0, 0, :],           # [32, 3]
+                fcT=fcT, fcb=w("fc%d.bias" % br), fcp=pack_a4(fcT, np.where(np.arange(168) < 161, np.arange(168), -1)),
+                b1=float(w(p + ".conv1.bias")[0]), b2=float(w(p + ".conv2.bias")[0]), bn_scale=float(sc[0]), bn_shift=float(sh[0]))

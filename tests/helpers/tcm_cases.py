@@ -3,8 +3,8 @@ tests/test_gpu_tcm_ops.py (csrc/tcm.hip, csrc/tcm2.hip), so that the two cannot 
 
 A case chooses every slope, scale, shift and bias of a block itself (``params``), and ``build`` turns the natural
 parameters into a pdse_tcm_desc / pdse_tcm2_desc / pdse_tcm2s_desc with the packers, in the way
-nets.EpsNetPlan._residual_fused / _residual_split do (tcm_fields / tcm2_fields; the host file holds the two to byte
-identity on a synthetic DiffUNet1).  Buffers are laid out for the structural checks of the GPU file:
+packing.tcm_fields / packing.tcm2_fields do for nets.EpsNetPlan._residual_fused / _residual_split (tcm_fields / tcm2_fields
+here; the host file holds the two to byte identity on a synthetic DiffUNet1).  Buffers are laid out for the structural checks of the GPU file:
   * x, x_out, h, h_out sit inside allocations whose margins hold NaN: after a launch every addressed element is finite
     and the margins are NaN bit for bit;
   * an hs tensor keeps its 64 zero frames on either side (a tap outside [0, T) is an address there, not a select), the
@@ -167,7 +167,7 @@ def natural_from_sd(sd, prefix):
     return p
 
 
-# ---- descriptor fields from natural parameters (nets.EpsNetPlan._residual_fused / _residual_split) ---------------------
+# ---- descriptor fields from natural parameters (packing.tcm_fields / tcm2_fields, recorded by nets.EpsNetPlan._residual_fused / _residual_split) ----
 def _kmat(W):
     """[64 out, 64 in, 5] -> [320, 64]: row = tap * 64 + input channel."""
     return np.concatenate([W[:, :, k].T for k in range(5)], axis=0)

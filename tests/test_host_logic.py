@@ -28,6 +28,37 @@ def test_pack_roundtrip():
     assert sorted(P.RHO.reshape(-1).tolist()) == list(range(32))
 
 
+def test_packing_fields_are_pure(weights):
+    """Every ``*_fields`` function of packing.py called on natural weights alone - no Ctx, no device, no pointer: each value is
+    an ndarray of one of the three upload classes (uint16 planes, int32, floating point) or a Python scalar or tuple."""
+    P, L = pkg("packing"), pkg("_lib")
+    eps, gcrn = weights("DiffUNet1"), weights("GCRN")
+    p, t1, t2, kk = "en.conv2", "TCMs.0.residual1", "TCMs.0.residual2", P.conv_taps(2, 3, 0)[0]
+    nxw = P._np(eps["en.conv3.conv1.weight"])[:, :, 0, 0]                   # [32, 64]
+    w = dict(wk0=P.conv_kmat(eps[p + ".l.weight"], kk), wk1=P.conv_kmat(eps[p + ".r.weight"], kk), bias0=P._np(eps[p + ".l.bias"]),
+             post=P.bn_fold(eps, "en.en2.0"), chain=P.biglu_chain(eps, p, 64, False), nx=[dict(w=nxw, bias=P._np(eps["en.conv3.conv1.bias"]))],
+             xf=None)
+    w1 = dict(w, **dict(zip(("wk0", "wk1"), P.compose_stage1(eps, "en.conv1", P.conv_taps(2, 5, 1)[0]))))       # [40, 32]
+    wx = dict(zip(("wk0", "wk1"), P.tcm_branch_kmats(eps, t1)), xf=dict(mode=2, scale0=np.ones(64), shift0=np.zeros(64), slope0=0.25,
+                                                            scale1=np.ones(64), shift1=np.zeros(64), slope1=0.5))
+    wg = dict(wk0=P.conv_kmat(gcrn["conv2.conv1.weight"], [(0, 0), (0, 1), (0, 2)]), bias0=P._np(gcrn["conv2.conv1.bias"]), post=P.bn_fold(gcrn, "bn2"))
+    g, pd = dict(w0=w["wk0"], w1=w["wk1"]), "de_real.de1.0"
+    gd = {"w%d" % i: P.convT_kmat(eps["%s.%s.weight" % (pd, br)], P.convT_phase_taps(2, 5, ph)[0]) for i, (ph, br) in enumerate(((0, "l"), (0, "r"), (1, "l"), (1, "r")))}
+    got = [P.gconv_fields(w, 6, 32, 0, L.EPI_BIGLU, False, ok) for ok in (True, False)] + [P.gconv_fields(wx, 5, 64, 0, L.EPI_GLU, False, True)]
+    got += [P.gconv_s3_fields(w, 6), P.gconv_s3_fields(w1, 10, 4), P.tcm_fields(eps, t1, t2), P.tcm_fields(eps, t2, None), P.gcrn_last_fields(gcrn, "conv1_t_1", 1)]
+    for npl in (1, 2, 3):
+        got += [P.gconv_gemm_fields(wg, 3, 16, 0, npl), P.bglu_fields(eps, p, False, 64, "en.en2.0", g, [nxw], npl, True),
+                P.bglu_fields(eps, "en.conv1", False, 64, "en.en1.0", dict(w0=w1["wk0"], w1=w1["wk1"]), [], npl, False),
+                P.bglu_fields(eps, pd, True, 1, None, gd, [], npl, True), P.tcm2_fields(eps, t1, t2, npl, 0), P.tcm2_fields(eps, None, t1, npl, 1)]
+    assert len(got) == 26
+    for f in got:
+        for k, v in f.items():
+            if isinstance(v, np.ndarray):
+                assert v.dtype in (np.uint16, np.int32) or v.dtype.kind == "f", (k, v.dtype)
+            else:
+                assert type(v) in (int, float, tuple) and all(type(e) is int for e in (v if type(v) is tuple else ())), (k, type(v))
+
+
 @pytest.mark.parametrize("chained,split,plane_h,parity", [(True, False, False, True), (False, False, False, True), (True, True, False, True),
                                                          (True, True, True, True), (True, True, True, False)])
 def test_eps_net_plan_vs_oracle(weights, chained, split, plane_h, parity, monkeypatch):

@@ -3,8 +3,8 @@ torch.nn's Conv1d / PReLU / BatchNorm1d (eval) in double; (2) every case of test
 tests/test_gpu_tcm_ops.py launches - replayed on tests/emu.py (run_tcm, run_tcm2, run_tcm2s) and held to the float64
 reference at 1e-6, which pins packers and descriptor construction without a GPU, together with the f16x2 window of
 every np = 2 case; (3) the case helper's descriptor fields against the descriptors nets.EpsNetPlan records for a
-synthetic DiffUNet1 - on EpsNetPlan itself (_residual_fused, _residual_split at np 1 / 2 / 3, both modes), byte for
-byte."""
+synthetic DiffUNet1 - on EpsNetPlan itself (_residual_fused, _residual_split at np 1 / 2 / 3, both modes, which record what
+packing.tcm_fields / packing.tcm2_fields pack), byte for byte."""
 import ctypes
 
 import numpy as np
