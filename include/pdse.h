@@ -173,6 +173,12 @@ typedef struct pdse_gconv_desc {
   /* host copy of the first 12 entries of `taps` (korder 1 / 2 kernels, ntaps <= 10): read from the kernel arguments,
      i.e. from scalar registers - the device table costs every workgroup one dependent L2 round trip per tap */
   int32_t tap_dt[12], tap_df[12];
+  /* flat 1 (korder 3 / 5, LINEAR, one source, Fout == 1, ntaps * in0.C <= 512, Cout a multiple of 256: the LSTM input projections):
+     the same convolution, element for element and bit for bit, run in the flat form of csrc/gconv4.hip - the GEMM columns are
+     n = b * Tout + t over all B * Tout positions (tiles of 32 straddle batch items; every column addresses and masks its own
+     taps), a workgroup gathers and splits its 32 columns ONCE for the whole K and walks 32 channel tiles against them.  A form,
+     not a meaning: 0 runs the tiled kernel every other launch takes. */
+  int32_t flat, pad_;
 } pdse_gconv_desc;
 
 /* Diffusion-step embedding + every per-stage time bias folded through the following 1x1

@@ -170,6 +170,7 @@ static int gconv_launch(const pdse_gconv_desc* d, hipStream_t s, const bool dry)
     PDSE_REQUIRE(d->korder < 3 || d->epi != PDSE_EPI_BIGLU, "korder 3 / 4 / 5 have LINEAR / GLU epilogues only");
   }
   PDSE_REQUIRE((d->in0.blk == 0 && d->in1.blk == 0) || d->korder == 3 || d->korder == 4 || d->korder == 5, "channel-blocked sources (pdse_src.blk) are read by the korder 3 kernel only");
+  PDSE_REQUIRE(d->flat == 0 || d->korder == 3 || d->korder == 5, "the flat form (pdse_gconv_desc.flat) is one of the korder 3 / 5 kernel");
   if (d->xf_mode) {
     PDSE_REQUIRE(d->xf_scale0 && d->xf_shift0, "xf_mode set without scale/shift");
     PDSE_REQUIRE(d->xf_mode != 2 || (d->xf_scale1 && d->xf_shift1), "xf_mode 2 without second set");

@@ -397,6 +397,119 @@ static int launch4(const pdse_gconv_desc* d, hipStream_t s, const int mtiles) {
   return d->in0.blk ? launch4b<EPI, MT, true, 3>(d, s, mtiles) : launch4b<EPI, MT, false, 3>(d, s, mtiles);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Flat form (pdse_gconv_desc.flat; the LSTM input projections: LINEAR, one source, Fout == 1, K <= 512, Cout = 2048).
+// gconv4_kernel runs these as 16 channel groups x 8 column tiles per workgroup: every group gathers and splits the same
+// activations again, and the column tiles are cut per batch item.  Here
+//   * the columns are n = b Tout + t over all B Tout positions; a lane derives (b, t) of its own column, so a tile may
+//     straddle batch items: each column addresses its own item and masks its own taps;
+//   * the workgroup gathers its 32 columns once for the WHOLE K, splits them and keeps the planes in LDS in B-fragment order,
+//     [K block][plane][64 lanes] uint4 (64 KB for K = 512 in the two-plane form); one barrier, none afterwards;
+//   * its 8 waves then walk MTW channel tiles each (8 MTW = 32 tiles of 32 rows per workgroup) over all K blocks: the A
+//     fragments come straight from global memory into registers (the packed weights are read in 1 KB rows and are shared by
+//     every workgroup, so they stay in L2), the B fragments from LDS.
+// Every accumulator sees its K blocks in the order of gconv4_kernel ((tap, channel block)) and each product is the same
+// instruction on the same operands; the epilogue is the same function: results are bit for bit those of the tiled form.
+// ---------------------------------------------------------------------------------------------------------------
+template <int MTW, bool BLK, int NP>
+__global__ __launch_bounds__(512, NP == 2 ? 4 : 2) void gconv4_flat_kernel(const pdse_gconv_desc d) {
+  extern __shared__ uint4 bimg[];   // [K blocks][NP][64]
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col = lane & 31, h = lane >> 5;
+  const int n = blockIdx.x * 32 + col;
+  const bool pvalid = n < d.B * d.Tout;
+  const int b = pvalid ? n / d.Tout : 0;
+  const int t = pvalid ? n - b * d.Tout : 0;
+  const int mtiles = (d.Cout + 31) >> 5;
+  const int cbn = d.in0.C >> 4, nkb = d.ntaps * cbn;   // K blocks of 16 channels, order (tap, channel block)
+  const bool elu = d.in0.act == PDSE_ACT_ELU;
+
+  for (int kb = wave; kb < nkb; kb += 8) {   // wave-uniform
+    const int tap = kb / cbn, cb = kb - tap * cbn;
+    int dt = 0, df = 0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      dt = tap == k ? d.tap_dt[k] : dt;
+      df = tap == k ? d.tap_df[k] : df;
+    }
+    const int tin = t + dt, fin = df;   // Fout == 1: output bin 0
+    const bool inb = pvalid && fin >= 0 && fin < d.Fin && tin >= 0 && tin < d.Tin;
+    // a column without a value at this tap reads element 0 of the source (always there) and drops it
+    const int64_t pos = inb ? (int64_t)b * d.in0.sb + (int64_t)tin * d.in0.st + (int64_t)fin * d.in0.sf : 0;
+    float x[8];
+    if constexpr (BLK) {   // [B][C/8][T][F][8]: block 2 cb + h
+      const float* q = d.in0.ptr + pos + (int64_t)(2 * cb + h) * d.in0.sc;
+      const float4 v0 = *reinterpret_cast<const float4*>(q), v1 = *reinterpret_cast<const float4*>(q + 4);
+      x[0] = v0.x, x[1] = v0.y, x[2] = v0.z, x[3] = v0.w, x[4] = v1.x, x[5] = v1.y, x[6] = v1.z, x[7] = v1.w;
+    } else {
+      const float* q = d.in0.ptr + pos + (int64_t)(16 * cb + 8 * h) * d.in0.sc;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] = q[(int64_t)e * d.in0.sc];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = inb ? x[e] : 0.f;
+    if (elu) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] = x[e] < 0.f ? fast_exp(x[e]) - 1.0f : x[e];
+    }
+    uint4 bp[NP];
+    g4_split(x, bp);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) bimg[(kb * NP + p) * 64 + lane] = bp[p];
+  }
+  __syncthreads();
+
+  const int mt0 = (blockIdx.y * 8 + wave) * MTW;
+  if (mt0 >= mtiles) return;   // (behind the only barrier)
+  const uint4* const wl = reinterpret_cast<const uint4*>(d.w0) + lane;
+  u32x4 a[MTW][NP];   // (Cout is a multiple of 256: every tile mt0 .. mt0 + MTW - 1 exists)
+  auto lda = [&](const int kb, const int m) {
+    const u32x4* src = reinterpret_cast<const u32x4*>(wl + ((size_t)kb * mtiles + mt0 + m) * (NP * 64));
+#pragma unroll
+    for (int p = 0; p < NP; ++p) a[m][p] = src[p * 64];
+  };
+  f32x16 acc[MTW];
+#pragma unroll
+  for (int m = 0; m < MTW; ++m) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+    lda(0, m);
+  }
+  for (int kb = 0; kb < nkb; ++kb) {
+    uint4 bp[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) bp[p] = bimg[(kb * NP + p) * 64 + lane];
+    const int kn = min(kb + 1, nkb - 1);   // (the last block is requested once more instead of a branch in the loop)
+#pragma unroll
+    for (int m = 0; m < MTW; ++m) {
+      acc[m] = g4_mfma6(a[m], bp, acc[m]);
+      lda(kn, m);   // the next block's fragments of this tile, into the registers its products have just read
+    }
+  }
+  if constexpr (NP == 2) {
+    const float us = pow2i(-(PDSE_F16_ACT_EXP + d.wexp));
+#pragma unroll
+    for (int m = 0; m < MTW; ++m)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[m][r] *= us;
+  }
+  gconv_epilogue_impl<PDSE_EPI_LINEAR, MTW, true>(d, tail_from_desc(d), acc, acc, b, t, 0, pvalid, lane, h, mt0, mtiles, 0);   // out_cr == 1
+}
+
+template <bool BLK, int NP>
+static int launch4f(const pdse_gconv_desc* d, hipStream_t s) {
+  constexpr int MTW = 4;
+  const int mtiles = (d->Cout + 31) / 32, nkb = d->ntaps * (d->in0.C >> 4);
+  const long long N = (long long)d->B * d->Tout;
+  const dim3 grid((unsigned)((N + 31) / 32), (mtiles + 8 * MTW - 1) / (8 * MTW)), block(512);
+  const size_t lds = (size_t)nkb * NP * 64 * sizeof(uint4);
+  static unsigned long long attr_mask = 0;
+  if (lds > 64 * 1024 && pdse_lds_attr((const void*)gconv4_flat_kernel<MTW, BLK, NP>, &attr_mask, "gconv4 flat lds attribute")) return 1;
+  hipLaunchKernelGGL((gconv4_flat_kernel<MTW, BLK, NP>), grid, block, lds, s, *d);
+  return pdse_check_launch("gconv4 flat");
+}
+
 // korder 3: LINEAR / GLU, one or two sources of a multiple of 16 channels, no load transform; validated by pdse_gconv_launch
 static int check4(const pdse_gconv_desc* d) {
   const bool two = d->in1.C > 0;
@@ -417,11 +530,21 @@ static int check4(const pdse_gconv_desc* d) {
                    "no load transform / pad row, 32-bit gather offsets");
     return 1;
   }
+  if (d->flat && (d->flat != 1 || !(d->korder == 3 || d->korder == 5) || d->epi != PDSE_EPI_LINEAR || two || d->Fout != 1 ||
+                  d->ntaps * (d->in0.C >> 4) > 32 || (d->Cout & 255) || d->out_cr != 1 || (long long)d->B * d->Tout > (1ll << 30))) {
+    pdse_set_error("gconv4: the flat form takes korder 3 / 5 LINEAR launches of one source with Fout = 1, ntaps * C <= 512, "
+                   "Cout in multiples of 256 and out_cr = 1");
+    return 1;
+  }
   return 0;
 }
 
 int pdse_gconv4_launch(const pdse_gconv_desc* d, hipStream_t s) {
   if (check4(d)) return 1;
+  if (d->flat) {
+    if (d->korder == 5) return d->in0.blk ? launch4f<true, 2>(d, s) : launch4f<false, 2>(d, s);
+    return d->in0.blk ? launch4f<true, 3>(d, s) : launch4f<false, 3>(d, s);
+  }
   const int mtiles = (d->Cout + 31) / 32;
   if (d->epi == PDSE_EPI_GLU) return mtiles >= 2 ? launch4<PDSE_EPI_GLU, 2>(d, s, mtiles) : launch4<PDSE_EPI_GLU, 1>(d, s, mtiles);
   if (mtiles >= 4) return launch4<PDSE_EPI_LINEAR, 4>(d, s, mtiles);

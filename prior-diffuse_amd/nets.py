@@ -237,14 +237,16 @@ class PlanBase:
               bias1=None, bias1_sb=0, epi=L.EPI_LINEAR, act=L.ACT_NONE, act_slope=0.0,
               padrow=None, padrow_sb=0, padrow_off=0, cin1=False, resid=None, out,
               out_strides, out_off=0, out_cr=1, B, Tout, Fout, tag=TAG_NONE, bias0_off=0, phase1=None, nx=None,
-              bias1_off=0, bias_t0=None, label="gconv", s3=False, s3g=False, has_xf=False):
+              bias1_off=0, bias_t0=None, label="gconv", s3=False, s3g=False, has_xf=False, flat=False):
         """W: callable -> dict of the launch's natural weight operands (see ``packing.gconv_fields``); evaluated only when the
         weight bank does not hold this launch yet.  bias0 / bias1 / padrow / bias_t0 here are per-plan DEVICE tensors
         (time-conditioned biases); constant biases travel inside W.
         phase1 (dual-phase transposed conv, BIGLU): dict(mask, Fout1) - its weights wk2 / wk3 / ntaps1 come from W.
         nx (BIGLU, C2 == 64): dict(keep, row0, tiles=[dict(bias (device tensor) or None, bias_off, bias_sb, out, strides
         (sb, sc, st, sf), off, add)]) - 1x1 convolutions chained onto the block output (include/pdse.h: nx_*); their
-        weights (and constant biases) come from W()["nx"]."""
+        weights (and constant biases) come from W()["nx"].
+        flat (LINEAR GEMM form of one source with Fout == 1, korder 3 / 5): run the launch in the flat form of csrc/gconv4.hip
+        (pdse_gconv_desc.flat) - the same result bit for bit."""
         ctx = self.ctx
         d = L.GconvDesc()
         d.in0 = in0
@@ -307,6 +309,7 @@ class PlanBase:
         d.out_sb, d.out_sc_hi, d.out_sc_lo, d.out_st, d.out_sf = out_strides
         d.out_off, d.out_cr = out_off, out_cr
         d.B, d.Tout, d.Fout = B, Tout, Fout
+        d.flat = 1 if flat and s3g and d.korder in (3, 5) else 0
         self.add(d, tag)
         return d
 
@@ -1078,6 +1081,9 @@ class GcrnPlan(PlanBase):
     fuse_phases = True      # (f16x2 GEMMs, stages of <= 32 channels) a decoder stage's even and odd output bins as ONE launch: the
                             # even-bin descriptor names the next one as its odd phase and a plan runs the two together
                             # (csrc/gconv4.hip, bit-identical); False: the descriptors carry no mark - two launches per stage
+    flat_proj = True        # (f16x2 / bf16x3 GEMMs) the LSTM input projections in the flat form (pdse_gconv_desc.flat): columns over
+                            # (b, t), one gather and split per workgroup for 32 channel tiles; False: the tiled form every other
+                            # GEMM convolution takes (16 channel groups gathering the same tile) - bit-identical, for A/B timing
     persist_lstm = True     # B <= PERSIST_MAX_B and a plan that owns the GPU while it runs: the grouped LSTM as ONE persistent
                             # launch with register-resident weights (pdse_glstmp_desc, csrc/lstmp.hip) instead of T + 2 launches
     PERSIST_MAX_B = 4       # measured (tools/time_glstm.py --persist): 3.9 / 6.0 / 9.0 / 21.8 us per step at B = 1 / 2 / 4 / 8 against 11.4-12.0 for the wavefront
@@ -1162,7 +1168,8 @@ class GcrnPlan(PlanBase):
                        W=lambda p=p, wk_fn=wk_fn: dict(wk0=wk_fn(self.w(p + "weight_ih_l0")),
                                                        bias0=self.w(p + "bias_ih_l0") + self.w(p + "bias_hh_l0")),
                        out=self.gx, out_strides=gx_lay + (0, ost, osf), out_off=g * T * 2048 * Bp, B=B, Tout=Tout, Fout=Fout,
-                       tag=TAG_PRIOR, label=p + "ih", s3g=self.split_bf16)
+                       tag=TAG_PRIOR, label=p + "ih", s3g=self.split_bf16,
+                       flat=self.flat_proj and Fout == 1 and len(taps) * in0.C <= 512)
 
     def _lstm_layer(self, layer, xproj_src_fn, y_su, y_sg):
         B, T, Bp = self.B, self.T, self.Bp
