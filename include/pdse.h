@@ -808,7 +808,31 @@ typedef struct pdse_planes_desc {
  *                            "+ eps" on both signals adds to every frame's spectrum
  *   OFF_BRANGE  [25][2]      (whole numbers) first and last bin with a non-zero weight in each band (all below bin 256)
  * frames: [4][B][Mmax] per-frame values in the order of `out` (entries m.. of a shorter utterance are not written);
- * sorted: [2][B][Mmax] workspace.  Mmax = (Lmax - 480) / 120. */
+ * sorted: [2][B][Mmax] workspace.  Mmax = (Lmax - 480) / 120.
+ *
+ * measures (the former pad_ word; additive within ABI 9): 0 computes the four measures above and nothing else, and the stoi_*
+ * fields are not read.  PDSE_METRICS_STOI adds the short-time objective intelligibility measure of C. H. Taal et al. (IEEE
+ * TASL 2011) and its extended form of J. Jensen and C. H. Taal (IEEE/ACM TASLP 2016), csrc/stoi.hip: at most four further
+ * launches on stream s, no host synchronisation, no floating-point atomics, every sum in a fixed order; stoi_out[b] = {STOI,
+ * ESTOI} of utterance b over its own lens[b] samples, independent of B and of the utterance's place in the batch.
+ *   1. 16 kHz -> 10 kHz with the wav front end's converter (pdse_resample_desc above: up 5, down 8, half 128, the taps of
+ *      wavio.taps(16000, 10000); float64, product rounded before the add, one cast to fp32): n10 = ceil(5 len / 8) samples.
+ *      Published implementations design another low-pass; scores agree with theirs to filter-design accuracy, not bit for bit.
+ *   2. frames of 256 samples every 128, nf = 1 + (n10 - 256) / 128 whole frames, window hanning(258)[1:-1]; frame energy
+ *      20 log10(|w x| + eps) of the clean signal; frames of both signals whose clean energy lies within 40 dB of the loudest
+ *      are kept, in order (an integer prefix sum per utterance), and their windowed frames are overlap-added at hop 128.
+ *   3. the K kept frames give K frames of the compacted signals; 512-point DFT of each windowed frame in float64 on
+ *      v_mfma_f64_16x16x4_f64; band amplitudes sqrt(sum of |X|^2 over the band's bins) for 15 one-third-octave bands from 150 Hz.
+ *      Only bins 0..255 are computed: the highest band ends at bin 219.
+ *   4. every segment of 30 consecutive frames, hop 1: STOI scales the processed band to the clean band's norm, clips it at
+ *      x (1 + 10^(15/20)), removes the means and normalises; ESTOI mean-and-norm normalises the rows, then the columns, of
+ *      the 15 x 30 segment.  STOI = sum / (15 segments), ESTOI = sum / (30 segments).  K < 30: both are 1e-5.
+ * stoi_tables: PDSE_STOI_TABLE_DOUBLES float64 values built by the caller (prior-diffuse_amd/metrics.py: stoi_tables()):
+ *   OFF_WIN     [256]       0.5 (1 - cos(2 pi k / 257)), k = 1..256
+ *   OFF_BASIS   [256][512]  cos(2 pi k j / 512) for column j < 256, sin(2 pi k (j - 256) / 512) from column 256 on
+ *   OFF_BRANGE  [15][2]     (whole numbers) first bin of each band and the bin after its last
+ *   OFF_TAPS    [257]       the resampling taps
+ * stoi_work: PDSE_STOI_WORK_DOUBLES(B, Lmax) doubles of device workspace, 8-byte aligned, contents undefined on entry. */
 #define PDSE_METRICS_SSNR 0
 #define PDSE_METRICS_LLR 1
 #define PDSE_METRICS_WSS 2
@@ -819,6 +843,19 @@ typedef struct pdse_planes_desc {
 #define PDSE_METRICS_OFF_WEPS (PDSE_METRICS_OFF_CRIT + 25 * 512)
 #define PDSE_METRICS_OFF_BRANGE (PDSE_METRICS_OFF_WEPS + 2 * 512)
 #define PDSE_METRICS_TABLE_DOUBLES (PDSE_METRICS_OFF_BRANGE + 64)
+#define PDSE_METRICS_STOI 1
+#define PDSE_STOI_OFF_WIN 0
+#define PDSE_STOI_OFF_BASIS 256
+#define PDSE_STOI_OFF_BRANGE (256 + 256 * 512)
+#define PDSE_STOI_OFF_TAPS (PDSE_STOI_OFF_BRANGE + 32)
+#define PDSE_STOI_TABLE_DOUBLES (PDSE_STOI_OFF_TAPS + 264)
+/* samples at 10 kHz and whole frames of an utterance of len samples at 16 kHz */
+#define PDSE_STOI_N10(len) (((int64_t)(len) * 5 + 7) / 8)
+#define PDSE_STOI_FRAMES(len) (PDSE_STOI_N10(len) < 256 ? (int64_t)0 : 1 + (PDSE_STOI_N10(len) - 256) / 128)
+/* fp32 [2][B][N10] resampled signals, float64 [B][F] frame energies, int32 [B][F + 2] kept-frame indices and counts,
+ * float64 [2][B][F][15] band amplitudes */
+#define PDSE_STOI_WORK_DOUBLES(B, Lmax) \
+  ((int64_t)(B) * (PDSE_STOI_N10(Lmax) + PDSE_STOI_FRAMES(Lmax) + (PDSE_STOI_FRAMES(Lmax) + 2 + 1) / 2 + 30 * PDSE_STOI_FRAMES(Lmax)))
 typedef struct pdse_metrics_desc {
   const float* clean;        /* device [B][Lmax] */
   const float* proc;         /* device [B][Lmax]: the enhanced (or noisy) signal */
@@ -828,7 +865,10 @@ typedef struct pdse_metrics_desc {
   float* frames;             /* device [4][B][Mmax] */
   float* sorted;             /* device [2][B][Mmax] */
   float* out;                /* device [B][4] */
-  int32_t B, Lmax, Mmax, pad_;
+  int32_t B, Lmax, Mmax, measures;   /* measures: 0 or PDSE_METRICS_STOI */
+  const double* stoi_tables; /* device; the three stoi_ fields are read only with PDSE_METRICS_STOI */
+  double* stoi_work;         /* device [PDSE_STOI_WORK_DOUBLES(B, Lmax)] */
+  float* stoi_out;           /* device [B][2]: {STOI, ESTOI} */
 } pdse_metrics_desc;
 
 /* Wav front end (csrc/resample.hip, additive within ABI 9): integer PCM decode, mono mix and polyphase Kaiser-windowed-sinc rate

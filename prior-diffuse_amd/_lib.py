@@ -230,9 +230,11 @@ class GcrnLastDesc(C.Structure):
 
 
 class MetricsDesc(C.Structure):
-    """Objective quality scores of B utterance pairs (include/pdse.h: pdse_metrics_desc, csrc/metrics.hip)."""
+    """Objective quality scores of B utterance pairs (include/pdse.h: pdse_metrics_desc, csrc/metrics.hip; with
+    ``measures = METRICS_STOI`` also STOI and ESTOI, csrc/stoi.hip)."""
     _fields_ = [("clean", _fp), ("proc", _fp), ("lens_host", _fp), ("lens", _fp), ("tables", _fp), ("frames", _fp),
-                ("sorted", _fp), ("out", _fp), ("B", _i32), ("Lmax", _i32), ("Mmax", _i32), ("pad_", _i32)]
+                ("sorted", _fp), ("out", _fp), ("B", _i32), ("Lmax", _i32), ("Mmax", _i32), ("measures", _i32),
+                ("stoi_tables", _fp), ("stoi_work", _fp), ("stoi_out", _fp)]
 
 
 class ResampleDesc(C.Structure):
@@ -272,6 +274,29 @@ METRICS_OFF_CRIT = METRICS_OFF_BASIS + 480 * 1024
 METRICS_OFF_WEPS = METRICS_OFF_CRIT + 25 * 512
 METRICS_OFF_BRANGE = METRICS_OFF_WEPS + 2 * 512
 METRICS_TABLE_DOUBLES = METRICS_OFF_BRANGE + 64
+
+METRICS_STOI = 1          # PDSE_METRICS_STOI: pdse_metrics_desc.measures
+STOI_OFF_WIN, STOI_OFF_BASIS = 0, 256
+STOI_OFF_BRANGE = STOI_OFF_BASIS + 256 * 512
+STOI_OFF_TAPS = STOI_OFF_BRANGE + 32
+STOI_TABLE_DOUBLES = STOI_OFF_TAPS + 264
+
+
+def stoi_n10(length):
+    """PDSE_STOI_N10: samples at 10 kHz of ``length`` samples at 16 kHz."""
+    return (int(length) * 5 + 7) // 8
+
+
+def stoi_frames(length):
+    """PDSE_STOI_FRAMES: whole 256-sample frames every 128 of those samples."""
+    n = stoi_n10(length)
+    return 0 if n < 256 else 1 + (n - 256) // 128
+
+
+def stoi_work_doubles(B, Lmax):
+    """PDSE_STOI_WORK_DOUBLES: float64 elements of pdse_metrics_desc.stoi_work."""
+    F = stoi_frames(Lmax)
+    return int(B) * (stoi_n10(Lmax) + F + (F + 3) // 2 + 30 * F)
 
 # The operator table, in kind order: (kind, descriptor mirror, direct entry of include/pdse.h).  Everything below that exists
 # once per operator is derived from it; tests/test_abi.py holds every row, and every mirror's layout, against the header.

@@ -14,6 +14,7 @@
 //                         fwSNRseg values, all in float64.  The spectrum never leaves the workgroup.
 //   metrics_reduce_kernel one workgroup per utterance: the means, and for LLR / WSS the ascending order (rank count, NaN
 //                         last like numpy.sort) and the mean of the first round(0.95 m) values.
+// pdse_metrics_desc.measures = PDSE_METRICS_STOI adds STOI and ESTOI behind them: csrc/stoi.hip, four launches of its own.
 // Every sum has a fixed order and every frame is computed from its own samples at a position in its tile that depends on
 // the frame index alone, so an utterance's scores do not depend on scheduling, on B or on its place in the batch.
 //
@@ -400,8 +401,15 @@ int pdse_metrics_launch(const pdse_metrics_desc* d, hipStream_t s) {
     longest = d->lens_host[b] > longest ? d->lens_host[b] : longest;
   }
   REQ(d->Mmax >= (longest - WIN) / HOP && d->Mmax <= (d->Lmax - WIN) / HOP, "metrics: Mmax does not match the lengths");
+  // measures: 0 is the four measures above alone; the STOI fields are looked at only when it selects them
+  REQ(d->measures == 0 || d->measures == PDSE_METRICS_STOI, "metrics: unknown measure selector");
+  if (d->measures & PDSE_METRICS_STOI) {
+    REQ(d->stoi_tables && d->stoi_work && d->stoi_out, "metrics: null STOI pointer (stoi_tables, stoi_work or stoi_out) with STOI selected");
+    REQ(((uintptr_t)d->stoi_tables & 7) == 0 && ((uintptr_t)d->stoi_work & 7) == 0, "metrics: stoi_tables and stoi_work must be 8-byte aligned");
+  }
   hipLaunchKernelGGL(metrics_time_kernel, dim3((d->Mmax + TFR - 1) / TFR, d->B), dim3(256), 0, s, *d);
   hipLaunchKernelGGL(metrics_spec_kernel, dim3((d->Mmax + SFR - 1) / SFR, d->B), dim3(256), 0, s, *d);
   hipLaunchKernelGGL(metrics_reduce_kernel, dim3(d->B), dim3(256), 0, s, *d);
-  return pdse_check_launch("metrics");
+  if (pdse_check_launch("metrics")) return 1;
+  return (d->measures & PDSE_METRICS_STOI) ? pdse_stoi_launch(d, s) : 0;
 }

@@ -72,6 +72,7 @@ int pdse_gconv4_launch(const pdse_gconv_desc* d, hipStream_t s);  // korder 3 (s
 int pdse_gconv_pair_check(const pdse_gconv_desc* d, const pdse_gconv_desc* e);     // both descriptors, then:
 int pdse_gconv4_pair_check(const pdse_gconv_desc* d, const pdse_gconv_desc* e);    // that e is d's odd phase
 int pdse_gconv4_pair_launch(const pdse_gconv_desc* d, const pdse_gconv_desc* e, hipStream_t s);
+int pdse_stoi_launch(const pdse_metrics_desc* d, hipStream_t s);   /* csrc/stoi.hip, reached through pdse_metrics_launch (measures) */
 int pdse_gru3_launch(const pdse_gru_desc* d, hipStream_t s);   /* csrc/gru3.hip, reached through pdse_gru_launch */
 int pdse_range_validate(const pdse_range_desc* d);                 /* reads the row table back and checks it (direct launches, plan_add) */
 #endif

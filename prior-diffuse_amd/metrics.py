@@ -2,10 +2,12 @@
 (SNRseg :36-55, llr :192-263, wss :266-427, fwSNRseg :58-174) and the ``composite`` arithmetic (:462-470), for batches that are
 already in HBM (``ComplexDDPMTrainer.evaluate_batch``) or for two directories of wav files:
 
-    python -m prior_diffuse_amd.metrics REF_DIR DEG_DIR
+    python -m prior_diffuse_amd.metrics [--stoi] REF_DIR DEG_DIR
 
-PESQ and STOI are not computed: the reference takes them from the ``pesq`` and ``pystoi`` packages, which are not dependencies
-of this one.  The kernels are csrc/metrics.hip (include/pdse.h: pdse_metrics_desc); there is no CPU fallback."""
+The reference takes PESQ and STOI from the ``pesq`` and ``pystoi`` packages, which are not dependencies of this one.  PESQ (ITU
+code) is not computed.  STOI and ESTOI are, on request (``quality(stoi=True)``, ``--stoi``): csrc/stoi.hip, written from the
+two papers (Taal et al. 2011, Jensen & Taal 2016).  The kernels are csrc/metrics.hip and csrc/stoi.hip (include/pdse.h:
+pdse_metrics_desc); there is no CPU fallback."""
 import glob
 import os
 import sys
@@ -71,7 +73,52 @@ def tables():
     return out
 
 
+# ---- STOI / ESTOI: the measure's constants (Taal et al. 2011, section II; they are properties of the measure) ----------------
+STOI_FS, STOI_FRAME, STOI_HOP, STOI_NFFT, STOI_BANDS, STOI_SEG = 10000, 256, 128, 512, 15, 30
+STOI_MIN_CF, STOI_BETA, STOI_DYN_RANGE = 150.0, -15.0, 40.0
+STOI_BINS = 256        # DFT bins csrc/stoi.hip computes (0..255 of the 257): every band ends below
+
+
+def stoi_band_edges():
+    """[15][2] first bin and the bin after the last of every one-third-octave band: centre frequencies 150 * 2^(k / 3) Hz, edges
+    a sixth of an octave to either side, each moved to the nearest bin of the 512-point DFT at 10 kHz."""
+    f = np.linspace(0, STOI_FS, STOI_NFFT + 1)[:STOI_NFFT // 2 + 1]
+    k = np.arange(STOI_BANDS)
+    lo = STOI_MIN_CF * 2.0 ** ((2 * k - 1) / 6.0)
+    hi = STOI_MIN_CF * 2.0 ** ((2 * k + 1) / 6.0)
+    edges = np.zeros((STOI_BANDS, 2), dtype=np.int64)
+    for i in range(STOI_BANDS):
+        edges[i] = np.argmin((f - lo[i]) ** 2), np.argmin((f - hi[i]) ** 2)
+    return edges
+
+
+def stoi_tables():
+    """The constant tables of pdse_metrics_desc.stoi_tables in float64: the analysis window hanning(258)[1:-1], the cos|sin
+    basis of the 512-point DFT for bins 0..255, the band edges, and the taps of the 16 kHz -> 10 kHz converter
+    (``wavio.taps``).  Returns a float64 array of STOI_TABLE_DOUBLES values (include/pdse.h lists the sections)."""
+    from . import wavio
+
+    win = 0.5 * (1 - np.cos(2 * np.pi * np.arange(1, STOI_FRAME + 1) / (STOI_FRAME + 1)))
+    k = np.arange(STOI_FRAME)[:, None]
+    j = np.arange(STOI_BINS)[None, :]
+    ang = ((k * j) % STOI_NFFT) * (2 * np.pi / STOI_NFFT)
+    basis = np.concatenate([np.cos(ang), np.sin(ang)], axis=1)                      # [256][512]
+    edges = stoi_band_edges()
+    if edges.max() > STOI_BINS or (edges[:, 0] >= edges[:, 1]).any():
+        raise AssertionError("a one-third-octave band is empty or reaches bin 256: csrc/stoi.hip computes bins 0..255")
+    h, up, down, half = wavio.taps(FS, STOI_FS)
+    if (up, down, half, h.size) != (5, 8, 128, 257):
+        raise AssertionError("csrc/stoi.hip holds the polyphase constants of 16 kHz -> 10 kHz: up 5, down 8, half 128")
+    out = np.zeros(L.STOI_TABLE_DOUBLES)
+    out[L.STOI_OFF_WIN:L.STOI_OFF_WIN + STOI_FRAME] = win
+    out[L.STOI_OFF_BASIS:L.STOI_OFF_BRANGE] = basis.reshape(-1)
+    out[L.STOI_OFF_BRANGE:L.STOI_OFF_BRANGE + 2 * STOI_BANDS] = edges.reshape(-1)
+    out[L.STOI_OFF_TAPS:L.STOI_OFF_TAPS + h.size] = h
+    return out
+
+
 _TABLES = {}      # device -> uploaded tables
+_STOI_TABLES = {}
 
 
 def _device_tables(device):
@@ -83,6 +130,15 @@ def _device_tables(device):
         # cannot run ahead of the upload
         _TABLES[key] = torch.from_numpy(tables()).to(device)
     return _TABLES[key]
+
+
+def _device_stoi_tables(device):
+    import torch
+
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _STOI_TABLES:
+        _STOI_TABLES[key] = torch.from_numpy(stoi_tables()).to(device)      # pageable, as above
+    return _STOI_TABLES[key]
 
 
 def _check(clean, proc, lens):
@@ -108,7 +164,7 @@ def _check(clean, proc, lens):
     return B, Lmax, lens_np
 
 
-def quality(clean, proc, lens=None, per_frame=False):
+def quality(clean, proc, lens=None, per_frame=False, stoi=False):
     """SSNR, LLR, WSS and fwSNRseg of every utterance pair of a batch, computed on the device the tensors live on.
 
     clean, proc: fp32 [B, L] device tensors (``proc`` is the enhanced or the noisy signal); lens: per-utterance lengths
@@ -116,7 +172,15 @@ def quality(clean, proc, lens=None, per_frame=False):
     beyond an utterance's length are never read.  Returns a dict of device tensors ``ssnr``, ``llr``, ``wss``, ``fwsnrseg``,
     each [B]; with ``per_frame`` also ``frames`` ([4, B, M] in that order; entries beyond an utterance's own
     ``frame_count`` are undefined) and ``frame_counts`` (list).  Asynchronous on the current stream; the constant tables are
-    uploaded once per device.  Raises ValueError for shape or length errors."""
+    uploaded once per device.  Raises ValueError for shape or length errors.
+
+    stoi=True adds ``stoi`` and ``estoi`` ([B] device tensors): the short-time objective intelligibility measure of Taal et al.
+    (2011) and its extended form (Jensen & Taal 2016) at 10 kHz, 256-sample frames every 128, 15 one-third-octave bands, segments
+    of 30 frames (csrc/stoi.hip, four more launches).  An utterance left with fewer than 30 frames after the silent frames are
+    removed scores 1e-5.  The 16 kHz -> 10 kHz conversion is this package's own Kaiser-windowed-sinc converter
+    (``wavio.resample``, bit for bit); ``pystoi`` designs a different low-pass, so - like the wav front end against librosa -
+    scores agree with it to filter-design accuracy, not bit for bit, and that agreement has not been measured.
+    With the default the call, its launches and its result are what they were without the argument."""
     import torch
 
     B, Lmax, lens_np = _check(clean, proc, lens)
@@ -136,8 +200,15 @@ def quality(clean, proc, lens=None, per_frame=False):
     d.clean, d.proc, d.lens_host, d.lens = clean.data_ptr(), proc.data_ptr(), lens_np.ctypes.data, lens_dev.data_ptr()
     d.tables, d.frames, d.sorted, d.out = tab.data_ptr(), frames.data_ptr(), work.data_ptr(), out.data_ptr()
     d.B, d.Lmax, d.Mmax = B, Lmax, Mmax
+    if stoi:
+        stab = _device_stoi_tables(dev)
+        swork = torch.empty(L.stoi_work_doubles(B, Lmax), dtype=torch.float64, device=dev)
+        sout = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        d.measures, d.stoi_tables, d.stoi_work, d.stoi_out = L.METRICS_STOI, stab.data_ptr(), swork.data_ptr(), sout.data_ptr()
     L.launch(d, torch.cuda.current_stream(dev).cuda_stream, device=dev)
     res = {"ssnr": out[:, 0], "llr": out[:, 1], "wss": out[:, 2], "fwsnrseg": out[:, 3]}
+    if stoi:
+        res["stoi"], res["estoi"] = sout[:, 0], sout[:, 1]
     if per_frame:
         res["frames"] = frames
         res["frame_counts"] = [frame_count(n) for n in lens_np]
@@ -201,9 +272,12 @@ def main(argv=None, device=None, batch=32):
     """device: default the current cuda device."""
     import torch
 
-    argv = sys.argv[1:] if argv is None else argv
+    argv = list(sys.argv[1:] if argv is None else argv)
+    stoi = "--stoi" in argv
+    if stoi:
+        argv.remove("--stoi")
     if len(argv) != 2:
-        print("usage: python -m prior_diffuse_amd.metrics REF_DIR DEG_DIR")
+        print("usage: python -m prior_diffuse_amd.metrics [--stoi] REF_DIR DEG_DIR")
         return 2
     pairs = pair_files(argv[0], argv[1])
     if not pairs:
@@ -217,13 +291,18 @@ def main(argv=None, device=None, batch=32):
         for i in range(0, len(items), batch):       # files of one length share a batch
             c = torch.stack([a for a, _ in items[i:i + batch]])
             p = torch.stack([a for _, a in items[i:i + batch]])
-            q = quality(c, p)
-            rows.append(torch.stack([q["ssnr"], q["llr"], q["wss"], q["fwsnrseg"]], dim=1).double().cpu().numpy())
+            q = quality(c, p, stoi=True) if stoi else quality(c, p)
+            keys = ["ssnr", "llr", "wss", "fwsnrseg"] + (["stoi", "estoi"] if stoi else [])
+            rows.append(torch.stack([q[k] for k in keys], dim=1).double().cpu().numpy())
     pm = np.concatenate(rows).mean(axis=0)
     print("ref=", argv[0])
     print("deg=", argv[1])
-    print("ssnr:%6.4f llr:%6.4f wss:%6.4f fwsnrseg:%6.4f" % tuple(pm))
-    print("PESQ and STOI are not computed (the reference takes them from the pesq and pystoi packages).")
+    if stoi:
+        print("ssnr:%6.4f llr:%6.4f wss:%6.4f fwsnrseg:%6.4f stoi:%6.4f estoi:%6.4f" % tuple(pm))
+        print("PESQ is not computed (the reference takes it from the pesq package).")
+    else:
+        print("ssnr:%6.4f llr:%6.4f wss:%6.4f fwsnrseg:%6.4f" % tuple(pm))
+        print("PESQ and STOI are not computed (the reference takes them from the pesq and pystoi packages).")
     return 0
 
 

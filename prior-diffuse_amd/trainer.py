@@ -263,13 +263,15 @@ class ComplexDDPMTrainer(object):
         out = self._checked(run, B=B, L_=L_, ragged=True)
         return [out[b, :lens[b]].clone() for b in range(B)]
 
-    def evaluate_batch(self, noisy_wavs, clean_wavs, x_T=None):
+    def evaluate_batch(self, noisy_wavs, clean_wavs, x_T=None, stoi=False):
         """The validation loop's enhancement and scoring in one call (:408-494 with utils/metrics.py: compare_complex, less
         PESQ and STOI): ``enhance_batch(noisy_wavs, trim_to_frames=True)``, the clean references cut to the same
         ``(frame_num - 1) * 160`` samples (utils/metrics.py:562-563), then ``metrics.quality`` on the device-resident result.
         Returns (enhanced_list, scores): ``scores`` holds the per-utterance device tensors ``ssnr``, ``llr``, ``wss``,
         ``fwsnrseg`` and, as compare_complex returns means, ``mean_ssnr`` ... ``mean_fwsnrseg`` (0-dim device tensors).
-        One synchronisation in total: the pass's own check (``_checked``); the scores are asynchronous."""
+        One synchronisation in total: the pass's own check (``_checked``); the scores are asynchronous.
+        stoi=True: ``metrics.quality(..., stoi=True)``, so ``scores`` also holds ``stoi``, ``estoi``, ``mean_stoi`` and
+        ``mean_estoi`` - every figure of the reference's loop except PESQ."""
         from . import metrics
 
         clean_wavs = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in clean_wavs]
@@ -283,8 +285,8 @@ class ComplexDDPMTrainer(object):
         pad = torch.nn.utils.rnn.pad_sequence
         clean = pad([c[:n] for c, n in zip(clean_wavs, cut)], batch_first=True).to(self.device)
         with torch.cuda.device(self.device):
-            scores = metrics.quality(clean, pad(enhanced, batch_first=True), lens=cut)
-        for k in ("ssnr", "llr", "wss", "fwsnrseg"):
+            scores = metrics.quality(clean, pad(enhanced, batch_first=True), lens=cut, stoi=stoi)
+        for k in ("ssnr", "llr", "wss", "fwsnrseg") + (("stoi", "estoi") if stoi else ()):
             scores["mean_" + k] = scores[k].mean()
         return enhanced, scores
 
