@@ -373,6 +373,15 @@ typedef struct pdse_glstm_desc {
      11.7 us per step when the plan owns the GPU; measured slower by 1 % with three batches in flight).  Same summation orders:
      bit-identical results. */
   int32_t slices;
+  /* Chunked form (additive within ABI 9; the descriptor grew by one 8-byte word, so a caller compiled against the earlier
+     header must be rebuilt - its shorter struct would be read past its end; pdse_desc_size() tells the two apart and plan files
+     record the size): tc == 0 and lag == 0 is the three-stage wavefront above.  tc >= 1 takes the layer-2 input projection out of the per-step launches: they carry layer 1 at frame s
+     and layer 2 at frame s - lag only (lag == tc + 1, T + tc + 1 of them), and one projection launch per chunk of tc frames
+     runs between them.  hT1, part and gx2 are then rings of R = 2 tc frames instead of ping-pongs:
+       hT1 [R][G][H/8][2][Bp][4]  h1[t] in slot (t + 1) % R;   part [R][G][H/8][Bp][2] and gx2 [R][G][4H][Bp]  frame t in slot t % R
+     (gx2: chunk t / tc in half (t / tc) & 1).  Layer 1 is the same code in the same order: h1 is bit-identical. */
+  int32_t tc;
+  int32_t lag;
   int32_t pad_;
 } pdse_glstm_desc;
 

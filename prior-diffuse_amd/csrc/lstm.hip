@@ -142,7 +142,12 @@ __device__ long long* g_trace_l = nullptr;   // PDSE_GLSTM_TRACE=1 (diagnostic):
 // the 256 CUs hold two workgroups (A alone 6.9 us, A + C 11.3: the stages queue for the same ports).  NS = 2 (round 4): the two
 // slices of a workgroup share ONE fetch of the state (36 MB per step), 3 x 64 workgroups sit on a CU of their own, every summation
 // keeps its order (reduction over the 8 waves per row, LayerNorm partials per 8 units): results are bit-identical to NS = 1.
-template <int NS>
+//
+// CH (pdse_glstm_desc.tc >= 1): the chunked form.  Stage B is the one stage that is not sequential - gx2[t] depends on h1[t]
+// alone - so it leaves the per-step launch: grid z carries stages A and C only (C at frame s - lag, lag = tc + 1), and
+// glstm_proj_kernel below evaluates stage B for a chunk of tc frames from ONE fetch of its weight slice.  hT1, part and gx2
+// are rings of R = 2 tc frames (pdse.h).  Stages A and C are the same code in the same order as in the three-stage form.
+template <int NS, bool CH>
 __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d, const int s, const int stage_mask) {
   extern __shared__ __attribute__((aligned(16))) float lds_[];
   float (*red)[32 * NS][33] = reinterpret_cast<float (*)[32 * NS][33]>(lds_);                    // [8 waves][rows][items + 1]
@@ -152,8 +157,9 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
   const int col = lane & 31, h = lane >> 5;
   const int slice = blockIdx.x * NS, g = blockIdx.y;
   const int nbt = d.Bp >> 5;
-  const int stage = blockIdx.z / nbt, bt = blockIdx.z - stage * nbt;
-  const int t = s - stage;
+  const int zs = blockIdx.z / nbt, bt = blockIdx.z - zs * nbt;
+  const int stage = CH ? 2 * zs : zs;
+  const int t = s - (CH ? (stage ? d.lag : 0) : stage);
   if (t < 0 || t >= d.T || !((stage_mask >> stage) & 1)) return;
 #ifdef PDSE_DIAG
   long long* const trace = (s == d.T / 2) ? g_trace_l : nullptr;
@@ -165,6 +171,9 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
   const int H = d.H, Bp = d.Bp, G = d.G;
   const size_t hsz = (size_t)H * Bp;               // one group's state
   const int par = t & 1;
+  const int R = CH ? 2 * d.tc : 2;
+  const int r1 = CH ? t % R : par;                 // hT1 slot of h1[t-1]; part and gx2 slot of frame t
+  const int w1 = CH ? (t + 1) % R : par ^ 1;       // hT1 slot of h1[t]
 
   // ---- operands of this stage's matvec
   const float* Aw;                                  // [H/8 groups of 4 k-steps][64 lanes][4]
@@ -174,10 +183,10 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
   bool skip = false;
   if (stage == 0) {                                 // W_hh1 h1[t-1]
     Aw = d.whh1;
-    hsrc0 = hsrc1 = d.hT1 + ((size_t)par * G + g) * hsz;
+    hsrc0 = hsrc1 = d.hT1 + ((size_t)r1 * G + g) * hsz;
     kq0 = 0, kq1 = 32;
     skip = t == 0;
-  } else if (stage == 1) {                          // W'_ih2 y1[t]: features of chunk g = units 256g..256g+255 of BOTH groups
+  } else if (!CH && stage == 1) {                          // W'_ih2 y1[t]: features of chunk g = units 256g..256g+255 of BOTH groups
     Aw = d.wih2;
     const float* base = d.hT1 + (size_t)((t + 1) & 1) * G * hsz;   // h1[t] was written to parity (t & 1) ^ 1
     hsrc0 = base, hsrc1 = base + hsz;               // source group g' = 0, then g' = 1
@@ -205,7 +214,7 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
     // stage B, LayerNorm fold without its cancellation: W' (y - k) - (mu - k) W' 1 for ANY k; with k = the item's own first feature
     // (within a few deviations of mu) both terms are of the size of the deviations, not of the mean.  Requested first: the
     // subtraction from operand i then waits for operand i alone
-    const float k0 = stage == 1 ? hsrc0[(size_t)(bt * 32 + col) * 4] : 0.f;
+    const float k0 = !CH && stage == 1 ? hsrc0[(size_t)(bt * 32 + col) * 4] : 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
 #pragma unroll
@@ -213,7 +222,7 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
       bv[i] = B4[(size_t)i * 2 * Bp];
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (stage == 1) {
+    if (!CH && stage == 1) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) bv[i].x -= k0, bv[i].y -= k0, bv[i].z -= k0, bv[i].w -= k0;
     }
@@ -253,12 +262,12 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
       if (t > 0) c_old = d.cst1[ci];
     } else if (stage == 2) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) pre[q] = d.gx2[(((size_t)par * G + g) * (4 * H) + (size_t)q * H + hu) * Bp + b];
+      for (int q = 0; q < 4; ++q) pre[q] = d.gx2[(((size_t)r1 * G + g) * (4 * H) + (size_t)q * H + hu) * Bp + b];
       if (t > 0) c_old = d.cst2[ci];
     }
   }
   float k0e = 0.f;                                   // stage B: the k of the fold, for the epilogue's item
-  if (stage == 1) {
+  if (!CH && stage == 1) {
     k0e = hsrc0[(size_t)b * 4];
     // LayerNorm statistics of frame t: 2 groups x H/8 slices partial (sum, sum of squared deviations from the slice's own mean)
     // pairs per batch item, fixed order; a part's 8 entries are combined about the part's mean (Chan): no raw squares anywhere
@@ -307,7 +316,7 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
       gate[q] = sum;
     }
   }
-  if (stage == 1) {
+  if (!CH && stage == 1) {
     if (!fin) return;                               // no further barrier in this stage
     double s1 = 0.0;
 #pragma unroll
@@ -340,7 +349,7 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
     hv = sigm_g(gate[3]) * tanhf(c);
     if (stage == 0) {
       d.cst1[ci] = c;
-      d.hT1[((size_t)(par ^ 1) * G + g) * hsz + hidx(hu, b, Bp)] = hv;
+      d.hT1[((size_t)w1 * G + g) * hsz + hidx(hu, b, Bp)] = hv;
       stat[uu][bb][0] = hv;                         // stat[] is unused in stages 0 / 2: staging for the partial sums
     } else {
       d.cst2[ci] = c;
@@ -368,16 +377,177 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
       const float e = v[k] - m;
       m2 += e * e;
     }
-    float2* P2 = reinterpret_cast<float2*>(d.part) + (((size_t)par * G + g) * (H / 8) + slice + ps) * Bp + b;
+    float2* P2 = reinterpret_cast<float2*>(d.part) + (((size_t)r1 * G + g) * (H / 8) + slice + ps) * Bp + b;
     *P2 = make_float2(s1, m2);
   }
 }
 
+// Stage B of the chunked form: gx2 of frames t0 .. t0 + nf - 1 (one chunk) as one launch.  Workgroup (slice, g, batch tile,
+// frame share fs of FS) keeps its 32 gate rows x K = 512 of W'_ih2 in registers (each wave its 64 k-steps, 8 x 16 bytes per
+// lane) and walks its frames: the weights are fetched once per chunk and workgroup instead of once per frame.  Per frame
+// the arithmetic is stage B's own, statement for statement - operand h1[t] - k from the hT1 ring in the same K order, the
+// eight waves' partial products summed through LDS in wave order, the LayerNorm moments from the frame's 128 partials in the
+// same fixed order (Chan's combine, no raw squares, no atomics), the fold rs (acc - (mu - k) r2) + c2 - so the packed wih2
+// serves both forms.  The next frame's operand is requested before this frame's MFMAs; red / stat alternate between two LDS
+// buffers, so one barrier per frame separates a buffer's writers from its previous readers.
+constexpr int PROJ_BUF = 8 * 32 * 33 + 16 * 32 * 2;   // floats: red [8 waves][32 rows][33], stat [16][32][2]
+__global__ __launch_bounds__(512) void glstm_proj_kernel(const pdse_glstm_desc d, const int t0, const int nf, const int FS) {
+  extern __shared__ __attribute__((aligned(16))) float lds_[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 31, h = lane >> 5;
+  const int slice = blockIdx.x, g = blockIdx.y;
+  const int nbt = d.Bp >> 5;
+  const int fs = blockIdx.z / nbt, bt = blockIdx.z - fs * nbt;
+  const int per = (nf + FS - 1) / FS;
+  const int f0 = fs * per, f1 = min(nf, f0 + per);
+  if (f0 >= f1) return;                                // the whole workgroup
+  const int H = d.H, Bp = d.Bp, G = d.G;
+  const size_t hsz = (size_t)H * Bp;
+  const int R = 2 * d.tc;
+
+  const int q0 = wave * 8;                             // wave w multiplies k-groups 8w .. 8w+7: source group w / 4
+  const size_t srcoff = (size_t)(q0 >> 5) * hsz;
+  const int kq = 32 * g + (q0 & 31);
+  const size_t boff = ((size_t)kq * 2 + h) * Bp + bt * 32 + col;      // in 16-byte units
+  const float4* A4 = reinterpret_cast<const float4*>(d.wih2) + ((size_t)(g * (H / 8) + slice) * (H / 8)) * 64 + lane;
+  float4 av[8], bv[8], bn[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) av[i] = A4[(size_t)(q0 + i) * 64];
+
+  const int uu = (threadIdx.x >> 5) & 7, bb = threadIdx.x & 31;       // epilogue: (unit, item) threads 0 .. 255
+  const int b = bt * 32 + bb;
+  const int hu = slice * 8 + uu;
+  const int p = threadIdx.x >> 5;                                     // statistics: 16 parts of 8 partials
+  const bool fin = threadIdx.x < 256;
+  float r2v[4], c2v[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    r2v[q] = d.r2[(size_t)g * 4 * H + (size_t)q * H + hu];
+    c2v[q] = d.c2[(size_t)g * 4 * H + (size_t)q * H + hu];
+  }
+
+  const float* base = d.hT1 + (size_t)((t0 + f0 + 1) % R) * G * hsz;  // h1[t] sits in slot (t + 1) % R
+  float k0 = base[(size_t)(bt * 32 + col) * 4], k0n = 0.f;
+  {
+    const float4* B4 = reinterpret_cast<const float4*>(base + srcoff) + boff;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bv[i] = B4[(size_t)i * 2 * Bp];
+  }
+  for (int f = f0; f < f1; ++f) {
+    const int t = t0 + f;
+    float* const buf = lds_ + ((f - f0) & 1) * PROJ_BUF;
+    float (*red)[32][33] = reinterpret_cast<float (*)[32][33]>(buf);
+    float (*stat)[32][2] = reinterpret_cast<float (*)[32][2]>(buf + 8 * 32 * 33);
+    const float k0e = base[(size_t)b * 4];
+    const float2* P2 = reinterpret_cast<const float2*>(d.part) + ((size_t)(t % R) * G * (H / 8)) * Bp + b;
+    float2 pv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pv[e] = P2[(size_t)(p * 8 + e) * Bp];
+    if (f + 1 < f1) {                                  // the next frame's operand, in flight behind this frame's MFMAs
+      base = d.hT1 + (size_t)((t + 2) % R) * G * hsz;
+      k0n = base[(size_t)(bt * 32 + col) * 4];
+      const float4* B4 = reinterpret_cast<const float4*>(base + srcoff) + boff;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) bn[i] = B4[(size_t)i * 2 * Bp];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bv[i].x -= k0, bv[i].y -= k0, bv[i].z -= k0, bv[i].w -= k0;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].x, bv[i].x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].y, bv[i].y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].z, bv[i].z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].w, bv[i].w, acc, 0, 0, 0);
+    }
+    {
+      float s1 = 0.f, m2 = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s1 += pv[e].x;
+      const float mp = s1 * (1.0f / 64.0f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float dv = pv[e].x * 0.125f - mp;
+        m2 += pv[e].y + 8.0f * (dv * dv);
+      }
+      stat[p][bb][0] = s1;
+      stat[p][bb][1] = m2;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[wave][(r & 3) + 8 * (r >> 2) + 4 * h][col] = acc[r];
+    __syncthreads();
+    if (fin) {
+      float gate[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) sum += red[w][q * 8 + uu][bb];
+        gate[q] = sum;
+      }
+      double s1 = 0.0;
+#pragma unroll
+      for (int pp = 0; pp < 16; ++pp) s1 += (double)stat[pp][bb][0];
+      const double n = (double)(G * H);
+      const double mu = s1 / n;
+      const float muf = (float)mu;
+      float m2 = 0.f;
+#pragma unroll
+      for (int pp = 0; pp < 16; ++pp) {
+        const float dv = stat[pp][bb][0] * (1.0f / 64.0f) - muf;
+        m2 += stat[pp][bb][1] + 64.0f * (dv * dv);
+      }
+      const double var = (double)m2 / n;
+      const float rs = (float)(1.0 / sqrt(var + (double)d.eps));
+      const float muk = (float)(mu - (double)k0e);
+      float* out = d.gx2 + (((size_t)(t % R) * G + g) * (4 * H)) * Bp;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) out[((size_t)q * H + hu) * Bp + b] = rs * (gate[q] - muk * r2v[q]) + c2v[q];
+    }
+    k0 = k0n;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bv[i] = bn[i];
+  }
+}
+
+// the chunked form's launch sequence (pdse.h): per-step launches of stages A and C, a projection launch behind each chunk's
+// last layer-1 frame.  Launch boundaries on one stream are the only synchronisation.
+static int glstm_chunk_launch(const pdse_glstm_desc* d, hipStream_t s, const int mask) {
+  const int NS = d->slices == 2 ? 2 : 1, TC = d->tc, T = d->T, nbt = d->Bp / 32;
+  const dim3 grid(d->H / 8 / NS, d->G, 2 * nbt), block(512);
+  const size_t lds = (size_t)(8 * 32 * NS * 33 + 16 * 32 * 2 + 4 * 32 * 8 * NS) * sizeof(float);
+  const size_t plds = (size_t)2 * PROJ_BUF * sizeof(float);
+  static unsigned long long attr_wave = 0, attr_proj = 0;
+  if (NS == 2 && pdse_lds_attr((const void*)glstm_wave_kernel<2, true>, &attr_wave, "glstm lds attribute")) return 1;
+  if (pdse_lds_attr((const void*)glstm_proj_kernel, &attr_proj, "glstm projection lds attribute")) return 1;
+  for (int st = 0; st < T + TC + 1; ++st) {
+    if (st > 0 && st <= T && (st % TC == 0 || st == T) && (mask & 2)) {   // frames (st - 1) / TC * TC .. st - 1 are complete
+      const int t0 = (st - 1) / TC * TC, nf = st - t0;
+      const int FS = min(nf, nbt == 1 ? 2 : 1);                            // B <= 32: two workgroups share a chunk's frames (256 in all)
+      hipLaunchKernelGGL(glstm_proj_kernel, dim3(d->H / 8, d->G, nbt * FS), block, plds, s, *d, t0, nf, FS);
+    }
+    if (st >= T && st < d->lag) continue;                                  // T < lag: steps with neither stage
+    if (NS == 2) hipLaunchKernelGGL((glstm_wave_kernel<2, true>), grid, block, lds, s, *d, st, mask);
+    else hipLaunchKernelGGL((glstm_wave_kernel<1, true>), grid, block, lds, s, *d, st, mask);
+  }
+  return pdse_check_launch("glstm");
+}
 
 int pdse_glstm_launch(const pdse_glstm_desc* d, hipStream_t s) {
   if (!d || !d->gx1 || !d->whh1 || !d->wih2 || !d->r2 || !d->c2 || !d->whh2 || !d->hT1 || !d->cst1 || !d->hT2 ||
       !d->cst2 || !d->gx2 || !d->part || !d->y) {
     pdse_set_error("glstm: null pointer");
+    return 1;
+  }
+  if (d->tc < 0 || (d->tc == 0 && d->lag != 0)) {
+    pdse_set_error("glstm: chunked form needs tc >= 1 (tc == 0 and lag == 0: the three-stage wavefront)");
+    return 1;
+  }
+  if (d->tc > 0 && (d->lag != d->tc + 1 || d->tc > 4096)) {
+    pdse_set_error("glstm: lag must be tc + 1 (tc <= 4096)");
     return 1;
   }
   if (d->B <= 0 || d->T <= 0 || d->G != 2 || d->H != 512 || d->Bp % 32 != 0 || d->Bp < d->B || (d->Bp / 32) * 3 > 65535) {
@@ -388,13 +558,14 @@ int pdse_glstm_launch(const pdse_glstm_desc* d, hipStream_t s) {
     pdse_set_error("glstm: slices is 0 / 1 (one slice of 8 units per workgroup) or 2");
     return 1;
   }
+  // PDSE_GLSTM_MASK (diagnostic, tools/time_glstm.py): run only some stages to time them apart - results are then wrong
+  static const int mask = PDSE_DIAG_ENV("PDSE_GLSTM_MASK") ? atoi(PDSE_DIAG_ENV("PDSE_GLSTM_MASK")) : 7;
+  if (d->tc > 0) return glstm_chunk_launch(d, s, mask);
   const int NS = d->slices == 2 ? 2 : 1;
   const dim3 grid(d->H / 8 / NS, d->G, 3 * (d->Bp / 32)), block(512);
   const size_t lds = (size_t)(8 * 32 * NS * 33 + 16 * 32 * 2 + 4 * 32 * 8 * NS) * sizeof(float);
   static unsigned long long attr_mask = 0;
-  if (NS == 2 && pdse_lds_attr((const void*)glstm_wave_kernel<2>, &attr_mask, "glstm lds attribute")) return 1;
-  // PDSE_GLSTM_MASK (diagnostic, tools/time_glstm.py): run only some stages to time them apart - results are then wrong
-  static const int mask = PDSE_DIAG_ENV("PDSE_GLSTM_MASK") ? atoi(PDSE_DIAG_ENV("PDSE_GLSTM_MASK")) : 7;
+  if (NS == 2 && pdse_lds_attr((const void*)glstm_wave_kernel<2, false>, &attr_mask, "glstm lds attribute")) return 1;
   static const bool tracing = PDSE_DIAG_ENV("PDSE_GLSTM_TRACE") != nullptr;
   static long long* tbuf = nullptr;
   const size_t nw = (size_t)grid.x * grid.y * grid.z * 8;
@@ -406,8 +577,8 @@ int pdse_glstm_launch(const pdse_glstm_desc* d, hipStream_t s) {
     (void)hipMemsetAsync(tbuf, 0, nw * 64, s);
   }
   for (int st = 0; st < d->T + 2; ++st) {
-    if (NS == 2) hipLaunchKernelGGL(glstm_wave_kernel<2>, grid, block, lds, s, *d, st, mask);
-    else hipLaunchKernelGGL(glstm_wave_kernel<1>, grid, block, lds, s, *d, st, mask);
+    if (NS == 2) hipLaunchKernelGGL((glstm_wave_kernel<2, false>), grid, block, lds, s, *d, st, mask);
+    else hipLaunchKernelGGL((glstm_wave_kernel<1, false>), grid, block, lds, s, *d, st, mask);
   }
   if (tracing) {   // diagnostic: stamps of wavefront step T/2 - start spread (100 MHz clock) and shader clocks since the wave started
     (void)hipStreamSynchronize(s);

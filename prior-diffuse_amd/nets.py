@@ -1086,6 +1086,12 @@ class GcrnPlan(PlanBase):
                             # GEMM convolution takes (16 channel groups gathering the same tile) - bit-identical, for A/B timing
     persist_lstm = True     # B <= PERSIST_MAX_B and a plan that owns the GPU while it runs: the grouped LSTM as ONE persistent
                             # launch with register-resident weights (pdse_glstmp_desc, csrc/lstmp.hip) instead of T + 2 launches
+    chunk_proj = True       # a plan that is NOT exclusive: the layer-2 input projection out of the per-step launches, evaluated per
+                            # chunk of CHUNK_TC frames (pdse_glstm_desc.tc; T + TC + 1 two-stage steps + ceil(T / TC) projection
+                            # launches).  An exclusive plan keeps the three-stage wavefront: TC more steps lengthen its chain;
+                            # so does a plan of fewer than 2 TC frames.
+                            # On: headline 13.17 against 13.25 ms, lower in every interleaved pair (profiles/glstm_chunk_ab.md)
+    CHUNK_TC = 32
     PERSIST_MAX_B = 4       # measured (tools/time_glstm.py --persist): 3.9 / 6.0 / 9.0 / 21.8 us per step at B = 1 / 2 / 4 / 8 against 11.4-12.0 for the wavefront
     ENC_C = [2, 16, 32, 64, 128, 256]
     ENC_F = [161, 80, 39, 19, 9, 4]
@@ -1106,6 +1112,14 @@ class GcrnPlan(PlanBase):
             self.gemm_planes = int(planes)
         self.persist = bool(self.persist_lstm and self.fused_glstm and exclusive and B <= self.PERSIST_MAX_B and not self.force_generic)
         self.exclusive = bool(exclusive)
+        # ... from T = 2 TC on.  The rings cost 2 TC frames whatever T is (43 MB at Bp = 32, 34 MB of it gx2): most of a short
+        # plan's memory, where a second plan is meant to cost its activations only.  The chain argument points the same way but is
+        # an estimate: per-launch times measured with the plan ALONE on the GPU (9.0 against 13.6 us) put the break-even of
+        # (T + TC + 1 + T / TC) * 9.0 against (T + 2) * 13.6 at T = 62; the plans concerned share the GPU, where it was not measured.
+        # self.chunk is deliberately not part of ns (the weight-bank key): both forms upload the same packed operands
+        # (pack_glstm_wavefront).  A packer of the chunked form's own would have to enter the key.
+        self.chunk = bool(self.chunk_proj and self.fused_glstm and not exclusive and not self.persist and not self.force_generic
+                          and T >= 2 * self.CHUNK_TC)
         super().__init__(ctx, plan, ns=(ctx.bank.token(sd), self.fused_last, self.fused_glstm, self.split_bf16, self.block8, self.persist,
                                         self.gemm_planes))
         self.sd, self.B, self.T = sd, B, T
@@ -1116,7 +1130,8 @@ class GcrnPlan(PlanBase):
         self.out = a(B, 2, T, F0)
         self.e = [a(B, self.ENC_C[i + 1], T, self.ENC_F[i + 1]) for i in range(5)]
         self.gx = a(2, T, 2048, Bp, zero=True)
-        self.hT = a(2, 2, 512, Bp, zero=True)
+        R = 2 * self.CHUNK_TC if self.chunk else 2      # chunked form: hT1, gx2 and part are rings of two chunks of frames
+        self.hT = a(R, 2, 512, Bp, zero=True)
         self.cst = a(2, 512, Bp, zero=True)
         self.y = a(B, T, 1024)
         if self.persist:
@@ -1126,7 +1141,7 @@ class GcrnPlan(PlanBase):
             ctx.keep += [self.gran, self.status]
         elif self.fused_glstm and not self.force_generic:
             self.hT2, self.cst2 = a(2, 2, 512, Bp, zero=True), a(2, 512, Bp, zero=True)
-            self.gx2, self.part = a(2, 2, 2048, Bp, zero=True), a(2, 2, 64, Bp, 2, zero=True)
+            self.gx2, self.part = a(R, 2, 2048, Bp, zero=True), a(R, 2, 64, Bp, 2, zero=True)
         else:
             self.yn = a(B, 1024, T)
         self.glstm = a(B, 256, T, 4)
@@ -1204,6 +1219,8 @@ class GcrnPlan(PlanBase):
         d.y, d.y_sb, d.y_st, d.y_su, d.y_sg = self.y.data_ptr(), T * 1024, 1024, 1, 512     # cat: index g*512 + u
         d.B, d.Bp, d.T, d.H, d.G, d.eps = B, Bp, T, 512, 2, 1e-5
         d.slices = 2 if self.exclusive else 1     # a plan that owns the GPU: two slices per workgroup share one fetch of the state (bit-identical)
+        if self.chunk:                             # same packed operands: the chunk projection walks K in stage B's order
+            d.tc, d.lag = self.CHUNK_TC, self.CHUNK_TC + 1
         self.add(d, TAG_LSTM)
 
     def _glstm_persistent(self, proj1):
