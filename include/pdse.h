@@ -924,6 +924,11 @@ typedef struct pdse_resample_desc {
  *   (pdse_bglu_desc.hp_par).  n = 8 n0 n1 n2 n3, exp = 0 (the planes are scaled already).  Margins, pad frames, the lo plane
  *   and the dump item lie outside the box and are not counted.
  * mode 0 clears all out_rows rows of out (rows may be NULL); mode 1 adds the rows' histograms to out[row.out_row][32].
+ * mode PDSE_RANGE_NONFINITE (2) is the finiteness verdict of a pass: row r is a contiguous fp32 tensor (ptr, 4-byte aligned,
+ *   and n >= 0; every other row field is ignored and may be zero), and out[r][0] grows by the number of its elements that are
+ *   Inf or NaN (exponent field all ones: an integer test).  Bins 1 .. 31 of the row are not written; nrows <= out_rows.  One
+ *   atomic add per workgroup, none where the count is 0.  (Bin 31 of mode 1 also counts finite values from 2^15 up, so it is no
+ *   finiteness test.)
  * The table lives on the device only.  pdse_range_hist and pdse_plan_add read it back once (a synchronous copy: not inside a
  *   stream capture) and validate every row before anything is launched or recorded - null pointers, unknown kind, n < 0,
  *   out_row, alignment; a recorded plan launches without further host work, and the kernel skips a row it cannot make sense of
@@ -931,6 +936,7 @@ typedef struct pdse_resample_desc {
 #define PDSE_RANGE_BINS 32
 #define PDSE_RANGE_F32 0
 #define PDSE_RANGE_F16HI 1
+#define PDSE_RANGE_NONFINITE 2       /* pdse_range_desc.mode */
 typedef struct pdse_range_row {
   const void* ptr;
   int64_t n;                   /* logical elements */

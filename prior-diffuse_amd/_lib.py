@@ -261,6 +261,7 @@ class RangeDesc(C.Structure):
 RANGE_BINS = 32            # PDSE_RANGE_BINS
 RANGE_F32, RANGE_F16HI = 0, 1
 RANGE_CLEAR, RANGE_ACCUMULATE = 0, 1
+RANGE_NONFINITE = 2        # PDSE_RANGE_NONFINITE: out[r][0] += Inf / NaN elements of the fp32 tensor of row r
 # The bin map of csrc/range.hip, decided there once: RANGE_BINADE[bin] is the exponent E of the bin's lower edge 2^E in scaled
 # units.  Bin 0 counts zeros (None); bin 1 everything non-zero below 2^-14 (-inf: hi is an fp16 subnormal); bins 2 .. 30 one
 # normal fp16 binade each, E = -14 .. 14; bin 31 starts at 2^15 and also takes infinities and NaN.

@@ -21,6 +21,15 @@
 // to global memory with atomicAdd on unsigned: integer counts, so the result does not depend on the order.
 // Streaming side: 16-byte loads (four fp32 or eight fp16 per lane), grid-stride over the row, a scalar tail for n % 4.
 // No scratch, no inline assembly.
+//
+// PDSE_RANGE_NONFINITE (mode 2) is the finiteness verdict of a pass, not a histogram: bin 31 above counts every value from 2^15
+// up together with Inf and NaN, so it cannot say whether a result is finite.  Row r of the table is an fp32 tensor (ptr, n; the
+// other row fields are not read); out[r][0] grows by the number of its elements whose exponent field is all ones, found by an
+// integer test on the bit pattern.  ptr is only 4-byte aligned: the elements up to the first 16-byte boundary and the n % 4
+// behind the last whole vector are read one by one by workgroup 0, everything between with 16-byte loads, grid-stride.  A lane
+// keeps its count in a register; the counts are summed within the wave by shuffles, across the workgroup's waves through LDS,
+// and one thread adds the total with ONE atomicAdd - none when it is 0, so a clean pass does no atomics.  Bins 1 .. 31 are
+// not written.  An integer count: independent of scheduling.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -135,17 +144,66 @@ __global__ __launch_bounds__(RH_THREADS) void range_hist_kernel(const pdse_range
   }
 }
 
+// mode 0: zero the n counters of a table
+__global__ __launch_bounds__(RH_THREADS) void range_clear_kernel(uint32_t* out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * RH_THREADS + threadIdx.x;
+  if (i < n) out[i] = 0u;
+}
+
+// 1 when the fp32 bit pattern is an infinity or a NaN (exponent field all ones), else 0
+__device__ __forceinline__ unsigned nonfinite_f32(uint32_t u) { return (u & 0x7f800000u) == 0x7f800000u ? 1u : 0u; }
+
+__global__ __launch_bounds__(RH_THREADS) void range_nonfinite_kernel(const pdse_range_desc d) {
+  __shared__ unsigned part[RH_WAVES];
+  const int row = (int)blockIdx.y;
+  if (row >= d.out_rows) return;                                                   // uniform over the workgroup, like all returns below
+  const pdse_range_row r = d.rows[row];
+  // rows were validated when the op was recorded or launched directly; a table overwritten since then is skipped, never followed
+  if (r.ptr == nullptr || r.n <= 0 || (reinterpret_cast<uintptr_t>(r.ptr) & 3u) != 0) return;
+  const uint32_t* const p = static_cast<const uint32_t*>(r.ptr);
+  const int tid = threadIdx.x;
+  int64_t head = (int64_t)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2);   // 0 .. 3 elements before the boundary
+  if (head > r.n) head = r.n;
+  const int64_t nvec = (r.n - head) >> 2;
+  const int tail = (int)((r.n - head) & 3);
+  const int64_t first = (int64_t)blockIdx.x * RH_THREADS;
+  const int64_t stride = (int64_t)gridDim.x * RH_THREADS;
+  if (blockIdx.x != 0 && first >= nvec) return;
+
+  unsigned c = 0;
+  const uint4* const p4 = reinterpret_cast<const uint4*>(p + head);                // 16-byte aligned by the choice of head
+  for (int64_t v = first + tid; v < nvec; v += stride) {
+    const uint4 q = p4[v];
+    c += nonfinite_f32(q.x) + nonfinite_f32(q.y) + nonfinite_f32(q.z) + nonfinite_f32(q.w);
+  }
+  if (blockIdx.x == 0) {   // the scalar ends: head on the first lanes of wave 0, tail on the first lanes of wave 1
+    if (tid < (int)head) c += nonfinite_f32(p[tid]);
+    if (tid >= 64 && tid - 64 < tail) c += nonfinite_f32(p[head + 4 * nvec + (tid - 64)]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+  if ((tid & 63) == 0) part[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned sum = 0;
+#pragma unroll
+    for (int w = 0; w < RH_WAVES; ++w) sum += part[w];
+    if (sum) atomicAdd(d.out + (int64_t)row * RH_BINS, sum);
+  }
+}
+
 }  // namespace
 
 // the descriptor's own fields (no device access)
 static int range_check_desc(const pdse_range_desc* d) {
   REQ(d && d->out, "range: null descriptor or output");
-  REQ(d->mode == 0 || d->mode == 1, "range: mode must be 0 (clear) or 1 (accumulate)");
+  REQ(d->mode == 0 || d->mode == 1 || d->mode == PDSE_RANGE_NONFINITE, "range: mode must be 0 (clear), 1 (accumulate) or 2 (non-finite count)");
   REQ(d->out_rows >= 1, "range: out_rows < 1");
   if (d->mode == 0) return 0;
   REQ(d->rows, "range: null row table");
   REQ(d->nrows >= 1 && d->nrows <= 65535, "range: zero rows (or more than 65535)");
   REQ(d->blocks >= 1 && d->blocks <= 65535, "range: blocks must be 1 .. 65535");
+  if (d->mode == PDSE_RANGE_NONFINITE) REQ(d->nrows <= d->out_rows, "range: more rows than the output table has (non-finite count: row r adds to out[r][0])");
   return 0;
 }
 
@@ -157,6 +215,11 @@ int pdse_range_validate(const pdse_range_desc* d) {
   if (pdse_check_hip(hipMemcpy(rows.data(), d->rows, rows.size() * sizeof(pdse_range_row), hipMemcpyDeviceToHost), "range: reading the row table")) return 1;
   for (const pdse_range_row& r : rows) {
     REQ(r.ptr, "range: null tensor pointer in a row");
+    if (d->mode == PDSE_RANGE_NONFINITE) {   // an fp32 tensor (ptr, n): nothing else of the row is read
+      REQ(r.n >= 0, "range: n < 0");
+      REQ((reinterpret_cast<uintptr_t>(r.ptr) & 3u) == 0, "range: fp32 tensor not aligned to 4 bytes");
+      continue;
+    }
     REQ(r.kind == PDSE_RANGE_F32 || r.kind == PDSE_RANGE_F16HI, "range: unknown element kind");
     REQ(r.n >= 0, "range: n < 0");
     REQ(r.out_row >= 0 && r.out_row < d->out_rows, "range: out_row outside the output table");
@@ -178,8 +241,17 @@ int pdse_range_validate(const pdse_range_desc* d) {
 
 int pdse_range_launch(const pdse_range_desc* d, hipStream_t s) {
   if (range_check_desc(d)) return 1;
-  if (d->mode == 0)   // clear: every counter of the table, no tensor is read
-    return pdse_check_hip(hipMemsetAsync(d->out, 0, (size_t)d->out_rows * RH_BINS * sizeof(uint32_t), s), "range: clear");
+  if (d->mode == 0) {   // clear: every counter of the table, no tensor is read
+    // A kernel, not hipMemsetAsync: a memset node in a captured graph was seen to fill its table with other data once a second
+    // graph that holds memset nodes had been launched in the process; kernel nodes replay as recorded.
+    const int64_t n = (int64_t)d->out_rows * RH_BINS;
+    hipLaunchKernelGGL(range_clear_kernel, dim3((unsigned)((n + RH_THREADS - 1) / RH_THREADS)), dim3(RH_THREADS), 0, s, d->out, n);
+    return pdse_check_launch("range: clear");
+  }
+  if (d->mode == PDSE_RANGE_NONFINITE) {
+    hipLaunchKernelGGL(range_nonfinite_kernel, dim3((unsigned)d->blocks, (unsigned)d->nrows), dim3(RH_THREADS), 0, s, *d);
+    return pdse_check_launch("range");
+  }
   hipLaunchKernelGGL(range_hist_kernel, dim3((unsigned)d->blocks, (unsigned)d->nrows), dim3(RH_THREADS), 0, s, *d);
   return pdse_check_launch("range");
 }

@@ -43,6 +43,10 @@ def parse_args_and_config(argv=None):
     p.add_argument("--batch", type=int, default=1,
                    help="(not a flag of the reference) --generate: enhance this many files per pass as exact ragged batches - every file's "
                         "result and noise are those of the one-file loop (priors GCRN and DiffUNet); default 1: one file per pass")
+    p.add_argument("--inflight", type=int, default=1,
+                   help="(not a flag of the reference) --generate: keep this many files (2 .. 4) in flight on HIP streams of their own, each "
+                        "verified on the device without a device-wide synchronisation (ComplexDDPMTrainer.enhance_stream); same files, "
+                        "same noise; not with --batch or --audit-range; default 1: one file at a time")
     args = p.parse_args(argv)
     args.log = os.path.join(args.assets, "log", args.doc)
     args.checkpoint = os.path.join(args.assets, "checkpoint", args.doc)
@@ -71,7 +75,7 @@ def main(argv=None):
         raise NotImplementedError("only ComplexDDPMTrainer's sampling path is built")
     trainer = ComplexDDPMTrainer(args, config)
     if args.generate:
-        return trainer.generate_wav(load_pre_train=True, data_path=args.data, batch=args.batch)
+        return trainer.generate_wav(load_pre_train=True, data_path=args.data, batch=args.batch, inflight=args.inflight)
     trainer.train_ddpm()
 
 

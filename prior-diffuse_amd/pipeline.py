@@ -60,7 +60,8 @@ class SamplerPipeline:
 
     def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, T=None, L_=None, fast_sampling=True,
                  use_sigma=False, params=default_params, with_signal=None, deltamu=False, cond="init", bank=None,
-                 split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False, ragged=False):
+                 split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False, ragged=False,
+                 verdict=False):
         """deltamu: the alternative parameterisation of utils/params.py:36 — ddpm_sd is a ``Nocon`` state_dict,
         x_T = noise + X_init/11 (:947-948), eps = Nocon(x, t) (:970-971), no final ``+ X_init`` (:995).
         cond (deltamu False): what conditions DiffUNet1 — "init": X_init/11 (pirorgrad, :967-969, + X_init at the end,
@@ -106,7 +107,15 @@ class SamplerPipeline:
         tables (``lens``, ``frames_tab``, ``valid_tab``: device int32, written by a copy before each pass, so a replayed
         hipGraph sees new lengths).  Everything else on the path is per-frame or looks back in time only.  The
         DB-AIAT priors attend and run a bidirectional GRU over all of T: ValueError.  False (default): every table is NULL and
-        the plan is launch for launch today's."""
+        the plan is launch for launch today's.
+        verdict: record the finiteness verdict of a pass with the plan (csrc/range.hip, PDSE_RANGE_NONFINITE): the plan owns
+        ``verdict_tab`` (int32 [rows][32], one row per judged tensor: ``spec``, and ``istft.wav`` with the signal back end), clears
+        it in its first launch and ends with one launch that counts the Inf / NaN elements of those tensors into column 0 of
+        their rows.  Both are ordinary descriptors (marked range "verdict" holds the count), so a hipGraph replay judges its
+        own pass.  ``verdict_fetch(stream)`` copies the table to pinned host memory without synchronising and
+        ``verdict_counts()`` reads it once an event recorded behind the copy has fired: what ``check()`` learns from a
+        reduction over the spectrogram and a device-wide synchronisation, per pass and per stream.  Plan files do not carry it
+        (``planfile.save_pipeline`` raises ValueError).  False (default): the plan is launch for launch today's."""
         if L_ is not None:
             T = 1 + L_ // 160
         if with_signal is None:
@@ -206,21 +215,35 @@ class SamplerPipeline:
             ctx.keep.append(self.range_hist)
         self._range_clear = None      # index of the clear launch in the plan
         self._ranges_run = set()      # marked ranges the last run() executed (range_report() reports those)
+        self.verdict = bool(verdict)
+        self.verdict_tab = self._verdict_host = None
+        self._verdict_clear = self._verdict_count = None      # indices of the verdict's two launches in the plan
+        if self.verdict:
+            # one row per judged tensor, cleared by the same launch the audit clears its histograms with (mode 0 of the operator)
+            self.verdict_tab = torch.zeros(2 if with_signal else 1, L.RANGE_BINS, dtype=torch.int32, device=self.device)
+            ctx.keep.append(self.verdict_tab)
+            if self.device.type == "cuda":
+                self._verdict_host = torch.zeros(self.verdict_tab.shape, dtype=torch.int32).pin_memory()
 
-        def range_launch(mode, rows=None):
+        def range_launch(mode, rows=None, tab=None):
+            tab = self.range_hist if tab is None else tab
             d = L.RangeDesc()
-            d.out, d.out_rows, d.mode, d.blocks = self.range_hist.data_ptr(), self.range_hist.shape[0], mode, 1
+            d.out, d.out_rows, d.mode, d.blocks = tab.data_ptr(), tab.shape[0], mode, 1
             if rows:
                 dev = ctx.up(rangeaudit.table_of(rows), np.uint8)
                 d.rows, d.nrows, d.blocks = dev.data_ptr(), len(rows), rangeaudit.work_blocks(rows)
+            elif tab is self.verdict_tab:
+                self._verdict_clear = len(self.descs)
             else:
                 self._range_clear = len(self.descs)
             self.eps.add(d, nets.TAG_NONE)
 
         def mark(name, fn):
             b = len(self.descs)
+            if self.verdict and not self.ranges:
+                range_launch(L.RANGE_CLEAR, tab=self.verdict_tab)   # first launch of the plan
             if self.audited and not self.ranges:
-                range_launch(L.RANGE_CLEAR)                     # first launch of the plan
+                range_launch(L.RANGE_CLEAR)                     # first launch of the plan (behind the verdict's clear, if any)
             fn()
             if self.audited and (name == "prior" or name.startswith("step")):
                 rows = []
@@ -288,6 +311,17 @@ class SamplerPipeline:
             mark("step%d" % nstep, one)
         if with_signal:
             mark("istft", lambda: self.istft.build(spec=self.spec, c=self.stft.c))
+        if self.verdict:
+            def count():
+                rows = []
+                for t in (self.spec,) + ((self.istft.wav,) if with_signal else ()):
+                    r = L.RangeRow()                               # an fp32 tensor: pointer and length, nothing else is read
+                    r.ptr, r.n = t.data_ptr(), t.numel()
+                    rows.append(r)
+                self._verdict_count = len(self.descs)
+                range_launch(L.RANGE_NONFINITE, rows, tab=self.verdict_tab)
+
+            mark("verdict", count)                                 # last launch of the plan
         if self.plan is not None:
             self.plan.keep(ctx.keep, ctx.bank)
         self._graph_stream = None
@@ -316,7 +350,11 @@ class SamplerPipeline:
         if self.audited and not b <= self._range_clear < e:
             c = self._range_clear                              # a call that starts later still starts from a cleared table
             self.plan.run_range(c, c + 1, self._stream())
+        if self.verdict and not b <= self._verdict_clear < e:
+            self.plan.run_range(self._verdict_clear, self._verdict_clear + 1, self._stream())
         self.plan.run_range(b, e, self._stream())
+        if self.verdict and not b <= self._verdict_count < e:  # a call that ends earlier is judged too: the buffers as it left them
+            self.plan.run_range(self._verdict_count, self._verdict_count + 1, self._stream())
         self._ranges_run = {k for k, (rb, re_) in self.ranges.items() if b <= rb and re_ <= e}
 
     def range_report(self):
@@ -341,6 +379,38 @@ class SamplerPipeline:
         return rangeaudit.RangeReport(rangeaudit.ReportRow(tname, rname, hist[i]) for i, (rname, tname) in enumerate(self.range_rows)
                                       if rname in self._ranges_run)
 
+    def verdict_fetch(self, stream=None):
+        """Enqueue, on ``stream`` (a ``torch.cuda.Stream``; None: the current one), the copy of the verdict table of the pass
+        that stream ran last into the pinned host buffer this pipeline owns.  Asynchronous: nothing is synchronised."""
+        if not self.verdict:
+            raise ValueError("the pipeline was built without the verdict (SamplerPipeline(verdict=True))")
+        if self.plan is None:
+            raise L.PdseError("SamplerPipeline built on a CPU context cannot run: there is no CPU fallback")
+        with torch.cuda.stream(torch.cuda.current_stream(self.device) if stream is None else stream):
+            self._verdict_host.copy_(self.verdict_tab, non_blocking=True)
+
+    def verdict_counts(self):
+        """The Inf / NaN counts the last ``verdict_fetch`` brought to the host, as Python ints: (spec,), or (spec, wav) with the
+        signal back end.  The caller has waited for an event recorded on the fetch's stream behind it (or synchronised);
+        nothing is synchronised here.  All zero: the pass's results are finite."""
+        if not self.verdict:
+            raise ValueError("the pipeline was built without the verdict (SamplerPipeline(verdict=True))")
+        if self._verdict_host is None:
+            raise L.PdseError("SamplerPipeline built on a CPU context cannot run: there is no CPU fallback")
+        return tuple(int(v) & 0xffffffff for v in self._verdict_host[:, 0].tolist())
+
+    @property
+    def windowed(self):
+        """True where the pass multiplies f16x2 operands: the arithmetic with an fp16 window, which a pass can leave."""
+        return self.split == "f16x2" and bool(self.split_bf16) and self.dtype == "f32"
+
+    @staticmethod
+    def nonfinite_error(where=""):
+        """The ``PdseRangeError`` of an f16x2 pass whose result is not finite (``check()``, and a non-zero verdict)."""
+        return L.PdseRangeError("non-finite values in the enhanced spectrogram of an f16x2 pass%s: an activation beyond +-%g left the fp16 "
+                                "window (include/pdse.h: PDSE_F16_ACT_EXP), or the input was not finite; build the pipeline with "
+                                "split='bf16x3' (ComplexDDPMTrainer does so for this geometry by itself)" % (where, 65504.0 / 2 ** packing.F16_ACT_EXP))
+
     def check(self, audit=False):
         """Synchronises and raises if a persistent launch of the last run gave up (its workgroups wait for each other
         with bounded polls: another workload on the GPU can keep them from all being resident), or - f16x2 passes - if the
@@ -362,9 +432,7 @@ class SamplerPipeline:
                 top = self.range_report().above()
                 if top:
                     where = " (range audit: first in %s of %s)" % (top[0].name, top[0].range)
-            raise L.PdseRangeError("non-finite values in the enhanced spectrogram of an f16x2 pass%s: an activation beyond +-%g left the fp16 "
-                                   "window (include/pdse.h: PDSE_F16_ACT_EXP), or the input was not finite; build the pipeline with "
-                                   "split='bf16x3' (ComplexDDPMTrainer does so for this geometry by itself)" % (where, 65504.0 / 2 ** packing.F16_ACT_EXP))
+            raise self.nonfinite_error(where)
         if audit:
             low = self.range_report().below()
             if low:

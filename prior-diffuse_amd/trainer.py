@@ -16,7 +16,7 @@ Deliberate differences from the reference, all recorded in SURVEY.md §0/§2:
 import glob
 import logging
 import os
-from collections import OrderedDict
+from collections import OrderedDict, deque, namedtuple
 from copy import deepcopy
 
 import numpy as np
@@ -25,8 +25,26 @@ import torch
 from . import _lib as L
 from . import nets, ops, raggedplan, wavdev, wavio
 from .params import PRIOR_SCALE_C, params as default_params
-from .pipeline import SamplerPipeline, ragged_args
+from .pipeline import SamplerPipeline, _expect, ragged_args
 from .schedule import inference_schedule as _inference_schedule
+
+
+# one item of ``enhance_stream`` in flight: the event behind its pass, clones and verdict copy; what a repeat needs
+_Job = namedtuple("_Job", "event pipe key wav x_T out")
+
+
+class _Slot:
+    """One slot of ``enhance_stream``: a HIP stream and the recorded geometries it keeps ((geometry, split) -> pipeline, LRU)."""
+
+    def __init__(self, stream):
+        self.stream, self.pipes, self.hits = stream, OrderedDict(), {}
+
+
+def _inflight_arg(inflight):
+    inflight = int(inflight)
+    if not 1 <= inflight <= 4:
+        raise ValueError("inflight must be 1 .. 4 (a process has four hardware queues), got %d" % inflight)
+    return inflight
 
 
 class ComplexDDPMTrainer(object):
@@ -107,6 +125,8 @@ class ComplexDDPMTrainer(object):
         self.model_ddpm = (ops.NoconOp if self.deltamu else ops.DiffUNet1Op)(self.ddpm_sd, self.device, bank=self.bank, exclusive=self.exclusive)   # :70-73
         self._pipes = OrderedDict()
         self._hits = {}                   # uses of a recorded geometry after the first
+        self._slots = []                  # enhance_stream: one stream and a few recorded geometries per item in flight
+        self._streaming = False
 
     # ---- A8 checkpoint rules (:91-97, :906-913) ---------------------------
     def _load_checkpoint(self):
@@ -123,6 +143,7 @@ class ComplexDDPMTrainer(object):
             self._hits.clear()
             self._range_fallback.clear()
             self._audit_clean.clear()
+            self._slots = []
             self.bank = nets.WeightBank()
             self.model = ops.PRIOR_OPS[self.prior_name](self.prior_sd, self.device, bank=self.bank, exclusive=self.exclusive)
             self.model_ddpm = (ops.NoconOp if self.deltamu else ops.DiffUNet1Op)(self.ddpm_sd, self.device, bank=self.bank, exclusive=self.exclusive)
@@ -178,8 +199,160 @@ class ComplexDDPMTrainer(object):
             pipe.check()
         return res
 
+    # ---- utterances in flight -------------------------------------------------
+    STREAM_PLANS = 2   # recorded geometries every slot of ``enhance_stream`` keeps alive (least recently used first out; <= MAX_PLANS)
+
+    def enhance_stream(self, items, inflight=3):
+        """A stream of independent items, ``inflight`` of them on the GPU at a time; a generator of ``(wav_out [B, L], spec
+        [B, 2, T, 161])``, one pair per item, in the order of the items.  items: an iterable of ``wav`` or ``(wav, x_T)``; wav
+        [B, L] or 1-D (B = 1), any scale, as for ``enhance``; x_T None or [B, 2, 1 + L // 160, 161].  The iterable is consumed
+        as slots come free, at most ``inflight`` items ahead of the one handed out.
+
+        Item i runs start to end on slot ``i % inflight`` (the ``by_batch`` form of ``PipelinedSampler``).  A slot is one HIP
+        stream and a cache of ``STREAM_PLANS`` = 2 recorded geometries, least recently used first out, built with this
+        trainer's weights (``bank``), ``split`` and ``dtype``, with ``verdict=True`` and with ``exclusive=False``: the items in
+        flight share the GPU, so no launch may wait for its own workgroups.  Memory is therefore bounded by ``inflight`` x 2
+        activation sets beside the trainer's own ``MAX_PLANS``; the slots live as long as the trainer (or its weights), so a
+        second stream of the same lengths re-records nothing.  ``1 <= inflight <= 4`` (a process has four hardware queues),
+        else ValueError.  A geometry a slot meets again is replayed from its hipGraph, one seen once runs launch by launch -
+        ``enhance``'s rule.
+
+        x_T None is drawn on the caller's stream at submission, in item order: the generator sees the draws of the
+        one-at-a-time loop.  A slot's results are cloned on the slot's stream ahead of its event, so what is handed out is never
+        overwritten by a later item.
+
+        Verification costs no device-wide synchronisation: the plan ends with the finiteness verdict of its own pass
+        (``SamplerPipeline(verdict=True)``), the counters travel to pinned host memory behind the pass, and before item i is
+        handed out the host waits for item i's event only.  Counts of zero: the item is handed out.  Otherwise (an activation
+        left the f16x2 window, or the input was not finite) every submitted item is waited for, ``_checked``'s warning is logged,
+        the geometry joins ``_range_fallback``, and THAT item is repeated through ``_checked`` on a "bf16x3" plan, synchronously
+        and with the same x_T, and handed out in its place; items already in flight keep their own verdicts, later items of the
+        geometry are built on "bf16x3".  Where the arithmetic has no window to leave (split "bf16x3", dtype "bf16", the exact fp32
+        of the full schedule) a non-zero count raises ``PdseRangeError`` from the generator at that item.
+
+        Closing the generator early (``close()``, garbage collection, an exception in the consumer) waits for the slots' events.
+        One stream per trainer at a time (RuntimeError), and on a trainer with ``exclusive=True`` no other entry point between
+        two items: its own plans assume the GPU to themselves.  ``audit=True`` trainers: ValueError (the audit reads a report
+        per pass).  All four priors; nothing here is ragged.
+
+        Every item's tensors equal, bit for bit, what ``ComplexDDPMTrainer(..., exclusive=False).enhance(wav, x_T)`` and its
+        plan's spectrogram give: the kernels the in-flight plans take do not depend on the batch size.  The default trainer
+        (``exclusive=True``) takes the persistent LSTM at B <= 4 in ``enhance``, which is 1e-5 from these kernels and not
+        bit-identical to them.  (Measured limit, DESIGN.md 4.9: at T = 401 three B = 1 graph replays sharing the GPU differed from
+        the sequential pass in a few of 192 passes, with and without the verdict; the tests hold T <= 21 to ``torch.equal``.)"""
+        inflight = _inflight_arg(inflight)
+        if self.audit:
+            raise ValueError("enhance_stream on a trainer built with audit=True: the range audit reads a report per pass")
+        return self._enhance_stream(items, inflight)
+
+    def _stream_slots(self, inflight):
+        slots = getattr(self, "_slots", None)
+        if slots is None:
+            slots = self._slots = []
+        while len(slots) < inflight:
+            slots.append(_Slot(torch.cuda.Stream(self.device)))
+        return slots[:inflight]
+
+    def _enhance_stream(self, items, inflight):
+        if getattr(self, "_streaming", False):
+            raise RuntimeError("enhance_stream: this trainer already has a stream open (its slots are in use)")
+        self._streaming = True
+        pending = deque()
+        try:
+            slots = self._stream_slots(inflight)
+            it, n, more = iter(items), 0, True
+
+            def refill():
+                nonlocal n, more
+                while more and len(pending) < inflight:
+                    try:
+                        item = next(it)
+                    except StopIteration:
+                        more = False
+                        return
+                    pending.append(self._stream_submit(slots[n % inflight], item))
+                    n += 1
+
+            while True:
+                refill()
+                if not pending:
+                    return
+                res = self._stream_collect(pending.popleft(), pending)
+                refill()                       # the slot is free: it gets the next item before the consumer gets this one
+                yield res
+        finally:
+            for job in pending:                # closed early, or an exception: the slots' buffers are not reused before their work is done
+                job.event.synchronize()
+            self._streaming = False
+
+    def _stream_submit(self, slot, item):
+        """Enqueue one item on a slot (whose previous item has been collected: its stream is idle); returns the job."""
+        wav, x_T = item if isinstance(item, (tuple, list)) else (item, None)
+        wav = torch.as_tensor(wav).to(self.device, torch.float32)
+        if wav.dim() == 1:
+            wav = wav[None]
+        B, L_ = wav.shape
+        cur = torch.cuda.current_stream(self.device)
+        x_T = self._x_T((B, 2, 1 + L_ // 160, 161), x_T)          # :947-950: the caller's stream, item order
+        key = (B, None, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling))      # _pipe's key of the geometry
+        split = "bf16x3" if key in self._range_fallback else (self.split or SamplerPipeline.default_split)
+        pipe = slot.pipes.get((key, split))
+        slot.hits[(key, split)] = slot.hits.get((key, split), 0) + 1 if pipe is not None else 0
+        if pipe is None:
+            while len(slot.pipes) >= self.STREAM_PLANS:
+                slot.pipes.popitem(last=False)
+            pipe = slot.pipes[(key, split)] = SamplerPipeline(
+                self.device, self.prior_name, self.prior_sd, self.ddpm_sd, B, L_=L_, fast_sampling=self.params.fast_sampling,
+                use_sigma=key[3], params=self.params, deltamu=self.deltamu, cond=self.cond, bank=self.bank,
+                xT_plus_init=self.xT_plus_init, exclusive=False, dtype=self.dtype, split=split, verdict=True)
+        else:
+            slot.pipes.move_to_end((key, split))
+        _expect(x_T, pipe.xT_in, "x_T")
+        ready = torch.cuda.Event()
+        ready.record(cur)                                          # behind the draw, the upload of the inputs and the recording of a new plan
+        st = slot.stream
+        with torch.cuda.stream(st):
+            st.wait_event(ready)
+            for src in (wav, x_T):                                 # allocated on the caller's stream: tell the caching allocator
+                src.record_stream(st)                              # this stream still reads them
+            pipe.stft.wav.copy_(wav, non_blocking=True)
+            pipe.xT_in.copy_(x_T, non_blocking=True)
+            pipe.stft.lens.fill_(L_)
+            if slot.hits[(key, split)] >= 1:                       # met again: one host call instead of ~770 launches
+                if not pipe.plan.has_graph:
+                    pipe.plan.build_graph(st.cuda_stream)
+                pipe.plan.launch_graph(st.cuda_stream)
+            else:
+                pipe.plan.run_range(0, len(pipe.descs), st.cuda_stream)
+            out = (pipe.istft.wav.clone(), pipe.spec.clone())      # ahead of the event: a later item of the slot cannot overwrite them
+            pipe.verdict_fetch(st)
+            event = torch.cuda.Event()
+            event.record(st)
+        return _Job(event, pipe, key, wav, x_T, out)
+
+    def _stream_collect(self, job, pending):
+        """Wait for one item's own event, read its verdict, and return its result - or that of its repeat on "bf16x3"."""
+        job.event.synchronize()
+        if not any(job.pipe.verdict_counts()):
+            cur = torch.cuda.current_stream(self.device)
+            for t in job.out:                                      # allocated on the slot's stream, read on the caller's from here on
+                t.record_stream(cur)
+            return job.out
+        err = SamplerPipeline.nonfinite_error()
+        if not job.pipe.windowed:
+            raise err
+        for other in pending:                                      # the repeat may take launches that want the GPU to themselves
+            other.event.synchronize()
+        logging.warning("%s - repeating this geometry with split='bf16x3'", err)
+        self._range_fallback.add(job.key)
+        self._pipes.pop(job.key, None)                             # f16x2 plans of the geometry: not used again
+        for slot in self._slots:
+            slot.pipes.pop((job.key, job.pipe.split), None)
+        run = lambda pipe: pipe.enhance(job.wav, job.x_T, graph=self._hits.get(next(reversed(self._pipes)), 0) >= 1)   # noqa: E731
+        return self._checked(run, B=job.wav.shape[0], L_=job.wav.shape[1])
+
     def _x_T(self, shape, x_T):
-        if x_T is None:                                               # :947-950 randn_like(init)
+        if x_T is None:                                            # :947-950 randn_like(init)
             return torch.randn(*shape, device=self.device, dtype=torch.float32)
         return x_T.to(self.device)
 
@@ -291,7 +464,7 @@ class ComplexDDPMTrainer(object):
         return enhanced, scores
 
     # ---- A2..A7: the reference's entry point --------------------------------
-    def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True, batch=1):
+    def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True, batch=1, inflight=1):
         """Per-file B=1 enhancement of ``data_path/*.wav`` into ``args.generated_wav``
         (:903-1018).  Returns the list of written paths instead of calling exit().
 
@@ -307,12 +480,24 @@ class ComplexDDPMTrainer(object):
         file, which keeps a seeded ``--generate`` run on the reference's generator stream file for file.
         Files that cannot be read (unsupported encoding) are logged and skipped instead of aborting the run.
         A file's PCM frames are decoded, mixed to mono and converted to 16 kHz on the device (``wavdev.load``); the waveform
-        is ``wavio.read_wav``'s bit for bit, so the written files do not depend on which of the two produced it."""
+        is ``wavio.read_wav``'s bit for bit, so the written files do not depend on which of the two produced it.
+
+        inflight (default 1: the loop below, untouched): N = 2 .. 4 with ``batch`` 1 sends the same loop through
+        ``enhance_stream(inflight=N)``: files are read and decoded as here, every file's x_T is drawn in path order and followed
+        at once by its ``rng_fidelity`` discards - the generator ends where this loop leaves it - unreadable files are skipped
+        with the same warning, and the same 16-bit files are written under the same names; every file is verified by its plan's
+        own verdict instead of a synchronisation per file.  The bits are those of an ``exclusive=False`` trainer (see
+        ``enhance_stream``).  With ``batch`` > 1: ValueError (streams of ragged windows are not built)."""
+        inflight = _inflight_arg(inflight)
+        if inflight > 1 and int(batch) > 1:
+            raise ValueError("generate_wav: inflight > 1 runs one file per pass (batch=1); streams of ragged windows are not built")
         if load_pre_train and getattr(self.args, "retrain", False):
             self._load_checkpoint()
         os.makedirs(self.args.generated_wav, exist_ok=True)
         if int(batch) > 1:
             return self._generate_wav_batched(data_path, rng_fidelity, int(batch))
+        if inflight > 1:
+            return self._generate_wav_stream(data_path, rng_fidelity, inflight)
         written = []
         with torch.no_grad():
             for path in sorted(glob.glob(data_path + "/*.wav")):
@@ -330,6 +515,33 @@ class ComplexDDPMTrainer(object):
                         torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
                 dst = os.path.join(self.args.generated_wav, path.split("/")[-1])
                 wavio.write_wav(dst, out, 16000)
+                written.append(dst)
+        print("success!")
+        return written
+
+    def _generate_wav_stream(self, data_path, rng_fidelity, inflight):
+        ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0
+        read = []                                    # paths of the items handed to the stream, in order
+
+        def files():
+            for path in sorted(glob.glob(data_path + "/*.wav")):
+                try:
+                    wav = wavdev.load([path], self.device, 16000)[0]            # [1, L] on the device, read_wav's bits
+                except (ValueError, EOFError, wavio.wave.Error) as e:
+                    logging.warning("skipping %s: %s", path, e)
+                    continue
+                shape = (1, 2, 1 + wav.shape[1] // 160, 161)
+                x_T = self._x_T(shape, None)                                  # :947-950 randn_like(init), path order
+                for _ in range(ndiscard):
+                    torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
+                read.append(path)
+                yield wav, x_T
+
+        written = []
+        with torch.no_grad():
+            for k, (out, _) in enumerate(self.enhance_stream(files(), inflight=inflight)):
+                dst = os.path.join(self.args.generated_wav, read[k].split("/")[-1])
+                wavio.write_wav(dst, out[0].cpu().numpy(), 16000)
                 written.append(dst)
         print("success!")
         return written
