@@ -489,6 +489,11 @@ typedef struct pdse_attn_desc {
   const float* qkv;
   float* out; /* [B,E,T,F] */
   int32_t B, T, F, E, heads, axis, pad0_, pad1_;
+  /* exact ragged batches: seqlen[b] (device int32 [B], NULL: the whole axis) own sequence length of item b, clamped to
+   * 0 .. S.  Every line of item b attends over keys [0, seqlen[b]) only, staged and walked in the chunks the launcher picks
+   * for S - the roundings are those of a launch with S = seqlen[b]; queries at positions >= seqlen[b] STORE ZEROS (stored,
+   * not skipped: `out` outlives a pass). */
+  const int32_t* seqlen;
 } pdse_attn_desc;
 
 /* Bidirectional single-layer GRU (dbaiat.py:45,83) along one axis, hidden H = 64 or 128, persistent per
@@ -511,6 +516,11 @@ typedef struct pdse_gru_desc {
   const float* x;
   const float* wih;
   const float* bih;
+  /* exact ragged batches (axis 1: the sequence runs over the outer axis T): seqlen[b] (device int32 [B], NULL: T) own
+   * sequence length of item b, clamped to 0 .. T.  A line of item b is advanced at positions < seqlen[b] only: the backward
+   * direction keeps h = 0 until position seqlen[b] - 1, so both directions are those of a launch with T = seqlen[b]; y is
+   * STORED AS ZEROS at positions >= seqlen[b].  Refused with axis 0. */
+  const int32_t* seqlen;
 } pdse_gru_desc;
 
 /* Swap the two inner axes of [N][R][Cc] -> [N][Cc][R] (fp32) through 32x32 LDS tiles: converts between the
@@ -654,6 +664,13 @@ typedef struct pdse_gncomb_desc {
   int32_t B, C;
   float k1, k2, eps;
   int32_t pad_;
+  /* exact ragged batches: frames[b] (device int32 [B], NULL: all of the plane) own frames of item b and per_frame, the
+   * elements of one frame of a channel plane (F of a [B,C,T,F] tensor).  The moments of item b are taken over the leading
+   * own = frames[b] * per_frame elements (clamped to 0 .. plane) of each of its C channel planes, summed in the order of a
+   * launch with plane = own, and divided by C * own; the update is applied to the whole plane (finite behind the own part). */
+  const int32_t* frames;
+  int32_t per_frame;
+  int32_t pad1_;
 } pdse_gncomb_desc;
 
 /* AHAM merge of the 4 layer outputs (dbaiat.py:266-288): w = softmax_i(conv1(avgpool(x_i)));
@@ -667,6 +684,12 @@ typedef struct pdse_aham_desc {
   int32_t B, C;
   float bias;
   int32_t pad_;
+  /* exact ragged batches: frames[b] / per_frame as in pdse_gncomb_desc; NULL: all of the plane - the average pool of item
+   * b covers the leading frames[b] * per_frame elements of each channel plane, in the order of a launch with that plane;
+   * the merge is applied to the whole plane. */
+  const int32_t* frames;
+  int32_t per_frame;
+  int32_t pad1_;
 } pdse_aham_desc;
 
 

@@ -137,24 +137,26 @@ class ChlnDesc(C.Structure):
 
 class AttnDesc(C.Structure):
     _fields_ = [("qkv", _fp), ("out", _fp), ("B", _i32), ("T", _i32), ("F", _i32), ("E", _i32),
-                ("heads", _i32), ("axis", _i32), ("pad0_", _i32), ("pad1_", _i32)]
+                ("heads", _i32), ("axis", _i32), ("pad0_", _i32), ("pad1_", _i32), ("seqlen", _fp)]
 
 
 class GruDesc(C.Structure):
     _fields_ = [("gx", _fp), ("whh", _fp), ("bhh", _fp), ("y", _fp),
                 ("B", _i32), ("T", _i32), ("F", _i32), ("H", _i32), ("axis", _i32), ("split", _i32),
-                ("x", _fp), ("wih", _fp), ("bih", _fp)]
+                ("x", _fp), ("wih", _fp), ("bih", _fp), ("seqlen", _fp)]
 
 
 class GncombDesc(C.Structure):
     _fields_ = [("base", _fp), ("row", _fp), ("col", _fp), ("g_row", _fp), ("b_row", _fp), ("g_col", _fp),
                 ("b_col", _fp), ("stats", _fp), ("out", _fp), ("plane", _i64), ("B", _i32), ("C", _i32),
-                ("k1", _f32), ("k2", _f32), ("eps", _f32), ("pad_", _i32)]
+                ("k1", _f32), ("k2", _f32), ("eps", _f32), ("pad_", _i32),
+                ("frames", _fp), ("per_frame", _i32), ("pad1_", _i32)]
 
 
 class AhamDesc(C.Structure):
     _fields_ = [("x", _fp * 4), ("w", _fp), ("means", _fp), ("out", _fp), ("plane", _i64),
-                ("B", _i32), ("C", _i32), ("bias", _f32), ("pad_", _i32)]
+                ("B", _i32), ("C", _i32), ("bias", _f32), ("pad_", _i32),
+                ("frames", _fp), ("per_frame", _i32), ("pad1_", _i32)]
 
 
 class QsampleDesc(C.Structure):

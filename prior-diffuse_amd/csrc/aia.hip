@@ -155,13 +155,18 @@ int pdse_chln_launch(const pdse_chln_desc* d, hipStream_t s) {
 // K and V of a chunk are staged, every thread advances the online softmax of its query over the chunk
 // and keeps (m, l, acc) in registers across chunks.  Chunks are multiples of four keys, so the rescale grouping - and
 // with it every rounding - is the one a single image would give.
-template <int HD>
+// RAGGED (pdse_attn_desc.seqlen): item b attends over its own keys [0, Sk) only, Sk = seqlen[b] - uniform per workgroup, so
+// every barrier is kept.  Keys are staged and walked in the same chunks of CH from key 0, in fours with the tail loop behind
+// them: the roundings of a launch with S = Sk (its chunk is CH too, or Sk <= CH in one image).  Queries at Sk .. S - 1 run no
+// key and store zeros.
+template <int HD, bool RAGGED>
 __global__ __launch_bounds__(ATTN_THREADS) void attn_kernel(const pdse_attn_desc d, const int CH) {
   extern __shared__ float kv[];  // [CH][HD] keys, then [CH][HD] values
   constexpr int W = HD;
   const int E = d.E;
   const int b = blockIdx.y, line = blockIdx.x, c0 = blockIdx.z * W;   // blockIdx.z: head
   const int S = d.axis == 0 ? d.F : d.T;
+  const int Sk = RAGGED ? min(max(d.seqlen[b], 0), S) : S;   // keys (and live queries) of this item
   const int NT = blockDim.x;
   const int64_t plane = (int64_t)d.T * d.F;
   const int64_t base = (int64_t)b * 3 * E * plane + (d.axis == 0 ? (int64_t)line * d.F : (int64_t)line);
@@ -177,14 +182,14 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_kernel(const pdse_attn_desc
     }
   };
   if (single) {
-    stage(0, S);
+    stage(0, Sk);
     __syncthreads();
   }
   const int64_t obase = (int64_t)b * E * plane + (d.axis == 0 ? (int64_t)line * d.F : (int64_t)line);
   const int rounds = (S + NT - 1) / NT;   // uniform trip count: the chunk loop holds barriers
   for (int round = 0; round < rounds; ++round) {
     const int idx = round * NT + threadIdx.x;
-    const bool valid = idx < S;
+    const bool valid = idx < Sk;
     const int sq = valid ? idx : 0;
     float q[HD], acc[HD];
 #pragma unroll
@@ -195,8 +200,8 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_kernel(const pdse_attn_desc
     float m = -1e30f, l = 0.f;
     const float* kh = ks;
     const float* vh = vs;
-    for (int k0 = 0; k0 < S; k0 += CH) {
-      const int n = min(CH, S - k0);
+    for (int k0 = 0; k0 < Sk; k0 += CH) {
+      const int n = min(CH, Sk - k0);
       if (!single) {
         __syncthreads();          // every reader of the previous chunk (or round) is done with the image
         stage(k0, n);
@@ -251,6 +256,9 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_kernel(const pdse_attn_desc
       const float inv = 1.0f / l;
 #pragma unroll
       for (int e = 0; e < HD; ++e) d.out[obase + (int64_t)(c0 + e) * plane + (int64_t)sq * ss] = acc[e] * inv;
+    } else if (RAGGED && idx < S) {
+#pragma unroll
+      for (int e = 0; e < HD; ++e) d.out[obase + (int64_t)(c0 + e) * plane + (int64_t)idx * ss] = 0.f;
     }
   }
 }
@@ -271,10 +279,15 @@ int pdse_attn_launch(const pdse_attn_desc* d, hipStream_t s) {
   const size_t lds = (size_t)2 * CH * HD * sizeof(float);   // <= 64 KB by the cap: within the default dynamic-LDS limit
   const int nt = S >= ATTN_THREADS ? ATTN_THREADS : (S + 63) / 64 * 64;   // one query per thread, whole waves
   const dim3 grid(lines, d->B, 4);
-  if (d->E == 32)
-    hipLaunchKernelGGL(attn_kernel<8>, grid, dim3(nt), lds, s, *d, CH);
+  if (d->seqlen) {
+    if (d->E == 32)
+      hipLaunchKernelGGL((attn_kernel<8, true>), grid, dim3(nt), lds, s, *d, CH);
+    else
+      hipLaunchKernelGGL((attn_kernel<16, true>), grid, dim3(nt), lds, s, *d, CH);
+  } else if (d->E == 32)
+    hipLaunchKernelGGL((attn_kernel<8, false>), grid, dim3(nt), lds, s, *d, CH);
   else
-    hipLaunchKernelGGL(attn_kernel<16>, grid, dim3(nt), lds, s, *d, CH);
+    hipLaunchKernelGGL((attn_kernel<16, false>), grid, dim3(nt), lds, s, *d, CH);
   return pdse_check_launch("attention");
 }
 
@@ -291,7 +304,13 @@ int pdse_attn_launch(const pdse_attn_desc* d, hipStream_t s) {
 // T=401: 1.55 ms per layer against 1.13 + 0.76 ms for recurrence + separate projection launch.  (Parking x_{t+1} in
 // LDS through the two waves without a W_hh tile saved the 32 extra registers but put the 16 W_ih MFMAs in front of
 // the recurrent ones: 1.81 ms.)
-template <int H, bool FUSED>
+// RAGGED (pdse_gru_desc.seqlen, axis 1): the 32 lines of a workgroup may belong to several items, so the length is per line
+// (every gate item of a thread is a unit of the same line, threadIdx.x & 31).  A line is advanced only at positions below its
+// own length: elsewhere its state keeps its value - zero, in the backward direction, until the line's last own position - and
+// y is stored as zero.  The columns of the MFMA tiles are independent lines, so a frozen column does not disturb the others.
+// The step loop ends at the largest own length of the workgroup's lines (uniform: every barrier is kept); the positions behind
+// it are zero-filled after the loop.
+template <int H, bool FUSED, bool RAGGED>
 __global__ __launch_bounds__(8 * H) void gru_kernel(const pdse_gru_desc d) {
   constexpr int G3 = 3 * H, NT = 8 * H, KS = H / 2, MW = G3 / 32, KI = H / 4;
   extern __shared__ float gru_lds[];
@@ -346,10 +365,19 @@ __global__ __launch_bounds__(8 * H) void gru_kernel(const pdse_gru_desc d) {
   }
   const float* bh = d.bhh + dir * G3;
   const float* bi = FUSED ? d.bih + dir * G3 : nullptr;
+  // RAGGED: own length of this thread's line, and the workgroup's step count
+  int slen = S, SW = S;
+  if constexpr (RAGGED) {
+    const int L0 = blockIdx.x * 32, L1 = min(L0 + 31, nlines - 1);
+    SW = 0;
+    for (int b = L0 / per_b; b <= L1 / per_b; ++b) SW = max(SW, min(max(d.seqlen[b], 0), S));
+    slen = live[0] ? min(max(d.seqlen[(L0 + (threadIdx.x & 31)) / per_b], 0), S) : 0;
+  }
   __syncthreads();
 
-  for (int step = 0; step < S; ++step) {
-    const int sq = dir ? S - 1 - step : step;
+  for (int step = 0; step < SW; ++step) {
+    const int sq = dir ? SW - 1 - step : step;
+    const bool own = !RAGGED || sq < slen;
     float xr[4], xz[4], xn[4];
     float xin[FUSED ? KI : 1];
     if constexpr (FUSED) {
@@ -413,15 +441,22 @@ __global__ __launch_bounds__(8 * H) void gru_kernel(const pdse_gru_desc d) {
       const float z = aia_sigmoid((FUSED ? 0.f : xz[k]) + gh[H + u][l]);
       const float n = tanhf((FUSED ? gxn[u][l] : xn[k]) + r * gh[2 * H + u][l]);
       hn[k] = (1.f - z) * n + z * hs[u][l];
+      if constexpr (RAGGED) hn[k] = own ? hn[k] : hs[u][l];
     }
     __syncthreads();   // every MFMA wave has consumed hs, every gate thread has read gh
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int it = threadIdx.x + NT * k;
       hs[it >> 5][it & 31] = hn[k];
-      if (live[k]) d.y[ybase[k] + (int64_t)sq * ss] = hn[k];
+      if (live[k]) d.y[ybase[k] + (int64_t)sq * ss] = own ? hn[k] : 0.f;
     }
     __syncthreads();
+  }
+  if constexpr (RAGGED) {
+    for (int sq = SW; sq < S; ++sq)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (live[k]) d.y[ybase[k] + (int64_t)sq * ss] = 0.f;
   }
 }
 
@@ -433,18 +468,26 @@ int pdse_gru_launch(const pdse_gru_desc* d, hipStream_t s) {
   const bool fused = d->x != nullptr;
   REQ(!fused || (d->H == 64 && d->wih && d->bih), "bigru: the fused input projection needs H == 64, wih and bih");
   REQ(d->split == 0 || d->split == 1, "bigru: split is 0 or 1");
+  REQ(!d->seqlen || d->axis == 1, "bigru: seqlen (exact ragged batches) is per item along the outer axis (axis 1)");
   if (d->split) return pdse_gru3_launch(d, s);   // split-bf16 operands (csrc/gru3.hip)
   REQ(fused || d->gx, "bigru: gx missing");
   const size_t lds = (size_t)(d->H * 32 + 3 * d->H * 33 + (fused ? d->H * 33 : 0)) * sizeof(float);
   const dim3 grid((nlines + 31) / 32, 2);
+  const bool ragged = d->seqlen != nullptr;
   if (d->H == 64) {
-    if (fused) hipLaunchKernelGGL((gru_kernel<64, true>), grid, dim3(512), lds, s, *d);
-    else hipLaunchKernelGGL((gru_kernel<64, false>), grid, dim3(512), lds, s, *d);
+    if (fused) {
+      if (ragged) hipLaunchKernelGGL((gru_kernel<64, true, true>), grid, dim3(512), lds, s, *d);
+      else hipLaunchKernelGGL((gru_kernel<64, true, false>), grid, dim3(512), lds, s, *d);
+    } else {
+      if (ragged) hipLaunchKernelGGL((gru_kernel<64, false, true>), grid, dim3(512), lds, s, *d);
+      else hipLaunchKernelGGL((gru_kernel<64, false, false>), grid, dim3(512), lds, s, *d);
+    }
   } else {
-    if (pdse_check_hip(hipFuncSetAttribute((const void*)gru_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                       "bigru lds attribute"))
+    const void* fn = ragged ? (const void*)gru_kernel<128, false, true> : (const void*)gru_kernel<128, false, false>;
+    if (pdse_check_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "bigru lds attribute"))
       return 1;
-    hipLaunchKernelGGL((gru_kernel<128, false>), grid, dim3(1024), lds, s, *d);
+    if (ragged) hipLaunchKernelGGL((gru_kernel<128, false, true>), grid, dim3(1024), lds, s, *d);
+    else hipLaunchKernelGGL((gru_kernel<128, false, false>), grid, dim3(1024), lds, s, *d);
   }
   return pdse_check_launch("bigru");
 }
@@ -459,17 +502,31 @@ int pdse_gru_launch(const pdse_gru_desc* d, hipStream_t s) {
 // E[x^2] - mean^2 lost 1 + mean^2 / var (5e-3 of the output at mean 64, std 0.25).  No third read of row / col.
 // stats: [B][GN_PARTS][4] = (sum, sum of squares) of row - p_row | of col - p_col per part.
 // ---------------------------------------------------------------------------------------
+// RAGGED (pdse_gncomb_desc.frames): the moments of item b cover the leading own = frames[b] * per_frame elements of each
+// channel plane.  The statistics pass assigns elements to parts and threads by their flat index, so its order of additions
+// depends on the plane: the ragged form walks the flat index i' over C * own exactly as a launch with plane = own does and
+// reads element (i' / own) * plane + i' % own; the apply pass divides by C * own and updates the whole plane.
 #define GN_PARTS 64
+template <bool RAGGED>
+__device__ __forceinline__ int64_t gn_own(const int32_t* frames, const int per_frame, const int b, const int64_t plane) {
+  if constexpr (!RAGGED) return plane;
+  const int64_t own = (int64_t)max(frames[b], 0) * per_frame;
+  return own < plane ? own : plane;
+}
+
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const pdse_gncomb_desc d) {
   __shared__ float red[4][4];
   const int b = blockIdx.y, part = blockIdx.x;
-  const int64_t n = (int64_t)d.C * d.plane;
-  const float* r = d.row + (int64_t)b * n;
-  const float* c = d.col + (int64_t)b * n;
+  const int64_t own = gn_own<RAGGED>(d.frames, d.per_frame, b, d.plane);
+  const int64_t n = (int64_t)d.C * own;
+  const float* r = d.row + (int64_t)b * d.C * d.plane;
+  const float* c = d.col + (int64_t)b * d.C * d.plane;
   const float pr = r[0], pc = c[0];
   float s[4] = {0.f, 0.f, 0.f, 0.f};
   for (int64_t i = (int64_t)part * 256 + threadIdx.x; i < n; i += (int64_t)GN_PARTS * 256) {
-    const float a = r[i] - pr, e = c[i] - pc;
+    const int64_t at = RAGGED ? (i / own) * d.plane + i % own : i;
+    const float a = r[at] - pr, e = c[at] - pc;
     s[0] += a;
     s[1] += a * a;
     s[2] += e;
@@ -486,11 +543,14 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const pdse_gncomb_desc d)
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const pdse_gncomb_desc d) {
   __shared__ float st[4];   // mean, 1/std of row | of col
   const int b = blockIdx.y;
   const int64_t n = (int64_t)d.C * d.plane;
   const int64_t off = (int64_t)b * n;
+  // elements the moments were taken over (an item without own frames: the pivot is its mean, finite all the same)
+  const int64_t cnt = RAGGED ? max((int64_t)d.C * gn_own<RAGGED>(d.frames, d.per_frame, b, d.plane), (int64_t)1) : n;
   if (threadIdx.x < 64) {
     // wave 0: lane = 4 g + k folds parts 4 g .. 4 g + 3 of statistic k, then the 16 groups are folded by a fixed butterfly
     const int k = threadIdx.x & 3, g = threadIdx.x >> 2;
@@ -500,8 +560,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const pdse_gncomb_desc d)
     for (int o = 4; o < 64; o <<= 1) acc += __shfl_xor(acc, o);
     const double s1 = __shfl(acc, threadIdx.x & 2), s2 = __shfl(acc, (threadIdx.x & 2) | 1);
     if (threadIdx.x == 0 || threadIdx.x == 2) {
-      const double m = s1 / (double)n;                       // mean - pivot
-      const double var = fmax(s2 / (double)n - m * m, 0.0);
+      const double m = s1 / (double)cnt;                     // mean - pivot
+      const double var = fmax(s2 / (double)cnt - m * m, 0.0);
       const double pv = (double)(threadIdx.x ? d.col : d.row)[off];
       st[threadIdx.x] = (float)(pv + m);
       st[threadIdx.x + 1] = (float)(1.0 / sqrt(var + (double)d.eps));
@@ -521,11 +581,17 @@ int pdse_gncomb_launch(const pdse_gncomb_desc* d, hipStream_t s) {
   REQ(d && d->base && d->row && d->col && d->g_row && d->b_row && d->g_col && d->b_col && d->stats && d->out,
       "gn_combine: null pointer");
   REQ(d->B > 0 && d->B <= 65535 && d->C > 0 && d->plane > 0, "gn_combine: bad sizes");
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(GN_PARTS, d->B), dim3(256), 0, s, *d);
+  REQ(!d->frames || d->per_frame > 0, "gn_combine: frames (exact ragged batches) needs per_frame > 0");
   const int64_t n = (int64_t)d->C * d->plane;
   int bx = (int)((n + 255) / 256);
   if (bx > 256) bx = 256;
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(bx, d->B), dim3(256), 0, s, *d);
+  if (d->frames) {
+    hipLaunchKernelGGL(gn_stats_kernel<true>, dim3(GN_PARTS, d->B), dim3(256), 0, s, *d);
+    hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(bx, d->B), dim3(256), 0, s, *d);
+  } else {
+    hipLaunchKernelGGL(gn_stats_kernel<false>, dim3(GN_PARTS, d->B), dim3(256), 0, s, *d);
+    hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(bx, d->B), dim3(256), 0, s, *d);
+  }
   return pdse_check_launch("gn_combine");
 }
 
@@ -533,16 +599,21 @@ int pdse_gncomb_launch(const pdse_gncomb_desc* d, hipStream_t s) {
 // AHAM (dbaiat.py:266-288): channel means of the 4 layer outputs, softmax over the layers of
 // conv1(mean) (conv1 is linear, so it commutes with the average pool), weighted merge.
 // ---------------------------------------------------------------------------------------
+// RAGGED (pdse_aham_desc.frames): the pool of item b covers the leading frames[b] * per_frame elements of a channel plane, in
+// the same thread-strided order, and divides by that count (an item without own frames: mean 0).
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void aham_mean_kernel(const pdse_aham_desc d) {
   __shared__ float red[4];
   const int c = blockIdx.x, b = blockIdx.y, i = blockIdx.z;
   const float* x = d.x[i] + ((int64_t)b * d.C + c) * d.plane;
+  const int64_t own = gn_own<RAGGED>(d.frames, d.per_frame, b, d.plane);
   float s = 0.f;
-  for (int64_t q = threadIdx.x; q < d.plane; q += 256) s += x[q];
+  for (int64_t q = threadIdx.x; q < own; q += 256) s += x[q];
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) d.means[((size_t)i * d.B + b) * d.C + c] = (red[0] + red[1] + red[2] + red[3]) / (float)d.plane;
+  if (threadIdx.x == 0)
+    d.means[((size_t)i * d.B + b) * d.C + c] = (RAGGED && own == 0) ? 0.f : (red[0] + red[1] + red[2] + red[3]) / (float)own;
 }
 
 __global__ __launch_bounds__(256) void aham_merge_kernel(const pdse_aham_desc d) {
@@ -567,7 +638,9 @@ __global__ __launch_bounds__(256) void aham_merge_kernel(const pdse_aham_desc d)
 int pdse_aham_launch(const pdse_aham_desc* d, hipStream_t s) {
   REQ(d && d->x[0] && d->x[1] && d->x[2] && d->x[3] && d->w && d->means && d->out, "aham: null pointer");
   REQ(d->B > 0 && d->B <= 65535 && d->C > 0 && d->C <= 65535 && d->plane > 0, "aham: bad sizes");
-  hipLaunchKernelGGL(aham_mean_kernel, dim3(d->C, d->B, 4), dim3(256), 0, s, *d);
+  REQ(!d->frames || d->per_frame > 0, "aham: frames (exact ragged batches) needs per_frame > 0");
+  if (d->frames) hipLaunchKernelGGL(aham_mean_kernel<true>, dim3(d->C, d->B, 4), dim3(256), 0, s, *d);
+  else hipLaunchKernelGGL(aham_mean_kernel<false>, dim3(d->C, d->B, 4), dim3(256), 0, s, *d);
   const int64_t n = (int64_t)d->C * d->plane;
   int bx = (int)((n + 255) / 256);
   if (bx > 256) bx = 256;

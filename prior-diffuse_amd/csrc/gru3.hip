@@ -60,6 +60,11 @@ __device__ __forceinline__ void g3_split4(const float (&x)[4], uint2 (&p)[3]) {
 
 constexpr int H = 64, G3 = 192;
 
+// RAGGED (pdse_gru_desc.seqlen, axis 1; see gru_kernel in aia.hip): a line is advanced only at positions below its own length -
+// elsewhere its state (hreg and its planes in hsP) keeps its value and y is stored as zero - the step loop ends at the largest
+// own length of the workgroup's lines (uniform: every barrier is kept, the x pipeline runs over those steps), and the positions
+// behind it are zero-filled after the loop.
+template <bool RAGGED>
 __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
   __shared__ uint4 hsP[4][3][64];       // h: [K block][plane][lane half hh * 32 + line], element j = unit 16 kb + 8 hh + j
   __shared__ uint4 xP[2][2][3][64];     // x_t planes, double-buffered by step parity: [buf][K block][plane][lane]
@@ -116,6 +121,14 @@ __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
     ybase = (int64_t)b * 2 * H * plane + pos + (int64_t)(dir * H + 4 * g) * plane;
   }
   float hreg[4] = {0.f, 0.f, 0.f, 0.f};
+  // RAGGED: own length of this thread's line, and the workgroup's step count
+  int slen = S, SW = S;
+  if constexpr (RAGGED) {
+    const int L0 = blockIdx.x * 32, L1 = min(L0 + 31, nlines - 1);
+    SW = 0;
+    for (int b = L0 / per_b; b <= L1 / per_b; ++b) SW = max(SW, min(max(d.seqlen[b], 0), S));
+    slen = live ? min(max(d.seqlen[Lg / per_b], 0), S) : 0;
+  }
   char* const hs_w = reinterpret_cast<char*>(&hsP[g >> 2][0][((g >> 1) & 1) * 32 + l]) + (g & 1) * 8;   // + plane * 1024 bytes
 
   // ---- the input: waves 6, 7 fetch K block (wave - 6) of x: channels 16 kb + 8 hh + j of line `col`
@@ -130,9 +143,9 @@ __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
   }
   float xr[8];
   auto fetch = [&](const int step) {
-    const int sq = dir ? S - 1 - step : step;
+    const int sq = dir ? SW - 1 - step : step;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) xr[j] = (xlive && step < S) ? d.x[xbase + (int64_t)j * plane + (int64_t)sq * ss] : 0.f;
+    for (int j = 0; j < 8; ++j) xr[j] = (xlive && step < SW) ? d.x[xbase + (int64_t)j * plane + (int64_t)sq * ss] : 0.f;
   };
   auto publish = [&](const int buf) {   // xr -> planes of K block (wave - 6)
     uint4 p[3];
@@ -149,8 +162,9 @@ __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
   }
   __syncthreads();
 
-  for (int step = 0; step < S; ++step) {
-    const int sq = dir ? S - 1 - step : step;
+  for (int step = 0; step < SW; ++step) {
+    const int sq = dir ? SW - 1 - step : step;
+    const bool own = !RAGGED || sq < slen;
     const int buf = step & 1;
     if (wave < 6 || xw) {
       f32x16 acc;
@@ -193,6 +207,7 @@ __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
       const float z = g3_sigmoid(gh[H + u][l]);
       const float n = g3_tanh(gxn[u][l] + r * gh[2 * H + u][l]);
       hn[k] = (1.f - z) * n + z * hreg[k];
+      if constexpr (RAGGED) hn[k] = own ? hn[k] : hreg[k];
       hreg[k] = hn[k];
     }
     uint2 hp[3];
@@ -202,9 +217,15 @@ __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
     for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(hs_w + p * 1024) = hp[p];
     if (live) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) d.y[ybase + (int64_t)k * plane + (int64_t)sq * ss] = hn[k];
+      for (int k = 0; k < 4; ++k) d.y[ybase + (int64_t)k * plane + (int64_t)sq * ss] = own ? hn[k] : 0.f;
     }
     __syncthreads();
+  }
+  if constexpr (RAGGED) {
+    if (live)
+      for (int sq = SW; sq < S; ++sq)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d.y[ybase + (int64_t)k * plane + (int64_t)sq * ss] = 0.f;
   }
 }
 
@@ -217,6 +238,7 @@ int pdse_gru3_launch(const pdse_gru_desc* d, hipStream_t s) {
     return 1;
   }
   const int nlines = d->B * (d->axis == 0 ? d->T : d->F);
-  hipLaunchKernelGGL(gru3_kernel, dim3((nlines + 31) / 32, 2), dim3(512), 0, s, *d);
+  if (d->seqlen) hipLaunchKernelGGL(gru3_kernel<true>, dim3((nlines + 31) / 32, 2), dim3(512), 0, s, *d);
+  else hipLaunchKernelGGL(gru3_kernel<false>, dim3((nlines + 31) / 32, 2), dim3(512), 0, s, *d);
   return pdse_check_launch("bigru (split-bf16)");
 }

@@ -43,6 +43,10 @@ def parse_args_and_config(argv=None):
     p.add_argument("--batch", type=int, default=1,
                    help="(not a flag of the reference) --generate: enhance this many files per pass as exact ragged batches - every file's "
                         "result and noise are those of the one-file loop (priors GCRN and DiffUNet); default 1: one file per pass")
+    p.add_argument("--masked-prior", action="store_true",
+                   help="(not a flag of the reference) --generate --batch N with a DB-AIAT prior (aia_complex_trans_ri, "
+                        "dual_aia_trans_merge_crm): record the ragged batches with the length-masked attention, GRU, GroupNorm and AHAM "
+                        "kernels, so that every file's result is that of the one-file loop; default: these priors refuse --batch")
     p.add_argument("--inflight", type=int, default=1,
                    help="(not a flag of the reference) --generate: keep this many files (2 .. 4) in flight on HIP streams of their own, each "
                         "verified on the device without a device-wide synchronisation (ComplexDDPMTrainer.enhance_stream); same files, "

@@ -1447,8 +1447,13 @@ class AiaPlan(PlanBase):
     gemm_planes = 2          # operand form of those GEMMs: f16x2 (csrc/dense.hip np 2, csrc/gconv4.hip korder 5); 3: the three-plane bf16 split
     TPAD, G = 8, 40          # leading zero frames (the largest dilation) and 8-channel groups of the dense buffers
 
-    def __init__(self, ctx, sd, B, T, plan=None, d=32, split_bf16=None, planes=None):
-        """d: d_model of the transformer layers (32: AIA_Transformer(64, 64); 64: AIA_Transformer_merge(128, 64))."""
+    def __init__(self, ctx, sd, B, T, plan=None, d=32, split_bf16=None, planes=None, frames=None):
+        """d: d_model of the transformer layers (32: AIA_Transformer(64, 64); 64: AIA_Transformer_merge(128, 64)).
+        frames: exact ragged batches - device int32 [B], every utterance's own frames.  It goes to the four operators through
+        which padding frames could reach an utterance's own, and only to their instances that run along the frames: the column
+        layers' attention and bidirectional GRU (``seqlen``), the GroupNorm statistics of the layer update and the AHAM average
+        pool (``frames``, ``per_frame`` = 80 bins).  Everything else is per frame, per position or causal in time (DESIGN.md
+        4.8).  None: every table NULL, the dense plan."""
         if split_bf16 is not None:
             self.split_bf16 = bool(split_bf16)
         if planes is not None:       # 3 / 2: bf16x3 / f16x2 (fp32-equivalent); 1: the opt-in bf16 mode - dense blocks / strided convolutions on plain bf16 operands
@@ -1459,6 +1464,7 @@ class AiaPlan(PlanBase):
         super().__init__(ctx, plan, ns=(ctx.bank.token(sd), d, self.fused_gru_input, self.split_bf16, self.split_gru, self.gemm_planes,
                                         self.fused))
         self.sd, self.B, self.T, self.d = sd, B, T, d
+        self.frames = frames
         a = ctx.alloc
         FH = self.FH
         self.x = a(B, 2, T, F0)
@@ -1639,6 +1645,8 @@ class AiaPlan(PlanBase):
         d = L.AttnDesc()
         d.qkv, d.out, d.B, d.E, d.heads, d.axis = self.qkv.data_ptr(), self.att.data_ptr(), B, dm, 4, 0
         d.T, d.F = (FH, T) if att_ft else (T, FH)                     # "ft": the innermost axis is the sequence either way
+        if att_ft:
+            d.seqlen = Ctx.ptr(self.frames)                           # keys of an utterance's own frames only
         self.add(d, TAG_PRIOR)
         self._pw(self.att, dm, lambda: dict(wk0=self.w(p + ".self_attn.out_proj.weight").T,
                                             bias0=self.w(p + ".self_attn.out_proj.bias")),
@@ -1688,6 +1696,8 @@ class AiaPlan(PlanBase):
         gd.bhh = self.upw(g + "bhh", lambda: np.stack([self.w(g + "bias_hh_l0"), self.w(g + "bias_hh_l0_reverse")], 0)).data_ptr()
         gd.B, gd.H, gd.axis = B, 2 * dm, 1                            # lines on the innermost axis, sequence on the outer
         gd.T, gd.F = (FH, T) if gru_ft else (T, FH)
+        if not gru_ft:
+            gd.seqlen = Ctx.ptr(self.frames)                          # the backward direction starts at the utterance's own last frame
         self.add(gd, TAG_LSTM)
         # relu -> linear2 -> + residual (the normed tensor); ReLU = the load transform with slope 0, identity affine
         self._pw(self.gy, 4 * dm, lambda: dict(wk0=self.w(p + ".linear2.weight").T, bias0=self.w(p + ".linear2.bias"),
@@ -1723,6 +1733,8 @@ class AiaPlan(PlanBase):
         ah.w = self.upw(p + ".w", lambda: self.w(p + ".conv1.weight").reshape(64)).data_ptr()
         ah.bias = self._wf(p + ".conv1.bias")
         ah.means, ah.out, ah.plane, ah.B, ah.C = self.means.data_ptr(), dst.data_ptr(), self.T * self.FH, self.B, 64
+        if self.frames is not None:
+            ah.frames, ah.per_frame = self.frames.data_ptr(), self.FH
         self.add(ah, TAG_PRIOR)
 
     def _dense_decoder(self, de, merged, out, out_C, out_off):
@@ -1762,6 +1774,8 @@ class AiaPlan(PlanBase):
         g.g_col, g.b_col = self._wp("%s.col_norm.%d.weight" % (p, i)), self._wp("%s.col_norm.%d.bias" % (p, i))
         g.stats, g.plane, g.B, g.C = self.gn_stats.data_ptr(), self.T * self.FH, self.B, self.d
         g.k1, g.k2, g.eps = self._wf(p + ".k1"), self._wf(p + ".k2"), 1e-8
+        if self.frames is not None:
+            g.frames, g.per_frame = self.frames.data_ptr(), self.FH
         self.add(g, TAG_PRIOR)
 
     def build(self, x=None, out=None):
@@ -1799,8 +1813,8 @@ class DualAiaPlan(AiaPlan):
     append), and IEEE addition commutes.  The golden vectors of the reference module confirm that the two output
     lists are bit-identical (tests/test_oracle_golden.py), so each layer is evaluated once."""
 
-    def __init__(self, ctx, sd, B, T, plan=None, split_bf16=None, planes=None):
-        super().__init__(ctx, sd, B, T, plan, d=64, split_bf16=split_bf16, planes=planes)
+    def __init__(self, ctx, sd, B, T, plan=None, split_bf16=None, planes=None, frames=None):
+        super().__init__(ctx, sd, B, T, plan, d=64, split_bf16=split_bf16, planes=planes, frames=frames)
         a = ctx.alloc
         self.mag = a(B, 1, T, F0)
         self.x_mag_en = a(B, 64, T, self.FH)

@@ -24,11 +24,12 @@ F0 = 161
 
 
 RAGGED_PRIORS = ("GCRN", "DiffUNet")
+MASKED_PRIORS = ("aia_complex_trans_ri", "dual_aia_trans_merge_crm")    # ragged with the length-masked kernels (masked_prior=True)
 
 
-def ragged_args(prior_name, L_):
-    """Argument check of ``SamplerPipeline(ragged=True)``, without a device."""
-    if prior_name not in RAGGED_PRIORS:
+def ragged_args(prior_name, L_, masked=False):
+    """Argument check of ``SamplerPipeline(ragged=True, masked_prior=masked)``, without a device."""
+    if prior_name not in RAGGED_PRIORS and not (masked and prior_name in MASKED_PRIORS):
         raise ValueError("exact ragged batches: prior %r attends and runs a bidirectional GRU over all T frames of the padded batch, "
                          "so padding reaches every frame of an utterance (supported priors: %s)" % (prior_name, ", ".join(RAGGED_PRIORS)))
     if L_ is None:
@@ -61,7 +62,7 @@ class SamplerPipeline:
     def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, T=None, L_=None, fast_sampling=True,
                  use_sigma=False, params=default_params, with_signal=None, deltamu=False, cond="init", bank=None,
                  split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False, ragged=False,
-                 verdict=False):
+                 verdict=False, masked_prior=False):
         """deltamu: the alternative parameterisation of utils/params.py:36 — ddpm_sd is a ``Nocon`` state_dict,
         x_T = noise + X_init/11 (:947-948), eps = Nocon(x, t) (:970-971), no final ``+ X_init`` (:995).
         cond (deltamu False): what conditions DiffUNet1 — "init": X_init/11 (pirorgrad, :967-969, + X_init at the end,
@@ -106,7 +107,8 @@ class SamplerPipeline:
         bottleneck of the eps-net (and of a DiffUNet prior), the overlap-add and the ``--sigma`` maximum - and owns their length
         tables (``lens``, ``frames_tab``, ``valid_tab``: device int32, written by a copy before each pass, so a replayed
         hipGraph sees new lengths).  Everything else on the path is per-frame or looks back in time only.  The
-        DB-AIAT priors attend and run a bidirectional GRU over all of T: ValueError.  False (default): every table is NULL and
+        DB-AIAT priors attend and run a bidirectional GRU over all of T: ValueError, unless ``masked_prior`` records their
+        length-masked kernels.  False (default): every table is NULL and
         the plan is launch for launch today's.
         verdict: record the finiteness verdict of a pass with the plan (csrc/range.hip, PDSE_RANGE_NONFINITE): the plan owns
         ``verdict_tab`` (int32 [rows][32], one row per judged tensor: ``spec``, and ``istft.wav`` with the signal back end), clears
@@ -115,7 +117,12 @@ class SamplerPipeline:
         own pass.  ``verdict_fetch(stream)`` copies the table to pinned host memory without synchronising and
         ``verdict_counts()`` reads it once an event recorded behind the copy has fired: what ``check()`` learns from a
         reduction over the spectrogram and a device-wide synchronisation, per pass and per stream.  Plan files do not carry it
-        (``planfile.save_pipeline`` raises ValueError).  False (default): the plan is launch for launch today's."""
+        (``planfile.save_pipeline`` raises ValueError).  False (default): the plan is launch for launch today's.
+        masked_prior (with ``ragged``): record a DB-AIAT prior (``aia_complex_trans_ri``, ``dual_aia_trans_merge_crm``) with the
+        length-masked forms of its four operators that reach across frames - attention and the bidirectional GRU along the
+        frames, the GroupNorm statistics of the layer update and the AHAM average pool (csrc/aia.hip, csrc/gru3.hip; DESIGN.md
+        4.8) - on ``frames_tab``, so that ``ragged=True`` accepts these priors with the same contract.  False (default): they
+        are refused as before; for the other priors the flag changes nothing."""
         if L_ is not None:
             T = 1 + L_ // 160
         if with_signal is None:
@@ -137,8 +144,9 @@ class SamplerPipeline:
             # it keeps exact fp32 MFMA arithmetic - BASELINE config 3 is an fp32 configuration anyway.
             split_bf16 = bool(fast_sampling)
         self.ragged = bool(ragged)
+        self.masked_prior = bool(masked_prior)
         if self.ragged:
-            ragged_args(prior_name, L_)
+            ragged_args(prior_name, L_, masked=self.masked_prior)
         self.B, self.T, self.L = B, T, L_
         self.device = torch.device(device)
         self.ctx = ctx = nets.Ctx(device, bank)
@@ -179,9 +187,11 @@ class SamplerPipeline:
             self.prior = adopt(nets.EpsNetPlan(ctx, prior_sd, B, T, time_cond=False, plan=self.plan, split_bf16=split_bf16, exclusive=exclusive,
                                                frames=self.frames_tab))
         elif prior_name == "aia_complex_trans_ri":
-            self.prior = adopt(nets.AiaPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", planes=aplanes))
+            self.prior = adopt(nets.AiaPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", planes=aplanes,
+                                            frames=self.frames_tab))
         elif prior_name == "dual_aia_trans_merge_crm":
-            self.prior = adopt(nets.DualAiaPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", planes=aplanes))
+            self.prior = adopt(nets.DualAiaPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", planes=aplanes,
+                                                frames=self.frames_tab))
         else:
             raise ValueError("prior %r not built (GCRN, DiffUNet, aia_complex_trans_ri, dual_aia_trans_merge_crm)" % prior_name)
         if dtype == "bf16":

@@ -49,9 +49,10 @@ def _inflight_arg(inflight):
 
 class ComplexDDPMTrainer(object):
     MAX_PLANS = 3   # recorded (B, T) geometries kept alive (least recently used first out); weights are shared by all
+    masked_prior = False   # exact ragged batches of the DB-AIAT priors on the length-masked kernels (constructor)
 
     def __init__(self, args, config, device=None, prior_state_dict=None, ddpm_state_dict=None, params=None, exclusive=None,
-                 dtype=None, split=None, audit=None):
+                 dtype=None, split=None, audit=None, masked_prior=None):
         """args: .retrain .joint .draw .sigma .checkpoint .generated_wav
         config: .model.name, .train.{fft_num, win_size, win_shift, feat_type}
         Weights come from ``<args.checkpoint>/best_checkpoint.pth`` under the reference's
@@ -72,7 +73,13 @@ class ComplexDDPMTrainer(object):
         "bf16x3" whatever this says (``_checked``).
         audit: build the plans with the range audit of the f16x2 window (``SamplerPipeline(audit=True)``) and let ``_checked``
         treat a tensor that lies wholly BELOW the window - finite output, no other trace - like one that overflowed it: warn,
-        repeat the geometry on "bf16x3".  None: ``args.audit_range`` when the CLI set it (``main.py --audit-range``), else False."""
+        repeat the geometry on "bf16x3".  None: ``args.audit_range`` when the CLI set it (``main.py --audit-range``), else False.
+        masked_prior: let ``enhance_batch(exact=True)`` and ``generate_wav(batch=N)`` take the DB-AIAT priors
+        (``aia_complex_trans_ri``, ``dual_aia_trans_merge_crm``): their ragged plans are recorded with the length-masked attention,
+        GRU, GroupNorm and AHAM kernels (``SamplerPipeline(ragged=True, masked_prior=True)``), and every utterance comes out as
+        if enhanced alone, as for the other priors.  Dense passes are not touched.  None: ``args.masked_prior`` when the CLI set
+        it (``main.py --masked-prior``), else False: exact ragged batches of these priors raise ValueError as before."""
+        self.masked_prior = bool(getattr(args, "masked_prior", False) if masked_prior is None else masked_prior)
         if split is None:
             split = getattr(args, "split", None)
         if split not in (None, "f16x2", "bf16x3"):
@@ -168,7 +175,8 @@ class ComplexDDPMTrainer(object):
                 self.device, self.prior_name, self.prior_sd, self.ddpm_sd, B, T=T, L_=L_,
                 fast_sampling=self.params.fast_sampling, use_sigma=key[3], params=self.params, deltamu=self.deltamu,
                 cond=self.cond, bank=self.bank, xT_plus_init=self.xT_plus_init, exclusive=self.exclusive, dtype=self.dtype,
-                split="bf16x3" if key in self._range_fallback else self.split, audit=self.audit, ragged=ragged)
+                split="bf16x3" if key in self._range_fallback else self.split, audit=self.audit, ragged=ragged,
+                masked_prior=ragged and self.masked_prior)
         else:
             self._pipes.move_to_end(key)
         return pipe
@@ -390,7 +398,7 @@ class ComplexDDPMTrainer(object):
         exact True: every utterance exactly as ``enhance(wav_b[None], x_T_b)`` gives it alone (``generate_wav``'s per-file
         result) - the STFT reflects at, the TCM pads at and the ISTFT sums up to the utterance's own end, ``--sigma`` takes
         the maximum over its own frames (``SamplerPipeline(ragged=True)``; priors GCRN and DiffUNet, ValueError for the
-        DB-AIAT priors, which attend over all frames of the batch).  x_T: one padded [B, 2, T, 161] tensor, or a list of
+        DB-AIAT priors, which attend over all frames of the batch - unless the trainer was built with ``masked_prior=True``).  x_T: one padded [B, 2, T, 161] tensor, or a list of
         per-utterance [2, T_b, 161] (or [1, 2, T_b, 161]) tensors, T_b = 1 + len_b // 160; None: one draw per utterance at its
         own shape, in list order - the draws of the B = 1 calls."""
         wavs = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in wavs]
@@ -410,7 +418,7 @@ class ComplexDDPMTrainer(object):
 
     def _enhance_ragged(self, wavs, x_T, L_):
         """``enhance_batch(exact=True)`` on 1-D utterances, padded to ``L_`` samples; returns the list of enhanced utterances."""
-        ragged_args(self.prior_name, L_)
+        ragged_args(self.prior_name, L_, masked=self.masked_prior)
         lens = [int(w.numel()) for w in wavs]
         B, T = len(wavs), 1 + L_ // 160
         batch = torch.zeros(B, L_, dtype=torch.float32, device=self.device)
@@ -564,7 +572,7 @@ class ComplexDDPMTrainer(object):
         return out
 
     def _generate_wav_batched(self, data_path, rng_fidelity, batch):
-        ragged_args(self.prior_name, 161)
+        ragged_args(self.prior_name, 161, masked=self.masked_prior)
         paths = sorted(glob.glob(data_path + "/*.wav"))
         ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0
         written = []

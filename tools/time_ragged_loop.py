@@ -5,6 +5,10 @@ then ``--runs`` timed runs of each; prints the median ms per file with the lowes
 batched loop (padded frames / own frames) and whether both loops wrote the same bytes.
 
     python tools/time_ragged_loop.py [--files 64] [--batch 32] [--runs 3] [--out profiles/ragged_file_loop_timing.txt]
+    python tools/time_ragged_loop.py --prior aia_complex_trans_ri --batch 8 --out profiles/ragged_aia_timing.txt
+
+``--prior`` names the prior network (default GCRN); the DB-AIAT priors are built with ``masked_prior=True``, without which their
+batched loop is refused.
 """
 import argparse
 import importlib
@@ -29,6 +33,8 @@ def main():
     ap.add_argument("--shared", action="store_true",
                     help="build both trainers with exclusive=False (the kernels that do not depend on the batch size: the two loops then "
                          "write the same bytes); default: the trainers a user gets, whose one-file loop takes the persistent small-batch LSTM")
+    ap.add_argument("--prior", default="GCRN", choices=("GCRN", "DiffUNet", "aia_complex_trans_ri", "dual_aia_trans_merge_crm"),
+                    help="the prior network; the DB-AIAT priors run their batches on the length-masked kernels (masked_prior=True)")
     ap.add_argument("--out", default=None, help="append the result lines to this file")
     args = ap.parse_args()
     sys.path.insert(0, HERE)
@@ -62,12 +68,13 @@ def main():
         waste = sum(raggedplan.padding_waste(lens[lo:hi], args.batch) * sum(1 + int(n) // 160 for n in lens[lo:hi])
                     for lo, hi in raggedplan.windows(len(lens), args.batch)) / sum(1 + int(n) // 160 for n in lens)
         trs = {}
+        masked = ("aia_complex_trans_ri", "dual_aia_trans_merge_crm")
         for batch in (1, args.batch):
             trs[batch] = trainer.ComplexDDPMTrainer(
                 ns(retrain=False, joint=True, draw=False, sigma=False, checkpoint="x", generated_wav=os.path.join(work, "out%d" % batch)),
-                ns(model=ns(name="GCRN"), train=ns(fft_num=320, win_size=320, win_shift=160, feat_type="sqrt")),
-                device="cuda:0", prior_state_dict=synth.make_state_dict("GCRN"), ddpm_state_dict=synth.make_state_dict("DiffUNet1"),
-                exclusive=False if args.shared else None)
+                ns(model=ns(name=args.prior), train=ns(fft_num=320, win_size=320, win_shift=160, feat_type="sqrt")),
+                device="cuda:0", prior_state_dict=synth.make_state_dict(args.prior), ddpm_state_dict=synth.make_state_dict("DiffUNet1"),
+                exclusive=False if args.shared else None, masked_prior=args.prior in masked)
             torch.manual_seed(1)
             written = trs[batch].generate_wav(load_pre_train=False, data_path=src, batch=batch)     # untimed
             assert len(written) == args.files
@@ -81,14 +88,15 @@ def main():
                 trs[batch].generate_wav(load_pre_train=False, data_path=src, batch=batch)
                 torch.cuda.synchronize()
                 ms[batch].append(1e3 * (time.perf_counter() - t0) / args.files)
-        res = {"files": args.files, "seconds": [args.min_seconds, args.max_seconds], "runs": args.runs, "batch": args.batch,
+        res = {"prior": args.prior, "files": args.files, "seconds": [args.min_seconds, args.max_seconds], "runs": args.runs, "batch": args.batch,
                "padding_waste": round(waste, 4), "same_bytes": bool(same), "exclusive": not args.shared}
         for batch in (1, args.batch):
             res["ms_per_file_batch%d" % batch] = [round(statistics.median(ms[batch]), 3), round(min(ms[batch]), 3), round(max(ms[batch]), 3)]
-            say("generate_wav(batch=%-2d): %8.3f ms per file (%.3f .. %.3f over %d runs of %d files of %.0f - %.0f s)" % (
-                batch, statistics.median(ms[batch]), min(ms[batch]), max(ms[batch]), args.runs, args.files, args.min_seconds, args.max_seconds))
+            say("%s generate_wav(batch=%-2d): %8.3f ms per file (%.3f .. %.3f over %d runs of %d files of %.0f - %.0f s)" % (
+                args.prior, batch, statistics.median(ms[batch]), min(ms[batch]), max(ms[batch]), args.runs, args.files, args.min_seconds, args.max_seconds))
         say("padding waste of batch=%d: %.3f padded frames per own frame; written files byte-identical to batch=1: %s (trainers %s)" % (
-            args.batch, waste, same, "exclusive=False" if args.shared else "as a user gets them: batch=1 on the persistent small-batch LSTM"))
+            args.batch, waste, same, "exclusive=False" if args.shared else
+            "as a user gets them" + (": batch=1 on the persistent small-batch LSTM" if args.prior == "GCRN" else "")))
         say("RESULT " + json.dumps(res))
     finally:
         shutil.rmtree(work, ignore_errors=True)
