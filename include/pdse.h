@@ -918,8 +918,26 @@ typedef struct pdse_metrics_desc {
  * happens before the launch and needs no device): n_in >= 1, n_out <= Lmax; a recorded plan reads it again on every run, so it
  * must outlive the plan.  taps: 2 half + 1 float64 values built by the caller (prior-diffuse_amd/wavio.py: taps()).
  * A workgroup computes PDSE_RESAMPLE_BLOCK consecutive outputs from an input window staged in LDS; ratios whose window of
- * (PDSE_RESAMPLE_BLOCK - 1) down / up + 2 jmax + 2 samples exceeds 64 KB are refused. */
+ * (PDSE_RESAMPLE_BLOCK - 1) down / up + 2 jmax + 2 samples exceeds 64 KB are refused.
+ *
+ * fmt (the former trailing pad word; additive within ABI 9) selects the sample encoding.  fmt == 0 is the operator described
+ * above, unchanged: width 1, 2 or 4, ch 1 or 2, the same checks, error texts and kernels.  fmt != 0 takes a second kernel whose
+ * decode step covers what RIFF/WAVE files hold; ch is then 1 .. 8, and everything behind the decode (window, convert, zero tail,
+ * the frame beyond pcm_bytes, independence of B) is the step above.  The arithmetic is that of wavio.read_any:
+ *   PDSE_WAV_INT    width 1, 2, 4: as above; width 3: the 24-bit two's complement value, sign-extended, / 8388608 (exact)
+ *   PDSE_WAV_FLOAT  width 4: the binary32 bits as they are (moved as an integer: NaN payloads and subnormals survive);
+ *                   width 8: binary64 converted to fp32 once, round to nearest even; beyond the fp32 range: infinity
+ *   PDSE_WAV_ULAW   width 1: u = ~byte, mag = ((((u & 15) << 3) + 0x84) << ((u >> 4) & 7)) - 0x84, negative when u & 0x80, / 32768
+ *   PDSE_WAV_ALAW   width 1: a = byte ^ 0x55, e = (a >> 4) & 7, m = a & 15, mag = (m << 4) + 8 when e == 0, else
+ *                   ((m << 4) + 0x108) << (e - 1); positive when a & 0x80; / 32768
+ *   mix             the fp32 sum of the channels in channel order, then one division by (float)ch (ch == 2: (a + b) / 2, as above)
+ * Another width, a ch outside 1 .. 8 or an unknown fmt is refused before the launch. */
 #define PDSE_RESAMPLE_BLOCK 256
+#define PDSE_WAV_INT 1
+#define PDSE_WAV_FLOAT 2
+#define PDSE_WAV_ALAW 3
+#define PDSE_WAV_ULAW 4
+#define PDSE_WAV_MAX_CH 8
 typedef struct pdse_resample_desc {
   const uint8_t* pcm;          /* device [pcm_bytes] */
   const int64_t* offs;         /* device [B] byte offset of every utterance in pcm */
@@ -928,7 +946,7 @@ typedef struct pdse_resample_desc {
   const double* taps;          /* device [2 half + 1], or NULL when up == down */
   float* out;                  /* device [B][Lmax] */
   int64_t pcm_bytes;
-  int32_t B, Lmax, up, down, half, width, ch, pad_;
+  int32_t B, Lmax, up, down, half, width, ch, fmt;   /* fmt: 0 (integer PCM, width 1 / 2 / 4, ch 1 / 2) or PDSE_WAV_* */
 } pdse_resample_desc;
 
 /* Range audit of the f16x2 window (csrc/range.hip, additive within ABI 9): per-tensor histograms of the fp16 binade of

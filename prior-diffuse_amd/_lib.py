@@ -244,7 +244,7 @@ class ResampleDesc(C.Structure):
     """PCM decode, mono mix and rate conversion of B utterances (include/pdse.h: pdse_resample_desc, csrc/resample.hip)."""
     _fields_ = [("pcm", _fp), ("offs", _fp), ("n_in_host", _fp), ("n_in", _fp), ("taps", _fp), ("out", _fp),
                 ("pcm_bytes", _i64), ("B", _i32), ("Lmax", _i32), ("up", _i32), ("down", _i32), ("half", _i32),
-                ("width", _i32), ("ch", _i32), ("pad_", _i32)]
+                ("width", _i32), ("ch", _i32), ("fmt", _i32)]
 
 
 class RangeRow(C.Structure):
@@ -272,6 +272,9 @@ RANGE_BIN_FULL = RANGE_BINADE.index(-2)      # first bin whose elements are carr
 RANGE_BIN_TOP = RANGE_BINS - 1               # hi leaves the fp16 range
 
 RESAMPLE_BLOCK = 256      # PDSE_RESAMPLE_BLOCK: outputs per workgroup
+# pdse_resample_desc.fmt: 0 is the integer-PCM operator as it was (width 1 / 2 / 4, one or two channels); the others (PDSE_WAV_*)
+WAV_INT, WAV_FLOAT, WAV_ALAW, WAV_ULAW = 1, 2, 3, 4
+WAV_MAX_CH = 8            # PDSE_WAV_MAX_CH: channels the kernel of fmt != 0 mixes
 
 METRICS_OFF_WIN, METRICS_OFF_BASIS = 0, 512
 METRICS_OFF_CRIT = METRICS_OFF_BASIS + 480 * 1024

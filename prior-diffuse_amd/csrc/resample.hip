@@ -18,6 +18,15 @@
 // row is written.  A row is computed from its own utterance alone, at positions that depend on the output index alone:
 // it does not depend on B or on the utterance's place in the batch.  No atomics, no scratch, no host synchronisation.
 // All sample positions are 64-bit: n down passes 2^31 for a ten-minute 44.1 kHz file.
+// Two kernel templates run the same steps behind the decode (window, convert, zero tail).  resample_kernel<WIDTH, CH>
+// is the operator of fmt == 0 - integer PCM, one or two channels - as it was.  wav_kernel<FMT, WIDTH> (fmt != 0) decodes what
+// else a RIFF/WAVE file holds - 24-bit PCM, binary32 / binary64, G.711 A-law and mu-law - with the channel count, 1 .. 8, as a
+// runtime loop; its arithmetic is wavio.read_any's (include/pdse.h lists it):
+//   s24      the three bytes sign-extended, / 8388608 (exact)
+//   binary32 the bits as they are, moved as an integer (no arithmetic touches a mono sample: NaN payloads survive)
+//   binary64 one conversion to fp32, round to nearest even (v_cvt_f32_f64); beyond the fp32 range: infinity
+//   G.711    the 16-bit linear value of the code, / 32768
+//   mix      fp32 sum of the channels in channel order, one division by (float)ch (correctly rounded: hipcc's default)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -112,11 +121,117 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_kernel(const pdse_resample_
   row[n] = (float)acc;
 }
 
+// ---- fmt != 0: the encodings of RIFF/WAVE beyond one- and two-channel integer PCM ------------------------------------------
+template <int FMT, int WIDTH>
+__device__ __forceinline__ float wav_sample(const uint8_t* p) {
+  if constexpr (FMT == PDSE_WAV_INT && WIDTH == 3) {
+    const uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+    return (float)((int32_t)(v << 8) >> 8) / 8388608.0f;
+  } else if constexpr (FMT == PDSE_WAV_INT) {
+    return pcm_sample<WIDTH>(p);
+  } else if constexpr (FMT == PDSE_WAV_FLOAT && WIDTH == 4) {
+    return __uint_as_float((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+  } else if constexpr (FMT == PDSE_WAV_FLOAT) {
+    uint64_t v = 0;
+    for (int i = 7; i >= 0; --i) v = (v << 8) | (uint64_t)p[i];
+    return (float)__longlong_as_double((long long)v);
+  } else if constexpr (FMT == PDSE_WAV_ULAW) {
+    const int u = ~(int)p[0] & 0xFF;
+    const int mag = ((((u & 15) << 3) + 0x84) << ((u >> 4) & 7)) - 0x84;
+    return (float)((u & 0x80) ? -mag : mag) / 32768.0f;
+  } else {
+    const int a = (int)p[0] ^ 0x55, e = (a >> 4) & 7, m = a & 15;
+    const int mag = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
+    return (float)((a & 0x80) ? mag : -mag) / 32768.0f;
+  }
+}
+
+template <int FMT, int WIDTH>
+struct WavFrame {
+  __device__ __forceinline__ float operator()(const pdse_resample_desc& d, int64_t base, int64_t k) const {
+    const int ch = d.ch;
+    const int64_t at = base + k * (int64_t)(WIDTH * ch);
+    if (at < 0 || at + WIDTH * ch > d.pcm_bytes) return 0.0f;
+    const uint8_t* p = d.pcm + at;
+    float s = wav_sample<FMT, WIDTH>(p);
+    if (ch == 1) return s;
+    for (int c = 1; c < ch; ++c) s = s + wav_sample<FMT, WIDTH>(p + c * WIDTH);
+    return s / (float)ch;
+  }
+};
+
+// resample_kernel's steps behind the decode - zero tail, ratio 1, the LDS window, the float64 polyphase sum - statement for statement,
+// with the frame decode as a parameter: frame(d, base, k) is frame k of the utterance at byte `base`, mixed to mono.  resample_kernel
+// itself is kept as written rather than rebuilt on this function: going through it changes the register allocation of the six
+// instantiations fmt == 0 launches, and those are to stay the code they were.
+template <class Frame>
+__device__ __forceinline__ void resample_block(const pdse_resample_desc& d, const int jmax, const int win, const Frame& frame) {
+  extern __shared__ float xs[];   // [win] decoded samples k_lo .. k_lo + win - 1 (0 outside the utterance)
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int64_t n0 = (int64_t)blockIdx.x * RS_BLOCK;
+  const int64_t n_in = d.n_in[b];
+  const int64_t base = d.offs[b];
+  const int64_t up = d.up, down = d.down;
+  const int64_t n_full = (n_in * up + down - 1) / down;
+  const int64_t n_out = n_full < d.Lmax ? n_full : (int64_t)d.Lmax;
+  float* const row = d.out + (int64_t)b * d.Lmax;
+  const int64_t n = n0 + tid;
+  if (n0 >= n_out || n_in < 1) {   // the whole block lies in the row's zero tail (uniform over the workgroup)
+    if (n < d.Lmax) row[n] = 0.0f;
+    return;
+  }
+  if (up == down) {                // ratio 1: decode and mix only
+    if (n < d.Lmax) row[n] = n < n_out ? frame(d, base, n) : 0.0f;
+    return;
+  }
+  // the window of this block: the first output's k_c - jmax up to the last output's k_c + jmax
+  const int64_t k_lo = (n0 * down) / up - jmax;
+  for (int i = tid; i < win; i += RS_BLOCK) {
+    const int64_t k = k_lo + i;
+    xs[i] = (k >= 0 && k < n_in) ? frame(d, base, k) : 0.0f;
+  }
+  __syncthreads();
+  if (n >= d.Lmax) return;
+  if (n >= n_out) {
+    row[n] = 0.0f;
+    return;
+  }
+  const int64_t q = n * down;
+  const int64_t k_c = q / up;
+  const int r = (int)(q - k_c * up);
+  const int half = d.half, iup = d.up;
+  const int c = (int)(k_c - k_lo);            // position of k_c in the window: jmax <= c < win - jmax
+  // j runs over the terms that pass both tests, in ascending order: the sum is the one the host forms
+  int j_lo = -jmax, j_hi = jmax;
+  if (k_c - j_hi < 0) j_hi = (int)k_c;                        // k_c - j >= 0
+  if (k_c - j_lo >= n_in) j_lo = (int)(k_c - n_in + 1);       // k_c - j < n_in
+  double acc = 0.0;
+  for (int j = j_lo; j <= j_hi; ++j) {
+    const int off = r + j * iup;
+    if (off < -half || off > half) continue;
+    const double p = d.taps[off + half] * (double)xs[c - j];
+    acc = acc + p;
+  }
+  row[n] = (float)acc;
+}
+
+template <int FMT, int WIDTH>
+__global__ __launch_bounds__(RS_BLOCK) void wav_kernel(const pdse_resample_desc d, const int jmax, const int win) {
+  resample_block(d, jmax, win, WavFrame<FMT, WIDTH>());
+}
+
 template <int WIDTH, int CH>
 void launch(const pdse_resample_desc& d, int jmax, int win, hipStream_t s) {
   const dim3 grid((unsigned)((d.Lmax + RS_BLOCK - 1) / RS_BLOCK), (unsigned)d.B);
   const size_t lds = d.up == d.down ? 0 : (size_t)win * sizeof(float);
   hipLaunchKernelGGL((resample_kernel<WIDTH, CH>), grid, dim3(RS_BLOCK), lds, s, d, jmax, win);
+}
+
+template <int FMT, int WIDTH>
+void launch_wav(const pdse_resample_desc& d, int jmax, int win, hipStream_t s) {
+  const dim3 grid((unsigned)((d.Lmax + RS_BLOCK - 1) / RS_BLOCK), (unsigned)d.B);
+  const size_t lds = d.up == d.down ? 0 : (size_t)win * sizeof(float);
+  hipLaunchKernelGGL((wav_kernel<FMT, WIDTH>), grid, dim3(RS_BLOCK), lds, s, d, jmax, win);
 }
 
 }  // namespace
@@ -125,8 +240,17 @@ int pdse_resample_launch(const pdse_resample_desc* d, hipStream_t s) {
   REQ(d && d->pcm && d->offs && d->n_in_host && d->n_in && d->out, "resample: null pointer");
   REQ(d->B >= 1 && d->B <= 65535, "resample: B < 1 (or above 65535)");
   REQ(d->up >= 1 && d->down >= 1 && d->half >= 0, "resample: up < 1, down < 1 or half < 0");
-  REQ(d->width == 1 || d->width == 2 || d->width == 4, "resample: width must be 1, 2 or 4 bytes");
-  REQ(d->ch == 1 || d->ch == 2, "resample: ch must be 1 or 2");
+  if (d->fmt == 0) {
+    REQ(d->width == 1 || d->width == 2 || d->width == 4, "resample: width must be 1, 2 or 4 bytes");
+    REQ(d->ch == 1 || d->ch == 2, "resample: ch must be 1 or 2");
+  } else {
+    const int w = d->width;
+    REQ(d->fmt >= PDSE_WAV_INT && d->fmt <= PDSE_WAV_ULAW, "resample: unknown fmt (0 or PDSE_WAV_INT, _FLOAT, _ALAW, _ULAW)");
+    REQ(d->fmt != PDSE_WAV_INT || (w >= 1 && w <= 4), "resample: fmt PDSE_WAV_INT takes a width of 1, 2, 3 or 4 bytes");
+    REQ(d->fmt != PDSE_WAV_FLOAT || w == 4 || w == 8, "resample: fmt PDSE_WAV_FLOAT takes a width of 4 or 8 bytes");
+    REQ((d->fmt != PDSE_WAV_ALAW && d->fmt != PDSE_WAV_ULAW) || w == 1, "resample: fmt PDSE_WAV_ALAW / _ULAW takes a width of 1 byte");
+    REQ(d->ch >= 1 && d->ch <= PDSE_WAV_MAX_CH, "resample: with fmt != 0 ch must be 1 .. 8");
+  }
   REQ(d->Lmax >= 1 && d->pcm_bytes >= 0, "resample: Lmax < 1 or pcm_bytes < 0");
   for (int b = 0; b < d->B; ++b) {
     REQ(d->n_in_host[b] >= 1, "resample: n_in < 1");
@@ -138,6 +262,19 @@ int pdse_resample_launch(const pdse_resample_desc* d, hipStream_t s) {
   const int64_t win = ((int64_t)(RS_BLOCK - 1) * d->down) / d->up + 2 * (int64_t)jmax + 2;
   REQ(d->up == d->down || win * (int64_t)sizeof(float) <= RS_LDS_MAX,
       "resample: the input window of one block of outputs does not fit the LDS budget (down / up or half too large)");
+  if (d->fmt != 0) {
+    switch (d->fmt * 16 + d->width) {
+      case PDSE_WAV_INT * 16 + 1: launch_wav<PDSE_WAV_INT, 1>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_INT * 16 + 2: launch_wav<PDSE_WAV_INT, 2>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_INT * 16 + 3: launch_wav<PDSE_WAV_INT, 3>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_INT * 16 + 4: launch_wav<PDSE_WAV_INT, 4>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_FLOAT * 16 + 4: launch_wav<PDSE_WAV_FLOAT, 4>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_FLOAT * 16 + 8: launch_wav<PDSE_WAV_FLOAT, 8>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_ALAW * 16 + 1: launch_wav<PDSE_WAV_ALAW, 1>(*d, jmax, (int)win, s); break;
+      default: launch_wav<PDSE_WAV_ULAW, 1>(*d, jmax, (int)win, s); break;
+    }
+    return pdse_check_launch("resample");
+  }
   const int key = d->width * 4 + d->ch;
   switch (key) {
     case 1 * 4 + 1: launch<1, 1>(*d, jmax, (int)win, s); break;

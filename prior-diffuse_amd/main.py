@@ -51,6 +51,10 @@ def parse_args_and_config(argv=None):
                    help="(not a flag of the reference) --generate: keep this many files (2 .. 4) in flight on HIP streams of their own, each "
                         "verified on the device without a device-wide synchronisation (ComplexDDPMTrainer.enhance_stream); same files, "
                         "same noise; not with --batch or --audit-range; default 1: one file at a time")
+    p.add_argument("--all-wav", action="store_true",
+                   help="(not a flag of the reference) --generate: also read 24-bit PCM, IEEE float, G.711 A-law / mu-law and "
+                        "WAVE_FORMAT_EXTENSIBLE files (up to 8 channels on the device); default: 8/16/32-bit integer PCM, other "
+                        "files are skipped with a warning")
     args = p.parse_args(argv)
     args.log = os.path.join(args.assets, "log", args.doc)
     args.checkpoint = os.path.join(args.assets, "checkpoint", args.doc)

@@ -239,29 +239,31 @@ def pair_files(refdir, degdir):
     return list(zip(ref, deg))
 
 
-def load_pairs(pairs):
-    """Read every pair at 16 kHz; both files of a pair must be equally long (:513).  Returns {length: [(clean, deg), ...]}."""
+def load_pairs(pairs, formats="pcm"):
+    """Read every pair at 16 kHz; both files of a pair must be equally long (:513).  Returns {length: [(clean, deg), ...]}.
+    formats="all": ``wavio.read_any`` instead of ``wavio.read_wav`` (24-bit, float, G.711, extensible headers)."""
     from . import wavio
 
+    read = {"pcm": wavio.read_wav, "all": wavio.read_any}[formats]
     groups = {}
     for r, g in pairs:
-        c, p = wavio.read_wav(r, FS), wavio.read_wav(g, FS)
+        c, p = read(r, FS), read(g, FS)
         assert len(c) == len(p), "c.shape=%r, p.shape=%r (%s, %s)" % (c.shape, p.shape, r, g)
         groups.setdefault(len(c), []).append((c, p))
     return groups
 
 
-def load_pairs_device(pairs, device, chunk=32):
+def load_pairs_device(pairs, device, chunk=32, formats="pcm"):
     """``load_pairs`` with the decoding and the 16 kHz conversion on the device (``wavdev.load``: the same samples bit for
     bit): {length: [(clean, deg), ...]} of 1-D device tensors, ``chunk`` pairs per launch.  The rows are copies of their own
-    length: a chunk's padded [chunk, Lmax] tensors are released before the next chunk is loaded."""
+    length: a chunk's padded [chunk, Lmax] tensors are released before the next chunk is loaded.  formats: ``wavdev.load``'s."""
     from . import wavdev
 
     groups = {}
     for i in range(0, len(pairs), chunk):
         part = pairs[i:i + chunk]
-        c, cl = wavdev.load([r for r, _ in part], device, FS)
-        p, pl = wavdev.load([g for _, g in part], device, FS)
+        c, cl = wavdev.load([r for r, _ in part], device, FS, formats=formats)
+        p, pl = wavdev.load([g for _, g in part], device, FS, formats=formats)
         for k, (r, g) in enumerate(part):
             assert cl[k] == pl[k], "c.shape=%r, p.shape=%r (%s, %s)" % ((cl[k],), (pl[k],), r, g)
             groups.setdefault(cl[k], []).append((c[k, :cl[k]].clone(), p[k, :pl[k]].clone()))
@@ -276,15 +278,18 @@ def main(argv=None, device=None, batch=32):
     stoi = "--stoi" in argv
     if stoi:
         argv.remove("--stoi")
+    formats = "all" if "--all-wav" in argv else "pcm"
+    if formats == "all":
+        argv.remove("--all-wav")
     if len(argv) != 2:
-        print("usage: python -m prior_diffuse_amd.metrics [--stoi] REF_DIR DEG_DIR")
+        print("usage: python -m prior_diffuse_amd.metrics [--stoi] [--all-wav] REF_DIR DEG_DIR")
         return 2
     pairs = pair_files(argv[0], argv[1])
     if not pairs:
         print("no *.wav files in %s" % argv[0])
         return 1
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    groups = load_pairs_device(pairs, device, batch)
+    groups = load_pairs_device(pairs, device, batch, formats=formats)
     rows = []
     for length in sorted(groups):
         items = groups[length]

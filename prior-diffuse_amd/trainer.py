@@ -50,9 +50,10 @@ def _inflight_arg(inflight):
 class ComplexDDPMTrainer(object):
     MAX_PLANS = 3   # recorded (B, T) geometries kept alive (least recently used first out); weights are shared by all
     masked_prior = False   # exact ragged batches of the DB-AIAT priors on the length-masked kernels (constructor)
+    wav_formats = "pcm"    # what generate_wav opens: "pcm" (the wave module's integer PCM) or "all" (constructor)
 
     def __init__(self, args, config, device=None, prior_state_dict=None, ddpm_state_dict=None, params=None, exclusive=None,
-                 dtype=None, split=None, audit=None, masked_prior=None):
+                 dtype=None, split=None, audit=None, masked_prior=None, wav_formats=None):
         """args: .retrain .joint .draw .sigma .checkpoint .generated_wav
         config: .model.name, .train.{fft_num, win_size, win_shift, feat_type}
         Weights come from ``<args.checkpoint>/best_checkpoint.pth`` under the reference's
@@ -78,7 +79,18 @@ class ComplexDDPMTrainer(object):
         (``aia_complex_trans_ri``, ``dual_aia_trans_merge_crm``): their ragged plans are recorded with the length-masked attention,
         GRU, GroupNorm and AHAM kernels (``SamplerPipeline(ragged=True, masked_prior=True)``), and every utterance comes out as
         if enhanced alone, as for the other priors.  Dense passes are not touched.  None: ``args.masked_prior`` when the CLI set
-        it (``main.py --masked-prior``), else False: exact ragged batches of these priors raise ValueError as before."""
+        it (``main.py --masked-prior``), else False: exact ragged batches of these priors raise ValueError as before.
+        wav_formats: what the three ``generate_wav`` loops open.  "pcm": 8-, 16- and 32-bit integer PCM in a plain header, as
+        the ``wave`` module reads it; everything else is skipped with a warning.  "all": also 24-bit PCM, IEEE float (32 and
+        64 bits), G.711 A-law and mu-law and WAVE_FORMAT_EXTENSIBLE headers, decoded on the device
+        (``wavdev.load(formats="all")``, the waveform of ``wavio.read_any``); a float file with a non-finite sample is skipped
+        with the same warning before its x_T is drawn.  None: "all" when the CLI set ``args.all_wav`` (``main.py --all-wav``),
+        else "pcm"."""
+        if wav_formats is None:
+            wav_formats = "all" if getattr(args, "all_wav", False) else "pcm"
+        if wav_formats not in ("pcm", "all"):
+            raise ValueError("wav_formats must be 'pcm' or 'all'")
+        self.wav_formats = wav_formats
         self.masked_prior = bool(getattr(args, "masked_prior", False) if masked_prior is None else masked_prior)
         if split is None:
             split = getattr(args, "split", None)
@@ -510,7 +522,7 @@ class ComplexDDPMTrainer(object):
         with torch.no_grad():
             for path in sorted(glob.glob(data_path + "/*.wav")):
                 try:
-                    wav = wavdev.load([path], self.device, 16000)[0]            # [1, L] on the device, read_wav's bits
+                    wav = wavdev.load([path], self.device, 16000, formats=self.wav_formats)[0]            # [1, L] on the device, read_wav's bits
                 except (ValueError, EOFError, wavio.wave.Error) as e:
                     logging.warning("skipping %s: %s", path, e)
                     continue
@@ -534,7 +546,7 @@ class ComplexDDPMTrainer(object):
         def files():
             for path in sorted(glob.glob(data_path + "/*.wav")):
                 try:
-                    wav = wavdev.load([path], self.device, 16000)[0]            # [1, L] on the device, read_wav's bits
+                    wav = wavdev.load([path], self.device, 16000, formats=self.wav_formats)[0]            # [1, L] on the device, read_wav's bits
                 except (ValueError, EOFError, wavio.wave.Error) as e:
                     logging.warning("skipping %s: %s", path, e)
                     continue
@@ -558,14 +570,14 @@ class ComplexDDPMTrainer(object):
         """[(path, wav [len] on the device)] of the readable files of ``paths``, in order; the others are logged and skipped."""
         errors = (ValueError, EOFError, wavio.wave.Error)
         try:
-            wav, lens = wavdev.load(paths, self.device, 16000)
+            wav, lens = wavdev.load(paths, self.device, 16000, formats=self.wav_formats)
             return [(p, wav[i, :lens[i]]) for i, p in enumerate(paths)]
         except errors:
             pass                                     # at least one file cannot be read: find out which, one by one
         out = []
         for p in paths:
             try:
-                wav, lens = wavdev.load([p], self.device, 16000)
+                wav, lens = wavdev.load([p], self.device, 16000, formats=self.wav_formats)
                 out.append((p, wav[0, :lens[0]]))
             except errors as e:
                 logging.warning("skipping %s: %s", p, e)

@@ -10,7 +10,11 @@ Files of one call that differ in rate or format take one launch per (channels, w
 more than two channels, a file without frames, a rate pair whose input window per workgroup passes the kernel's 64 KB of LDS
 (input rates above about 900 kHz) - is read with ``wavio.read_wav`` and uploaded, as before.  There is no CPU
 fallback for the kernel itself.  The tap table of a rate pair is uploaded once per device and kept; nothing else persists
-between calls."""
+between calls.
+
+``load(..., formats="all")`` and ``decode(..., fmt=WAV_*)`` (opt-in; the defaults are the paragraph above, bit for bit) read what
+else a RIFF/WAVE file holds - 24-bit PCM, IEEE float of 32 and 64 bits, G.711 A-law and mu-law, WAVE_FORMAT_EXTENSIBLE headers, up
+to eight channels - with ``wavio.read_frames`` and the second kernel of csrc/resample.hip; the oracle is then ``wavio.read_any``."""
 import numpy as np
 
 from . import _lib as L
@@ -30,10 +34,11 @@ def _device_taps(device, sr_in, sr_out):
     return _TAPS[key]
 
 
-def kernel_covers(channels, n_frames, rate, sr=16000):
-    """Whether csrc/resample.hip takes such a file: one or two channels, at least one frame, and an input window of one workgroup's
+def kernel_covers(channels, n_frames, rate, sr=16000, max_channels=2):
+    """Whether csrc/resample.hip takes such a file: one or two channels (``max_channels``: ``L.WAV_MAX_CH`` for the kernel of
+    fmt != 0), at least one frame, and an input window of one workgroup's
     outputs ((RESAMPLE_BLOCK - 1) down / up + 2 jmax + 2 fp32 samples, include/pdse.h) within 64 KB of LDS."""
-    if channels > 2 or n_frames < 1:
+    if channels > max_channels or n_frames < 1:
         return False
     up, down, half = _ratio(rate, sr)
     return up == down or 4 * ((L.RESAMPLE_BLOCK - 1) * down // up + 2 * (half // up + 1) + 2) <= 64 * 1024
@@ -48,11 +53,14 @@ def _ratio(rate, sr, half_width=16):
     return up, down, half_width * max(up, down)
 
 
-def decode(pcm_list, channels, width, rate, device, sr=16000):
+def decode(pcm_list, channels, width, rate, device, sr=16000, fmt=0):
     """pcm_list: the interleaved little-endian PCM frames of B utterances of one format, each a uint8 array (or bytes) of whole
     frames (``wavio.read_pcm``); channels 1 or 2, width 1, 2 or 4 bytes, every utterance at least one frame long.
     Returns (wav, lens): wav [B, Lmax] fp32 on ``device`` with utterance b in wav[b, :lens[b]] - ``wavio.read_wav``'s samples bit
-    for bit - and zeros behind it.  Two uploads and one launch on the current stream; asynchronous."""
+    for bit - and zeros behind it.  Two uploads and one launch on the current stream; asynchronous.
+    fmt (default 0: the above): ``L.WAV_INT`` (width 1 .. 4), ``L.WAV_FLOAT`` (width 4 or 8), ``L.WAV_ALAW`` or ``L.WAV_ULAW``
+    (width 1) with 1 .. 8 channels takes the kernel of the other encodings (``wavio.read_frames``); the rows are then
+    ``wavio.read_any``'s bits.  The library refuses every other combination before the launch."""
     import torch
 
     device = torch.device(device)
@@ -88,18 +96,26 @@ def decode(pcm_list, channels, width, rate, device, sr=16000):
         d.pcm, d.offs, d.n_in, d.n_in_host = pcm_dev.data_ptr(), meta_dev.data_ptr(), meta_dev.data_ptr() + 8 * B, n_in32.ctypes.data
         d.taps, d.out = (taps.data_ptr() if taps is not None else None), out.data_ptr()
         d.pcm_bytes, d.B, d.Lmax = int(pcm.size), B, Lmax
-        d.up, d.down, d.half, d.width, d.ch = up, down, half, int(width), int(channels)
+        d.up, d.down, d.half, d.width, d.ch, d.fmt = up, down, half, int(width), int(channels), int(fmt)
         L.launch(d, torch.cuda.current_stream(device).cuda_stream, device=device)
     return out, lens
 
 
-def load(paths, device, sr=16000):
+def load(paths, device, sr=16000, formats="pcm"):
     """Read wav files and bring them to ``sr`` mono fp32 on the device: (wav [B, Lmax], lens) with file b in wav[b, :lens[b]],
     equal to ``wavio.read_wav(paths[b], sr)`` bit for bit, zeros behind it.  Raises what ``wavio.read_wav`` raises for a file it
-    cannot read."""
+    cannot read.
+    formats="all": the files are opened with ``wavio.read_frames`` (24-bit, float, G.711, extensible headers, up to 8 channels on
+    the device) and every row is ``wavio.read_any``'s; only files with more channels, without frames or with a rate pair beyond the
+    kernel's window take ``read_any`` on the host.  A float file whose decoded samples are not all finite raises ValueError
+    naming it (one ``isfinite().all()`` per float row, a synchronisation; integer files are not looked at)."""
     import torch
 
     device = torch.device(device)
+    if formats == "all":
+        return _load_all(paths, device, sr)
+    if formats != "pcm":
+        raise ValueError("formats must be 'pcm' or 'all', got %r" % (formats,))
     rows, groups = [None] * len(paths), {}
     for i, path in enumerate(paths):
         frames, n, ch, width, rate = wavio.read_pcm(path)
@@ -119,3 +135,40 @@ def load(paths, device, sr=16000):
     for i, r in enumerate(rows):
         out[i, :lens[i]] = r
     return out, lens
+
+
+def _load_all(paths, device, sr):
+    """``load(formats="all")``: one launch per (fmt, channels, width, rate)."""
+    import torch
+
+    rows, groups = [None] * len(paths), {}
+    for i, path in enumerate(paths):
+        frames, n, ch, width, rate, fmt = wavio.read_frames(path)
+        if not kernel_covers(ch, n, rate, sr, max_channels=L.WAV_MAX_CH):
+            rows[i] = torch.from_numpy(wavio.read_any(path, sr)).to(device)
+            if fmt == wavio.WAV_FLOAT:
+                _finite(rows[i], path)
+        else:
+            groups.setdefault((fmt, ch, width, rate), []).append((i, frames))
+    one = len(groups) == 1 and all(r is None for r in rows)
+    for (fmt, ch, width, rate), items in groups.items():
+        wav, lens = decode([f for _, f in items], ch, width, rate, device, sr, fmt=fmt)
+        if fmt == wavio.WAV_FLOAT:
+            for (i, _), row, n in zip(items, wav, lens):
+                _finite(row[:n], paths[i])
+        if one:
+            return wav, lens
+        for (i, _), row, n in zip(items, wav, lens):
+            rows[i] = row[:n]
+    lens = [int(r.numel()) for r in rows]
+    out = torch.zeros(len(rows), max(lens + [0]), dtype=torch.float32, device=device)
+    for i, r in enumerate(rows):
+        out[i, :lens[i]] = r
+    return out, lens
+
+
+def _finite(row, path):
+    import torch
+
+    if not bool(torch.isfinite(row).all()):
+        raise ValueError("%s: float samples that are not finite" % path)
