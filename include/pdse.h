@@ -1071,6 +1071,41 @@ int pdse_range_hist(const pdse_range_desc* d, pdse_stream_t s);
  * forms 1..4.)  Returns the previous setting, or -2 for any other form. */
 int pdse_bglu_set_form(int form);
 
+/* Wav back end (csrc/wavout.hip, additive within ABI 9): the way back of pdse_resample_desc.  B fp32 mono waveforms at 16 kHz,
+ * x[B][Lmax] with n_in[b] valid samples in row b, are converted to the rate of the files they came from, encoded and interleaved
+ * into ch equal channels (1 .. PDSE_WAV_MAX_CH: every channel carries the same signal), in one launch on stream s; no host
+ * synchronisation, no atomics.  Plain arguments: no descriptor and no operator kind, so the call cannot be recorded in a plan.
+ * The arithmetic is that of prior-diffuse_amd/wavio.py (resample + encode), operation for operation, so out is bit-identical to
+ * the host path:
+ *   convert y[b][n] = sum over j = -jmax .. jmax (ascending), jmax = half / up + 1, of taps[r + j up + half] * x[b][k_c - j] with
+ *           q = n down, k_c = q / up, r = q % up, skipping terms with |r + j up| > half or k_c - j outside [0, n_in[b]);
+ *           float64, product rounded before the add (no fused multiply-add), accumulator started at +0.0, one cast to fp32,
+ *           64-bit positions.  up == down (ratio 1): y = x, taps may be null.  taps: the 2 half + 1 float64 values of wavio.taps
+ *           for the pair (16000, rate); up = rate / g, down = 16000 / g.
+ *   encode  PDSE_WAV_INT, width 2, 3 or 4: v = rint(clamp(float64(y), -1, 1 - 2^-(8 width - 1)) * 2^(8 width - 1)) (the product is
+ *           exact; halves round to even), width bytes, little endian, two's complement.  NaN is written as 0.  A sample is
+ *           clipped when the clamp changed it; NaN and the infinities are.
+ *           PDSE_WAV_FLOAT, width 4: the binary32 bits of y as they are; nothing is clamped or counted.
+ * Row b of out[B][stride] holds the first n_keep[b] frames, n_keep[b] ch width bytes, followed by zeros up to stride; every byte of
+ * out is written, and a row may start at any byte.  0 <= n_keep[b] <= ceil(n_in[b] up / down): a file is cut to the frames its
+ * source holds.  A workgroup encodes PDSE_RESAMPLE_BLOCK consecutive frames of a row from an input window staged in LDS and
+ * writes the number of clipped samples among its kept frames (counted once, not per channel) to
+ * clipped[b][k], k < blocks = ceil(stride / (PDSE_RESAMPLE_BLOCK ch width)); the caller sums a row.  A row does not depend on B or on its
+ * place in the batch.  n_in_host and n_keep_host are the host copies of n_in and n_keep, read by the call itself: everything is
+ * validated before the launch and without a device - fmt and width as above, ch, n_in >= 1 and <= Lmax, n_keep, stride at least
+ * the longest row's bytes, and a rate pair whose window of (PDSE_RESAMPLE_BLOCK - 1) down / up + 2 jmax + 2 samples fits, with the
+ * 8 KB image of a block's bytes, in 64 KB of LDS. */
+int pdse_wav_encode(const float* x,              /* device [B][Lmax] */
+                    const int32_t* n_in_host,    /* host [B] */
+                    const int32_t* n_keep_host,  /* host [B] */
+                    const int32_t* n_in,         /* device [B] */
+                    const int32_t* n_keep,       /* device [B] */
+                    const double* taps,          /* device [2 half + 1], or NULL when up == down */
+                    uint8_t* out,                /* device [B][stride] */
+                    int32_t* clipped,            /* device [B][blocks] */
+                    int64_t stride, int32_t B, int32_t Lmax, int32_t up, int32_t down, int32_t half, int32_t fmt, int32_t width,
+                    int32_t ch, pdse_stream_t s);
+
 /* plans: a recorded operator sequence replayed by one call (and capturable in a hipGraph) */
 typedef struct pdse_plan pdse_plan;
 int pdse_plan_create(pdse_plan** out);

@@ -275,6 +275,7 @@ RESAMPLE_BLOCK = 256      # PDSE_RESAMPLE_BLOCK: outputs per workgroup
 # pdse_resample_desc.fmt: 0 is the integer-PCM operator as it was (width 1 / 2 / 4, one or two channels); the others (PDSE_WAV_*)
 WAV_INT, WAV_FLOAT, WAV_ALAW, WAV_ULAW = 1, 2, 3, 4
 WAV_MAX_CH = 8            # PDSE_WAV_MAX_CH: channels the kernel of fmt != 0 mixes
+WAVOUT_IMAGE_BYTES = RESAMPLE_BLOCK * WAV_MAX_CH * 4 + 16     # csrc/wavout.hip: LDS image of a block's bytes, beside its input window
 
 METRICS_OFF_WIN, METRICS_OFF_BASIS = 0, 512
 METRICS_OFF_CRIT = METRICS_OFF_BASIS + 480 * 1024
@@ -351,6 +352,7 @@ EXPORTS = [
     "pdse_plan_run_range",
     "pdse_plan_build_graph", "pdse_plan_launch_graph", "pdse_plan_time_ops", "pdse_plan_time_tag",
     "pdse_plan_destroy", "pdse_plan_load", "pdse_plan_region", "pdse_prior_forward", "pdse_eps_forward", "pdse_enhance",
+    "pdse_wav_encode",
 ] + [name for _, _, name in OPS]
 
 
@@ -406,6 +408,8 @@ def load():
                                        C.POINTER(C.c_int)]
     lib.pdse_plan_destroy.argtypes = [C.c_void_p]
     lib.pdse_plan_destroy.restype = None
+    lib.pdse_wav_encode.argtypes = [_fp] * 8 + [_i64] + [_i32] * 8 + [C.c_void_p]
+    lib.pdse_wav_encode.restype = C.c_int
     if lib.pdse_abi_version() != ABI_VERSION:
         raise PdseError("libpdse.so ABI %d != binding ABI %d" % (lib.pdse_abi_version(), ABI_VERSION))
     for kind, typ in DESC_TYPES.items():
@@ -432,6 +436,20 @@ def launch(desc, stream=0, device=None):
         on = torch.cuda.device(device)
     with on:
         check(getattr(lib, name)(C.byref(desc), C.c_void_p(stream)), name)
+
+
+def wav_encode(x, n_in_host, n_keep_host, n_in, n_keep, taps, out, clipped, stride, B, Lmax, up, down, half, fmt, width, ch,
+               stream=0, device=None):
+    """pdse_wav_encode (include/pdse.h: the wav back end, csrc/wavout.hip): pointers as integers, plain arguments."""
+    lib = load()
+    on = contextlib.nullcontext()
+    if device is not None:
+        import torch
+
+        on = torch.cuda.device(device)
+    with on:
+        check(lib.pdse_wav_encode(x, n_in_host, n_keep_host, n_in, n_keep, taps, out, clipped, int(stride), int(B), int(Lmax),
+                                  int(up), int(down), int(half), int(fmt), int(width), int(ch), C.c_void_p(stream)), "pdse_wav_encode")
 
 
 class Plan:

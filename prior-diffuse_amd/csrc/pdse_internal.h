@@ -74,5 +74,9 @@ int pdse_gconv4_pair_check(const pdse_gconv_desc* d, const pdse_gconv_desc* e); 
 int pdse_gconv4_pair_launch(const pdse_gconv_desc* d, const pdse_gconv_desc* e, hipStream_t s);
 int pdse_stoi_launch(const pdse_metrics_desc* d, hipStream_t s);   /* csrc/stoi.hip, reached through pdse_metrics_launch (measures) */
 int pdse_gru3_launch(const pdse_gru_desc* d, hipStream_t s);   /* csrc/gru3.hip, reached through pdse_gru_launch */
-int pdse_range_validate(const pdse_range_desc* d);                 /* reads the row table back and checks it (direct launches, plan_add) */
+// csrc/wavout.hip: the wav back end behind pdse_wav_encode (plain arguments: no descriptor, no operator kind, not recordable in a plan)
+int pdse_wavout_launch(const float* x, const int32_t* n_in_host, const int32_t* n_keep_host, const int32_t* n_in, const int32_t* n_keep,
+                       const double* taps, uint8_t* out, int32_t* clipped, int64_t stride, int32_t B, int32_t Lmax, int32_t up,
+                       int32_t down, int32_t half, int32_t fmt, int32_t width, int32_t ch, hipStream_t s);
+int pdse_range_validate(const pdse_range_desc* d);               /* reads the row table back and checks it (direct launches, plan_add) */
 #endif

@@ -55,6 +55,10 @@ def parse_args_and_config(argv=None):
                    help="(not a flag of the reference) --generate: also read 24-bit PCM, IEEE float, G.711 A-law / mu-law and "
                         "WAVE_FORMAT_EXTENSIBLE files (up to 8 channels on the device); default: 8/16/32-bit integer PCM, other "
                         "files are skipped with a warning")
+    p.add_argument("--keep-format", action="store_true",
+                   help="(not a flag of the reference) --generate: write every file at its source's rate, length and channel count, in "
+                        "its source's encoding (16/24/32-bit PCM, float as binary32, 8-bit and G.711 as 16-bit PCM; every channel "
+                        "carries the enhanced mono signal), encoded on the device; clipped files are logged; default: 16 kHz, 16-bit, mono")
     args = p.parse_args(argv)
     args.log = os.path.join(args.assets, "log", args.doc)
     args.checkpoint = os.path.join(args.assets, "checkpoint", args.doc)

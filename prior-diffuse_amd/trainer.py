@@ -51,9 +51,10 @@ class ComplexDDPMTrainer(object):
     MAX_PLANS = 3   # recorded (B, T) geometries kept alive (least recently used first out); weights are shared by all
     masked_prior = False   # exact ragged batches of the DB-AIAT priors on the length-masked kernels (constructor)
     wav_formats = "pcm"    # what generate_wav opens: "pcm" (the wave module's integer PCM) or "all" (constructor)
+    wav_out = "pcm16"      # what generate_wav writes: "pcm16" (16 kHz, 16-bit, mono) or "source" (the file's own rate and format)
 
     def __init__(self, args, config, device=None, prior_state_dict=None, ddpm_state_dict=None, params=None, exclusive=None,
-                 dtype=None, split=None, audit=None, masked_prior=None, wav_formats=None):
+                 dtype=None, split=None, audit=None, masked_prior=None, wav_formats=None, wav_out=None):
         """args: .retrain .joint .draw .sigma .checkpoint .generated_wav
         config: .model.name, .train.{fft_num, win_size, win_shift, feat_type}
         Weights come from ``<args.checkpoint>/best_checkpoint.pth`` under the reference's
@@ -85,7 +86,20 @@ class ComplexDDPMTrainer(object):
         64 bits), G.711 A-law and mu-law and WAVE_FORMAT_EXTENSIBLE headers, decoded on the device
         (``wavdev.load(formats="all")``, the waveform of ``wavio.read_any``); a float file with a non-finite sample is skipped
         with the same warning before its x_T is drawn.  None: "all" when the CLI set ``args.all_wav`` (``main.py --all-wav``),
-        else "pcm"."""
+        else "pcm".
+        wav_out: what the three ``generate_wav`` loops write.  "pcm16": 16 kHz, 16-bit, mono, whatever the source was
+        (``wavio.write_wav``, as ever).  "source": every file at its source's rate, frame count and channel count, in the source's
+        encoding where that holds an enhanced signal - 16-, 24- and 32-bit PCM as themselves, binary32 and binary64 as binary32,
+        8-bit PCM and G.711 as 16-bit PCM (``wavio.target_of``) - converted, clamped, encoded and interleaved on the device
+        (``wavdev.encode``: ``wavio.resample`` + ``wavio.encode`` byte for byte).  The network enhances the mono mix, so every
+        channel of a written file carries the same signal.  A file in which the integer clamp changed samples - an enhancer's
+        output is not bounded by +-1 - is written and logged with one warning that names it and the count.  None: "source" when
+        the CLI set ``args.keep_format`` (``main.py --keep-format``), else "pcm16"."""
+        if wav_out is None:
+            wav_out = "source" if getattr(args, "keep_format", False) else "pcm16"
+        if wav_out not in ("pcm16", "source"):
+            raise ValueError("wav_out must be 'pcm16' or 'source'")
+        self.wav_out = wav_out
         if wav_formats is None:
             wav_formats = "all" if getattr(args, "all_wav", False) else "pcm"
         if wav_formats not in ("pcm", "all"):
@@ -528,16 +542,44 @@ class ComplexDDPMTrainer(object):
                     continue
                 L_ = wav.shape[1]
                 x_T = self._x_T((1, 2, 1 + L_ // 160, 161), None)             # :947-950 randn_like(init): the file's draw, kept for a repeat
-                out = self.enhance(wav, x_T=x_T)[0].cpu().numpy()            # verified: SamplerPipeline.check(), f16x2 window fallback
+                out = self.enhance(wav, x_T=x_T)[0]                          # verified: SamplerPipeline.check(), f16x2 window fallback
+                if self.wav_out == "pcm16":
+                    out = out.cpu().numpy()
                 if rng_fidelity:
                     shape = (1, 2, 1 + wav.shape[1] // 160, 161)
                     for _ in range(len(self._pipes[next(reversed(self._pipes))].schedule[0]) - 1):
                         torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
                 dst = os.path.join(self.args.generated_wav, path.split("/")[-1])
-                wavio.write_wav(dst, out, 16000)
+                self._write_wav(dst, out, path)
                 written.append(dst)
         print("success!")
         return written
+
+    def _write_wav(self, dst, out, src):
+        """The one writer of the three loops.  out: the enhanced waveform of the file ``src`` at 16 kHz, 1-D - a numpy array or a
+        tensor.  "pcm16": ``wavio.write_wav``.  "source": the header of ``src`` is read again (``wavio.probe``), the waveform goes
+        through ``wavdev.encode`` at the source's rate, cut to the source's frame count, and the frames are written behind a plain
+        header (``wavio.write_payload``).  A source with more channels than the encoder interleaves (8) is written mono."""
+        if self.wav_out == "pcm16":
+            wavio.write_wav(dst, out.cpu().numpy() if torch.is_tensor(out) else out, 16000)
+            return
+        try:
+            rate, ch, tag, width, n_src = wavio.probe(src)
+        except ValueError as e:                      # a header the loader's reader took and ``probe`` does not
+            logging.warning("%s: written at 16 kHz, 16-bit, mono: %s", dst, e)
+            wavio.write_wav(dst, out.cpu().numpy() if torch.is_tensor(out) else out, 16000)
+            return
+        tag, width = wavio.target_of((tag, width))
+        fmt = wavio.WAV_FLOAT if tag == 3 else wavio.WAV_INT
+        if ch > L.WAV_MAX_CH:
+            logging.warning("%s: %d channels in the source, written as one", dst, ch)
+            ch = 1
+        out = torch.as_tensor(out, dtype=torch.float32).to(self.device).flatten()
+        keep = min(n_src, wavio.out_len(out.numel(), 16000, rate))
+        (payload,), (clipped,) = wavdev.encode(out[None], [out.numel()], self.device, rate, fmt, width, ch, n_keep=[keep])
+        wavio.write_payload(dst, payload, rate, fmt, width, ch)
+        if clipped:
+            logging.warning("%s: %d of %d samples clipped at the %d-bit range", dst, clipped, keep, 8 * width)
 
     def _generate_wav_stream(self, data_path, rng_fidelity, inflight):
         ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0
@@ -561,7 +603,7 @@ class ComplexDDPMTrainer(object):
         with torch.no_grad():
             for k, (out, _) in enumerate(self.enhance_stream(files(), inflight=inflight)):
                 dst = os.path.join(self.args.generated_wav, read[k].split("/")[-1])
-                wavio.write_wav(dst, out[0].cpu().numpy(), 16000)
+                self._write_wav(dst, out[0], read[k])
                 written.append(dst)
         print("success!")
         return written
@@ -604,7 +646,7 @@ class ComplexDDPMTrainer(object):
                         outs[i] = r
                 for (path, _), out in zip(files, outs):
                     dst = os.path.join(self.args.generated_wav, path.split("/")[-1])
-                    wavio.write_wav(dst, out.cpu().numpy(), 16000)
+                    self._write_wav(dst, out, path)
                     written.append(dst)
         print("success!")
         return written

@@ -14,7 +14,14 @@ between calls.
 
 ``load(..., formats="all")`` and ``decode(..., fmt=WAV_*)`` (opt-in; the defaults are the paragraph above, bit for bit) read what
 else a RIFF/WAVE file holds - 24-bit PCM, IEEE float of 32 and 64 bits, G.711 A-law and mu-law, WAVE_FORMAT_EXTENSIBLE headers, up
-to eight channels - with ``wavio.read_frames`` and the second kernel of csrc/resample.hip; the oracle is then ``wavio.read_any``."""
+to eight channels - with ``wavio.read_frames`` and the second kernel of csrc/resample.hip; the oracle is then ``wavio.read_any``.
+
+The way back (opt-in: ``generate_wav`` of a trainer built with ``wav_out="source"``), at the end of the file:
+
+    encode(rows, lens, device, rate, fmt, width, ch, n_keep=None)   -> (list of bytes objects, list of clip counts)
+
+one launch of csrc/wavout.hip (include/pdse.h: pdse_wav_encode) converts enhanced waveforms to their sources' rate, encodes them
+as 16-, 24- or 32-bit PCM or binary32 and interleaves the channels; the oracle is ``wavio.resample`` + ``wavio.encode``."""
 import numpy as np
 
 from . import _lib as L
@@ -172,3 +179,76 @@ def _finite(row, path):
 
     if not bool(torch.isfinite(row).all()):
         raise ValueError("%s: float samples that are not finite" % path)
+
+
+# ---- the way back (opt-in: generate_wav(wav_out="source")): csrc/wavout.hip, include/pdse.h: the wav back end -------------------
+def encoder_covers(rate, sr=16000):
+    """Whether csrc/wavout.hip converts ``sr`` to ``rate``: the input window of one workgroup's frames ((RESAMPLE_BLOCK - 1) down /
+    up + 2 jmax + 2 fp32 samples) beside the 8 KB image of its bytes within 64 KB of LDS (output rates down to about 300 Hz)."""
+    up, down, half = _ratio(sr, rate)
+    return up == down or 4 * ((L.RESAMPLE_BLOCK - 1) * down // up + 2 * (half // up + 1) + 2) + L.WAVOUT_IMAGE_BYTES + 64 <= 64 * 1024
+
+
+def encode(rows, lens, device, rate, fmt, width, ch, n_keep=None, sr=16000):
+    """The frames of B waveforms at ``sr`` as their files hold them at ``rate``: (list of bytes objects, list of clip counts).
+    rows: a [B, Lmax] fp32 tensor on ``device`` with waveform b in rows[b, :lens[b]] (what ``load`` returns, what ``enhance``
+    gives back), or a list of 1-D tensors; fmt ``L.WAV_INT`` with width 2, 3 or 4 bytes or ``L.WAV_FLOAT`` with width 4; every one
+    of the ``ch`` channels (1 .. 8) carries the waveform.  n_keep[b] (default: all ``wavio.out_len(lens[b], sr, rate)`` of them)
+    cuts file b to its first frames.  Element b is ``wavio.encode(wavio.resample(row_b, sr, rate)[:n_keep[b]], fmt, width, ch)``
+    byte for byte, and its clip count - the samples the integer clamp changed - is the host's.  One upload (the lengths), one
+    launch on the current stream, one copy back that carries the frames and the per-workgroup clip counts together.  A rate pair
+    the kernel's LDS window does not hold (``encoder_covers``) takes those host functions instead; the kernel itself has no CPU
+    fallback."""
+    out, keep, counts = encode_rows(rows, lens, device, rate, fmt, width, ch, n_keep, sr)
+    fb = int(ch) * int(width)
+    return [out[b, :keep[b] * fb].tobytes() for b in range(len(keep))], counts
+
+
+def encode_rows(rows, lens, device, rate, fmt, width, ch, n_keep=None, sr=16000):
+    """``encode`` before the rows are cut: (out, n_keep, clip counts) with out a uint8 array [B, stride] on the host, row b holding
+    n_keep[b] * ch * width bytes of frames and zeros behind them (the kernel's buffer as it came back)."""
+    import torch
+
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.PdseError("wavdev.encode runs on the GPU only (no CPU fallback); wavio.encode is the host path")
+    wavio._check_target(fmt, width, ch)
+    if not torch.is_tensor(rows):
+        rows = torch.nn.utils.rnn.pad_sequence([torch.as_tensor(r, dtype=torch.float32).flatten().to(device) for r in rows], batch_first=True)
+    rows = rows.to(device, torch.float32).contiguous()
+    if rows.dim() != 2 or rows.shape[0] != len(lens) or rows.shape[0] < 1:
+        raise ValueError("rows: [B, Lmax] with one length per row")
+    B, Lmax = int(rows.shape[0]), int(rows.shape[1])
+    lens = [int(n) for n in lens]
+    if any(n < 1 or n > Lmax for n in lens):
+        raise ValueError("lens: 1 .. %d samples per row" % Lmax)
+    n_out = [wavio.out_len(n, sr, rate) for n in lens]
+    keep = n_out if n_keep is None else [int(k) for k in n_keep]
+    if len(keep) != B or any(k < 0 or k > n for k, n in zip(keep, n_out)):
+        raise ValueError("n_keep: one count per row, at most the frames the row converts to")
+    fb = int(ch) * int(width)
+    stride = max(max(keep) * fb, 1)
+    if not encoder_covers(rate, sr):
+        host = rows.cpu().numpy()
+        out, counts = np.zeros((B, stride), dtype=np.uint8), []
+        for b in range(B):
+            with np.errstate(over="ignore", invalid="ignore"):
+                y = wavio.resample(host[b, :lens[b]], sr, rate)[:keep[b]]
+            payload, clipped = wavio.encode(y, fmt, width, ch)
+            out[b, :len(payload)] = np.frombuffer(payload, dtype=np.uint8)
+            counts.append(clipped)
+        return out, keep, counts
+    taps, up, down, half = _device_taps(device, sr, rate)
+    blocks = -(-stride // (L.RESAMPLE_BLOCK * fb))
+    counts_at = -(-B * stride // 4) * 4                      # the int32 counts behind the rows, in the same buffer: one copy back
+    meta = np.array(lens + keep, dtype=np.int32)
+    with torch.cuda.device(device):
+        meta_dev = torch.from_numpy(meta).to(device)
+        buf = torch.empty(counts_at + 4 * B * blocks, dtype=torch.uint8, device=device)
+        L.wav_encode(rows.data_ptr(), meta.ctypes.data, meta.ctypes.data + 4 * B, meta_dev.data_ptr(), meta_dev.data_ptr() + 4 * B,
+                     taps.data_ptr() if taps is not None else None, buf.data_ptr(), buf.data_ptr() + counts_at,
+                     stride, B, Lmax, up, down, half, fmt, width, ch,
+                     stream=torch.cuda.current_stream(device).cuda_stream, device=device)
+        host = buf.cpu().numpy()
+    counts = host[counts_at:].view(np.int32).reshape(B, blocks).sum(axis=1)
+    return host[:B * stride].reshape(B, stride), keep, [int(c) for c in counts]

@@ -227,3 +227,157 @@ def read_any(path, sr=16000):
         with np.errstate(over="ignore", invalid="ignore"):
             x = resample(x, rate, sr)
     return x
+
+
+# ---- the way back: a waveform at 16 kHz written in its source's rate and encoding (opt-in: generate_wav(wav_out="source")) ----
+# The host oracle of csrc/wavout.hip (include/pdse.h: the wav back end; prior-diffuse_amd/wavdev.py: encode).
+_FMT_TAG = {WAV_INT: 1, WAV_FLOAT: 3}                        # what write_any writes: WAVE_FORMAT_PCM, WAVE_FORMAT_IEEE_FLOAT
+_OUT_WIDTHS = {WAV_INT: (2, 3, 4), WAV_FLOAT: (4,)}
+MAX_OUT_CH = 8                                               # PDSE_WAV_MAX_CH
+
+
+def _check_target(fmt, width, ch):
+    if fmt not in _OUT_WIDTHS or width not in _OUT_WIDTHS[fmt]:
+        raise ValueError("no encoder for fmt %r with %r bytes per sample (WAV_INT: 2, 3, 4; WAV_FLOAT: 4)" % (fmt, width))
+    if not 1 <= int(ch) <= MAX_OUT_CH:
+        raise ValueError("%r channels (1 .. %d)" % (ch, MAX_OUT_CH))
+
+
+def encode(x, fmt, width, ch):
+    """(payload, clipped): the fp32 mono samples ``x`` as interleaved little-endian frames of ``ch`` equal channels (1 .. 8), and
+    the number of samples the clamp changed.  WAV_INT, width 2 / 3 / 4: ``write_wav``'s arithmetic at that width - float64(x)
+    clamped to [-1, 1 - 2^-(8 width - 1)], times 2^(8 width - 1) (exact), ``np.round`` (half to even); NaN is written as 0 and
+    counts as clipped, an infinity clamps and counts.  WAV_FLOAT, width 4: the binary32 bits as they are, nothing clamped
+    (clipped is 0).  The 16-bit mono payload is ``write_wav``'s data chunk byte for byte."""
+    _check_target(fmt, width, ch)
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    if fmt == WAV_FLOAT:
+        return np.repeat(x.view(np.uint32).astype("<u4"), ch).tobytes(), 0
+    bits = 8 * width - 1
+    x64 = x.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        y = np.clip(x64, -1.0, 1.0 - 2.0 ** -bits)
+        clipped = int(np.count_nonzero(y != x64))            # NaN != NaN: counted
+    y[np.isnan(y)] = 0.0
+    v = np.repeat(np.round(y * 2.0 ** bits).astype("<i4"), ch)
+    if width == 2:
+        return v.astype("<i2").tobytes(), clipped
+    if width == 3:
+        return np.ascontiguousarray(v.view(np.uint8).reshape(-1, 4)[:, :3]).tobytes(), clipped
+    return v.tobytes(), clipped
+
+
+def wav_header(n_bytes, sr, fmt, width, ch):
+    """The bytes in front of a data chunk of ``n_bytes``: RIFF, WAVE and a plain ``fmt `` chunk - tag 1 with the 16 bytes the
+    ``wave`` module writes (a 16-bit mono file is that module's byte for byte), tag 3 with cbSize = 0 and a ``fact`` chunk holding
+    the frame count - then the ``data`` chunk's own header.  An odd data chunk is followed by a pad byte (``wav_pad``), counted
+    in the RIFF size."""
+    import struct
+
+    _check_target(fmt, width, ch)
+    if n_bytes % (ch * width) or n_bytes + 64 >= 2 ** 32:
+        raise ValueError("a data chunk of %d bytes (whole frames of %d bytes, below 4 GiB: RF64 is not written)" % (n_bytes, ch * width))
+    body = struct.pack("<HHIIHH", _FMT_TAG[fmt], ch, int(sr), int(sr) * ch * width, ch * width, 8 * width)
+    if fmt == WAV_FLOAT:
+        chunks = b"fmt " + struct.pack("<I", 18) + body + struct.pack("<H", 0) + b"fact" + struct.pack("<II", 4, n_bytes // (ch * width))
+    else:
+        chunks = b"fmt " + struct.pack("<I", 16) + body
+    chunks = b"WAVE" + chunks + b"data" + struct.pack("<I", n_bytes)
+    return b"RIFF" + struct.pack("<I", len(chunks) + n_bytes + (n_bytes & 1)) + chunks
+
+
+def write_payload(path, payload, sr, fmt, width, ch):
+    """A RIFF/WAVE file around frames that are already encoded (``encode``, ``wavdev.encode``)."""
+    head = wav_header(len(payload), sr, fmt, width, ch)
+    with open(path, "wb") as f:
+        f.write(head)
+        f.write(payload)
+        if len(payload) & 1:
+            f.write(b"\0")
+
+
+def write_any(path, x, sr, fmt, width, ch):
+    """``write_wav`` for the other targets: ``encode(x, fmt, width, ch)`` in a file ``read_frames`` / ``read_any`` reads back.
+    Returns the clip count.  ``write_any(path, x, sr, WAV_INT, 2, 1)`` writes ``write_wav(path, x, sr)``'s file."""
+    payload, clipped = encode(x, fmt, width, ch)
+    write_payload(path, payload, sr, fmt, width, ch)
+    return clipped
+
+
+def target_of(source):
+    """(tag, width) a file is written with, from its source's (tag, width) - wFormatTag 1, 3, 6 or 7 as ``probe`` returns it:
+    16-, 24- and 32-bit PCM as itself, binary32 and binary64 as binary32, and what is too narrow to hold an enhanced signal -
+    8-bit PCM, A-law, mu-law - as 16-bit PCM."""
+    tag, width = int(source[0]), int(source[1])
+    if tag not in _TAG_FMT or width not in _WIDTHS[_TAG_FMT[tag]]:
+        raise ValueError("no wav encoding with format tag %d and %d bytes per sample" % (tag, width))
+    if tag == 3:
+        return 3, 4
+    if tag == 1 and width > 1:
+        return 1, width
+    return 1, 2
+
+
+def probe(path):
+    """(rate, channels, tag, width, n_frames) of a file ``read_frames`` opens, from its chunk headers alone: nothing of the data
+    chunk is read.  tag is the wFormatTag behind a WAVE_FORMAT_EXTENSIBLE header (1 PCM, 3 IEEE float, 6 A-law, 7 mu-law),
+    n_frames what ``read_frames`` returns (a data size beyond the end of the file is clamped to it).  ValueError for the files
+    ``read_frames`` refuses."""
+    import os
+    import struct
+
+    with open(path, "rb") as f:
+        end = os.fstat(f.fileno()).st_size
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise ValueError("%s: not a RIFF/WAVE file (%r)" % (path, head[:4]))
+        pos, fmt_chunk, n_data = 12, None, None
+        while pos + 8 <= end:
+            f.seek(pos)
+            cid, size = struct.unpack("<4sI", f.read(8))
+            body = pos + 8
+            if cid == b"fmt " and fmt_chunk is None:
+                fmt_chunk = f.read(size)
+                if len(fmt_chunk) < size:
+                    raise ValueError("%s: the file ends inside the fmt chunk" % path)
+            elif cid == b"data":
+                if fmt_chunk is None:
+                    raise ValueError("%s: data chunk before the fmt chunk" % path)
+                n_data = min(body + size, end) - body
+                break
+            pos = body + size + (size & 1)
+    if fmt_chunk is None or n_data is None:
+        raise ValueError("%s: no %s chunk" % (path, "fmt" if fmt_chunk is None else "data"))
+    if len(fmt_chunk) < 16:
+        raise ValueError("%s: fmt chunk of %d bytes" % (path, len(fmt_chunk)))
+    tag, ch, rate, _, align, bits = struct.unpack_from("<HHIIHH", fmt_chunk)
+    if tag == 0xFFFE:
+        if len(fmt_chunk) < 40 or struct.unpack_from("<H", fmt_chunk, 16)[0] < 22:
+            raise ValueError("%s: WAVE_FORMAT_EXTENSIBLE with a fmt chunk of %d bytes" % (path, len(fmt_chunk)))
+        if fmt_chunk[26:40] != _GUID_TAIL:
+            raise ValueError("%s: unknown SubFormat GUID %s" % (path, fmt_chunk[24:40].hex()))
+        tag = struct.unpack_from("<H", fmt_chunk, 24)[0]
+    if tag not in _TAG_FMT:
+        raise ValueError("%s: unsupported format tag 0x%04X" % (path, tag))
+    if bits % 8 or bits // 8 not in _WIDTHS[_TAG_FMT[tag]]:
+        raise ValueError("%s: %d bits per sample with format tag %d" % (path, bits, tag))
+    width = bits // 8
+    if ch < 1 or rate < 1:
+        raise ValueError("%s: %d channels at %d Hz" % (path, ch, rate))
+    if align != ch * width:
+        raise ValueError("%s: block align %d with %d channels of %d bytes" % (path, align, ch, width))
+    if n_data % align:
+        raise ValueError("%s: the data chunk ends inside a frame (%d bytes, %d per frame)" % (path, n_data, align))
+    return rate, ch, tag, width, n_data // align
+
+
+def restore(x16k, rate, n_src):
+    """The samples a file of ``n_src`` frames at ``rate`` is written with, from its enhanced waveform at 16 kHz: ``resample`` back
+    to the source's rate - the same taps, float64, one cast to fp32 - cut to ``n_src``.  ``resample`` returns ceil(n up / down)
+    samples in each direction, so the way there and back never comes out shorter than the source (at most a few samples longer:
+    tests/test_wavout_host.py walks the common rates) and the cut is all it takes."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        y = resample(np.asarray(x16k, dtype=np.float32), 16000, rate)
+    if y.size < n_src:
+        raise ValueError("%d samples at %d Hz from %d at 16 kHz: fewer than the %d the source holds" % (y.size, rate, np.size(x16k), n_src))
+    return y[:n_src]

@@ -4,12 +4,16 @@ one untimed run (weights, plan, graph capture), then three timed runs; prints th
 highest run.  Only the public interface is used, so the same script times any checkout of the project:
 
     python tools/time_file_loop.py [--rates 16000 44100 48000] [--root OTHER_CHECKOUT] [--files 16] [--seconds 4] [--runs 3]
-                                   [--format s16|s24|f32|f64|ulaw] [--channels N]
+                                   [--format s16|s24|f32|f64|ulaw] [--channels N] [--wav-out pcm16|source]
 
 --format other than s16, or --channels above 1, writes the files with a RIFF writer of this script's own and times
 ``generate_wav`` of a trainer built with ``wav_formats="all"`` (s16 with more channels goes through the same trainer, so the
 three formats are compared on one loop); the default - 16-bit mono through the default trainer - needs nothing a checkout
 before ``wav_formats`` lacks.
+
+--wav-out source times the same loop of a trainer built with ``wav_out="source"``: every file is written at its source's rate,
+length, channel count and encoding, converted and encoded on the device (``wavdev.encode``), instead of 16 kHz, 16-bit, mono.
+The default passes nothing, so a checkout before ``wav_out`` is timed by the same command (profiles/wav_out_timing.txt).
 
 Lines of several invocations (say, this commit and its parent, alternating) are collected in profiles/wav_frontend_timing.txt
 and profiles/wav_formats_timing.txt.
@@ -63,6 +67,7 @@ def main():
     ap.add_argument("--label", default=None)
     ap.add_argument("--format", choices=sorted(FORMATS), default="s16")
     ap.add_argument("--channels", type=int, default=1)
+    ap.add_argument("--wav-out", choices=("pcm16", "source"), default="pcm16")
     args = ap.parse_args()
     root = os.path.abspath(args.root)
     sys.path.insert(0, root)
@@ -85,7 +90,7 @@ def main():
             ns(retrain=False, joint=True, draw=False, sigma=False, checkpoint="x", generated_wav=os.path.join(work, "out")),
             ns(model=ns(name="GCRN"), train=ns(fft_num=320, win_size=320, win_shift=160, feat_type="sqrt")),
             device="cuda:0", prior_state_dict=synth.make_state_dict("GCRN"), ddpm_state_dict=synth.make_state_dict("DiffUNet1"),
-            **({"wav_formats": "all"} if all_wav else {}))
+            **({"wav_formats": "all"} if all_wav else {}), **({"wav_out": "source"} if args.wav_out == "source" else {}))
         for rate in args.rates:
             src = os.path.join(work, "in_%d" % rate)
             os.makedirs(src)
@@ -106,11 +111,11 @@ def main():
                 torch.cuda.synchronize()
                 ms.append(1e3 * (time.perf_counter() - t0) / args.files)
             res = {"label": label, "rate": rate, "format": args.format, "channels": args.channels,
-                   "loop": "wav_formats=all" if all_wav else "default", "files": args.files, "seconds_per_file": args.seconds,
+                   "loop": "wav_formats=all" if all_wav else "default", "wav_out": args.wav_out, "files": args.files, "seconds_per_file": args.seconds,
                    "ms_per_file_median": round(statistics.median(ms), 3), "ms_per_file_min": round(min(ms), 3),
                    "ms_per_file_max": round(max(ms), 3), "runs": args.runs}
-            print("%-10s %-4s x%d %6d Hz: %8.3f ms per file (%.3f .. %.3f over %d runs of %d files of %.1f s)" % (
-                label, args.format, args.channels, rate, res["ms_per_file_median"], res["ms_per_file_min"], res["ms_per_file_max"], args.runs, args.files,
+            print("%-10s %-4s x%d %6d Hz -> %-6s: %8.3f ms per file (%.3f .. %.3f over %d runs of %d files of %.1f s)" % (
+                label, args.format, args.channels, rate, args.wav_out, res["ms_per_file_median"], res["ms_per_file_min"], res["ms_per_file_max"], args.runs, args.files,
                 args.seconds), flush=True)
             print("RESULT " + json.dumps(res), flush=True)
     finally:
