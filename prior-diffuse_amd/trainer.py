@@ -18,8 +18,9 @@ import logging
 import os
 from collections import OrderedDict, deque, namedtuple
 from copy import deepcopy
+from functools import partial
+from itertools import chain
 
-import numpy as np
 import torch
 
 from . import _lib as L
@@ -33,11 +34,34 @@ from .schedule import inference_schedule as _inference_schedule
 _Job = namedtuple("_Job", "event pipe key wav x_T out")
 
 
+class _PlanCache(OrderedDict):
+    """Recorded plans of some geometries, key -> plan, least recently used first.  At most ``capacity`` plans - and so
+    activation sets - are alive at any moment: the least recently used one is dropped BEFORE a new one is built.
+    ``hits[key]``: how often the key was met again since its plan was built (0 for a fresh plan, a rebuilt one included)."""
+
+    def __init__(self, capacity):
+        super().__init__()
+        self.capacity, self.hits = capacity, {}
+
+    def take(self, key, build):
+        """-> (plan of ``key``, met_before); ``build()`` makes the plan where the cache does not hold one."""
+        met = key in self
+        self.hits[key] = self.hits.get(key, 0) + 1 if met else 0
+        if met:
+            self.move_to_end(key)
+        else:
+            while len(self) >= self.capacity:
+                self.popitem(last=False)
+            self[key] = build()
+        return self[key], met
+
+
 class _Slot:
     """One slot of ``enhance_stream``: a HIP stream and the recorded geometries it keeps ((geometry, split) -> pipeline, LRU)."""
 
-    def __init__(self, stream):
-        self.stream, self.pipes, self.hits = stream, OrderedDict(), {}
+    def __init__(self, stream, capacity):
+        self.stream, self.pipes = stream, _PlanCache(capacity)
+        self.hits = self.pipes.hits
 
 
 def _inflight_arg(inflight):
@@ -81,13 +105,13 @@ class ComplexDDPMTrainer(object):
         GRU, GroupNorm and AHAM kernels (``SamplerPipeline(ragged=True, masked_prior=True)``), and every utterance comes out as
         if enhanced alone, as for the other priors.  Dense passes are not touched.  None: ``args.masked_prior`` when the CLI set
         it (``main.py --masked-prior``), else False: exact ragged batches of these priors raise ValueError as before.
-        wav_formats: what the three ``generate_wav`` loops open.  "pcm": 8-, 16- and 32-bit integer PCM in a plain header, as
+        wav_formats: what ``generate_wav`` opens, in all three modes.  "pcm": 8-, 16- and 32-bit integer PCM in a plain header, as
         the ``wave`` module reads it; everything else is skipped with a warning.  "all": also 24-bit PCM, IEEE float (32 and
         64 bits), G.711 A-law and mu-law and WAVE_FORMAT_EXTENSIBLE headers, decoded on the device
         (``wavdev.load(formats="all")``, the waveform of ``wavio.read_any``); a float file with a non-finite sample is skipped
         with the same warning before its x_T is drawn.  None: "all" when the CLI set ``args.all_wav`` (``main.py --all-wav``),
         else "pcm".
-        wav_out: what the three ``generate_wav`` loops write.  "pcm16": 16 kHz, 16-bit, mono, whatever the source was
+        wav_out: what ``generate_wav`` writes, in all three modes.  "pcm16": 16 kHz, 16-bit, mono, whatever the source was
         (``wavio.write_wav``, as ever).  "source": every file at its source's rate, frame count and channel count, in the source's
         encoding where that holds an enhanced signal - 16-, 24- and 32-bit PCM as themselves, binary32 and binary64 as binary32,
         8-bit PCM and G.711 as 16-bit PCM (``wavio.target_of``) - converted, clamped, encoded and interleaved on the device
@@ -112,7 +136,6 @@ class ComplexDDPMTrainer(object):
             raise ValueError("split must be 'f16x2' or 'bf16x3'")
         self.split = split
         self.audit = bool(getattr(args, "audit_range", False) if audit is None else audit)
-        self._audit_clean = set()              # geometries whose audited f16x2 pass came back clean once: their report is not read again
         if dtype is None:
             dtype = "bf16" if getattr(args, "bf16", False) else "f32"
         if dtype not in ("f32", "bf16"):
@@ -123,7 +146,6 @@ class ComplexDDPMTrainer(object):
 
             exclusive = not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
         self.exclusive = bool(exclusive)
-        self._range_fallback = set()           # geometries whose f16x2 pass left the fp16 window once: they run on the three-plane bf16 split (_checked)
         self.c = PRIOR_SCALE_C                                        # :30
         self.args = deepcopy(args)
         self.config = deepcopy(config)
@@ -149,17 +171,11 @@ class ComplexDDPMTrainer(object):
         if self.prior_name not in ops.PRIOR_OPS:
             raise NotImplementedError("prior %r: built priors are %s" % (self.prior_name, sorted(ops.PRIOR_OPS)))
         self.prior_sd, self.ddpm_sd = prior_state_dict, ddpm_state_dict
+        self._streaming = False           # enhance_stream: one stream per trainer at a time
         if getattr(self.args, "retrain", False):                      # :91-97
             self._load_checkpoint()
-        if self.prior_sd is None or self.ddpm_sd is None:
-            raise ValueError("no weights: pass state_dicts or use --retrain with a best_checkpoint.pth")
-        self.bank = nets.WeightBank()     # packed weights in HBM: uploaded once, shared by every plan of this trainer
-        self.model = ops.PRIOR_OPS[self.prior_name](self.prior_sd, self.device, bank=self.bank, exclusive=self.exclusive)       # :69
-        self.model_ddpm = (ops.NoconOp if self.deltamu else ops.DiffUNet1Op)(self.ddpm_sd, self.device, bank=self.bank, exclusive=self.exclusive)   # :70-73
-        self._pipes = OrderedDict()
-        self._hits = {}                   # uses of a recorded geometry after the first
-        self._slots = []                  # enhance_stream: one stream and a few recorded geometries per item in flight
-        self._streaming = False
+        else:
+            self._install_weights()
 
     # ---- A8 checkpoint rules (:91-97, :906-913) ---------------------------
     def _load_checkpoint(self):
@@ -171,54 +187,77 @@ class ComplexDDPMTrainer(object):
                 self.ddpm_sd = data[2]
         else:
             self.prior_sd = data
-        if hasattr(self, "bank"):              # new weights: every recorded plan and the packed copies are stale, and so is every
-            self._pipes.clear()                # verdict on the fp16 window (fallback geometries, clean audits)
-            self._hits.clear()
-            self._range_fallback.clear()
-            self._audit_clean.clear()
-            self._slots = []
-            self.bank = nets.WeightBank()
-            self.model = ops.PRIOR_OPS[self.prior_name](self.prior_sd, self.device, bank=self.bank, exclusive=self.exclusive)
-            self.model_ddpm = (ops.NoconOp if self.deltamu else ops.DiffUNet1Op)(self.ddpm_sd, self.device, bank=self.bank, exclusive=self.exclusive)
         logging.info("loaded %s", path)
+        self._install_weights()
+
+    def _install_weights(self):
+        """Pack ``prior_sd`` / ``ddpm_sd`` for the device, once: the constructor's weights and every checkpoint loaded later."""
+        if self.prior_sd is None or self.ddpm_sd is None:
+            raise ValueError("no weights: pass state_dicts or use --retrain with a best_checkpoint.pth")
+        self._forget_plans()
+        self.bank = nets.WeightBank()     # packed weights in HBM: uploaded once, shared by every plan of this trainer
+        self.model = ops.PRIOR_OPS[self.prior_name](self.prior_sd, self.device, bank=self.bank, exclusive=self.exclusive)       # :69
+        self.model_ddpm = (ops.NoconOp if self.deltamu else ops.DiffUNet1Op)(self.ddpm_sd, self.device, bank=self.bank, exclusive=self.exclusive)   # :70-73
+
+    def _forget_plans(self):
+        """New weights: every recorded plan is stale, and so is every verdict on the fp16 window."""
+        self._pipes = _PlanCache(self.MAX_PLANS)   # the trainer's own plans; ``_hits``: uses of a recorded geometry after the first
+        self._slots = []                  # enhance_stream: one stream and a few recorded geometries per item in flight
+        self._range_fallback = set()      # geometries whose f16x2 pass left the fp16 window once: they run on the three-plane bf16 split (_checked)
+        self._audit_clean = set()         # geometries whose audited f16x2 pass came back clean once: their report is not read again
+
+    _hits = property(lambda self: self._pipes.hits)
 
     # ---- A1 ---------------------------------------------------------------
     def inference_schedule(self, fast_sampling=False):
         return _inference_schedule(self.params, fast_sampling)
 
     # ---- batched entry points ----------------------------------------------
+    def _key(self, B, T=None, L_=None, ragged=False):
+        """The key of a geometry in the plan caches and in ``_range_fallback`` / ``_audit_clean``."""
+        return (B, T, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling)) + ((True,) if ragged else ())
+
+    def _split_of(self, key, split):
+        """The operand split a plan of the geometry ``key`` is built with, where ``split`` is what it was asked for."""
+        return "bf16x3" if key in self._range_fallback else split
+
+    def _build(self, key, split, **kw):
+        """A new plan of the geometry ``key`` against the weights already packed in ``self.bank``: re-recording the descriptors
+        takes milliseconds.  split: ``_split_of(key, ...)``; kw: what the trainer's own plans and the stream's slots set apart."""
+        return SamplerPipeline(
+            self.device, self.prior_name, self.prior_sd, self.ddpm_sd, key[0], T=key[1], L_=key[2],
+            fast_sampling=self.params.fast_sampling, use_sigma=key[3], params=self.params, deltamu=self.deltamu,
+            cond=self.cond, bank=self.bank, xT_plus_init=self.xT_plus_init, dtype=self.dtype, split=split, **kw)
+
+    def _plan(self, **geom):
+        """-> (plan, key, met_before) of one geometry (``_key``'s arguments).  ``generate_wav`` meets a new utterance length
+        with almost every file; only ``MAX_PLANS`` geometries keep their activation buffers, the least recently used one is
+        dropped.  met_before: the geometry came back (a directory of equally long files, a serving loop) - the callers that
+        replay a plan from its hipGraph, one host call instead of ~770 launches, do so then; a length seen once is not worth
+        the capture."""
+        key = self._key(**geom)
+        ragged = len(key) == 6
+        build = partial(self._build, key, self._split_of(key, self.split), exclusive=self.exclusive, audit=self.audit,
+                        ragged=ragged, masked_prior=ragged and self.masked_prior)
+        pipe, met = self._pipes.take(key, build)
+        return pipe, key, met
+
     def _pipe(self, B, T=None, L_=None, ragged=False):
-        """The recorded plan of one geometry.  ``generate_wav`` meets a new utterance length with almost every file:
-        a new plan re-records its descriptors (milliseconds) against the weights already packed in ``self.bank``;
-        only ``MAX_PLANS`` geometries keep their activation buffers, the least recently used one is dropped."""
-        key = (B, T, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling)) + ((True,) if ragged else ())
-        pipe = self._pipes.get(key)
-        self._hits[key] = self._hits.get(key, 0) + 1 if pipe is not None else 0
-        if pipe is None:
-            while len(self._pipes) >= self.MAX_PLANS:
-                self._pipes.popitem(last=False)
-            pipe = self._pipes[key] = SamplerPipeline(
-                self.device, self.prior_name, self.prior_sd, self.ddpm_sd, B, T=T, L_=L_,
-                fast_sampling=self.params.fast_sampling, use_sigma=key[3], params=self.params, deltamu=self.deltamu,
-                cond=self.cond, bank=self.bank, xT_plus_init=self.xT_plus_init, exclusive=self.exclusive, dtype=self.dtype,
-                split="bf16x3" if key in self._range_fallback else self.split, audit=self.audit, ragged=ragged,
-                masked_prior=ragged and self.masked_prior)
-        else:
-            self._pipes.move_to_end(key)
-        return pipe
+        """The recorded plan of one geometry."""
+        return self._plan(B=B, T=T, L_=L_, ragged=ragged)[0]
 
     def _checked(self, run, **geom):
-        """``run(pipe) -> result`` on the plan of a geometry, verified (``SamplerPipeline.check``: synchronises).  A pass on f16x2
-        operands whose activations left the fp16 window shows as non-finite output (include/pdse.h: PDSE_F16_ACT_EXP): the geometry
-        is then rebuilt on the exact three-plane bf16 split - no window - and the pass repeated; later calls stay on it.
+        """``run(pipe, graph) -> result`` on the plan of a geometry, verified (``SamplerPipeline.check``: synchronises); graph:
+        the geometry was met before (``_plan``), for the callers that replay.  A pass on f16x2 operands whose activations left
+        the fp16 window shows as non-finite output (include/pdse.h: PDSE_F16_ACT_EXP): the geometry is then rebuilt on the exact
+        three-plane bf16 split - no window - and the pass repeated, launch by launch; later calls stay on it.
         With ``audit`` the range report of the pass is read as well and a tensor wholly below the window is handled the same
         way.  The audit is read on a geometry's passes until one comes back clean; after that the geometry keeps its audited
         plan (re-recording it would cost more than the launches do) and stops reading the report - a geometry is judged on the
         first inputs it sees, at the price of one small device-to-host copy per pass until then and of the audit launches for
         as long as the plan lives."""
-        pipe = self._pipe(**geom)
-        key = next(reversed(self._pipes))
-        res = run(pipe)
+        pipe, key, met = self._plan(**geom)
+        res = run(pipe, met)
         try:
             read = self.audit and pipe.audited and key not in self._audit_clean
             pipe.check(audit=read)
@@ -228,8 +267,8 @@ class ComplexDDPMTrainer(object):
             logging.warning("%s - repeating this geometry with split='bf16x3'", e)
             self._range_fallback.add(key)
             del self._pipes[key]
-            pipe = self._pipe(**geom)
-            res = run(pipe)
+            pipe, _, met = self._plan(**geom)
+            res = run(pipe, met)
             pipe.check()
         return res
 
@@ -280,15 +319,12 @@ class ComplexDDPMTrainer(object):
         return self._enhance_stream(items, inflight)
 
     def _stream_slots(self, inflight):
-        slots = getattr(self, "_slots", None)
-        if slots is None:
-            slots = self._slots = []
-        while len(slots) < inflight:
-            slots.append(_Slot(torch.cuda.Stream(self.device)))
-        return slots[:inflight]
+        while len(self._slots) < inflight:
+            self._slots.append(_Slot(torch.cuda.Stream(self.device), self.STREAM_PLANS))
+        return self._slots[:inflight]
 
     def _enhance_stream(self, items, inflight):
-        if getattr(self, "_streaming", False):
+        if self._streaming:
             raise RuntimeError("enhance_stream: this trainer already has a stream open (its slots are in use)")
         self._streaming = True
         pending = deque()
@@ -328,19 +364,9 @@ class ComplexDDPMTrainer(object):
         B, L_ = wav.shape
         cur = torch.cuda.current_stream(self.device)
         x_T = self._x_T((B, 2, 1 + L_ // 160, 161), x_T)          # :947-950: the caller's stream, item order
-        key = (B, None, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling))      # _pipe's key of the geometry
-        split = "bf16x3" if key in self._range_fallback else (self.split or SamplerPipeline.default_split)
-        pipe = slot.pipes.get((key, split))
-        slot.hits[(key, split)] = slot.hits.get((key, split), 0) + 1 if pipe is not None else 0
-        if pipe is None:
-            while len(slot.pipes) >= self.STREAM_PLANS:
-                slot.pipes.popitem(last=False)
-            pipe = slot.pipes[(key, split)] = SamplerPipeline(
-                self.device, self.prior_name, self.prior_sd, self.ddpm_sd, B, L_=L_, fast_sampling=self.params.fast_sampling,
-                use_sigma=key[3], params=self.params, deltamu=self.deltamu, cond=self.cond, bank=self.bank,
-                xT_plus_init=self.xT_plus_init, exclusive=False, dtype=self.dtype, split=split, verdict=True)
-        else:
-            slot.pipes.move_to_end((key, split))
+        key = self._key(B, L_=L_)
+        split = self._split_of(key, self.split or SamplerPipeline.default_split)      # resolved: the split is part of a slot's cache key
+        pipe, met = slot.pipes.take((key, split), partial(self._build, key, split, exclusive=False, verdict=True))
         _expect(x_T, pipe.xT_in, "x_T")
         ready = torch.cuda.Event()
         ready.record(cur)                                          # behind the draw, the upload of the inputs and the recording of a new plan
@@ -352,7 +378,7 @@ class ComplexDDPMTrainer(object):
             pipe.stft.wav.copy_(wav, non_blocking=True)
             pipe.xT_in.copy_(x_T, non_blocking=True)
             pipe.stft.lens.fill_(L_)
-            if slot.hits[(key, split)] >= 1:                       # met again: one host call instead of ~770 launches
+            if met:                                                # met again: one host call instead of ~770 launches
                 if not pipe.plan.has_graph:
                     pipe.plan.build_graph(st.cuda_stream)
                 pipe.plan.launch_graph(st.cuda_stream)
@@ -382,8 +408,7 @@ class ComplexDDPMTrainer(object):
         self._pipes.pop(job.key, None)                             # f16x2 plans of the geometry: not used again
         for slot in self._slots:
             slot.pipes.pop((job.key, job.pipe.split), None)
-        run = lambda pipe: pipe.enhance(job.wav, job.x_T, graph=self._hits.get(next(reversed(self._pipes)), 0) >= 1)   # noqa: E731
-        return self._checked(run, B=job.wav.shape[0], L_=job.wav.shape[1])
+        return self._checked(lambda pipe, graph: pipe.enhance(job.wav, job.x_T, graph=graph), B=job.wav.shape[0], L_=job.wav.shape[1])
 
     def _x_T(self, shape, x_T):
         if x_T is None:                                            # :947-950 randn_like(init)
@@ -397,7 +422,7 @@ class ComplexDDPMTrainer(object):
         x_T = self._x_T(feat.shape, x_T)
         if not verify:
             return self._pipe(B, T=T).sample(feat, x_T)[0]
-        return self._checked(lambda pipe: pipe.sample(feat, x_T)[0], B=B, T=T)
+        return self._checked(lambda pipe, graph: pipe.sample(feat, x_T)[0], B=B, T=T)     # never replayed
 
     def enhance(self, wav, x_T=None, verify=True):
         """wav [B,L] (any scale; RMS-normalised internally like :922-923) -> enhanced [B,L].
@@ -408,11 +433,10 @@ class ComplexDDPMTrainer(object):
         B, L_ = wav.shape
         T = 1 + L_ // 160
         x_T = self._x_T((B, 2, T, 161), x_T)
-        # a geometry that comes back (a directory of equally long files, a serving loop) is replayed from its hipGraph: one
-        # host call instead of ~770 launches; a length seen once is not worth the capture
-        run = lambda pipe: pipe.enhance(wav, x_T, graph=self._hits.get(next(reversed(self._pipes)), 0) >= 1)[0]   # noqa: E731
+        run = lambda pipe, graph: pipe.enhance(wav, x_T, graph=graph)[0]   # noqa: E731  (a geometry that comes back is replayed: ``_plan``)
         if not verify:
-            return run(self._pipe(B, L_=L_))
+            pipe, _, met = self._plan(B=B, L_=L_)
+            return run(pipe, met)
         return self._checked(run, B=B, L_=L_)
 
     def enhance_batch(self, wavs, x_T=None, trim_to_frames=False, exact=False):
@@ -438,7 +462,7 @@ class ComplexDDPMTrainer(object):
         B, L_ = batch.shape
         T = 1 + L_ // 160
         x_T = self._x_T((B, 2, T, 161), x_T)
-        out = self._checked(lambda pipe: pipe.enhance(batch, x_T, lens=lens)[0], B=B, L_=L_)
+        out = self._checked(lambda pipe, graph: pipe.enhance(batch, x_T, lens=lens)[0], B=B, L_=L_)    # never replayed
         cut = [(n // 160) * 160 if trim_to_frames else n for n in lens]
         return [out[i, :cut[i]].clone() for i in range(B)]
 
@@ -465,9 +489,7 @@ class ComplexDDPMTrainer(object):
             x_T = xp
         else:
             x_T = x_T.to(self.device)
-        run = lambda pipe: pipe.enhance(batch, x_T, lens=lens, exact=True,                                # noqa: E731
-                                        graph=self._hits.get(next(reversed(self._pipes)), 0) >= 1)[0]
-        out = self._checked(run, B=B, L_=L_, ragged=True)
+        out = self._checked(lambda pipe, graph: pipe.enhance(batch, x_T, lens=lens, exact=True, graph=graph)[0], B=B, L_=L_, ragged=True)
         return [out[b, :lens[b]].clone() for b in range(B)]
 
     def evaluate_batch(self, noisy_wavs, clean_wavs, x_T=None, stoi=False):
@@ -502,24 +524,28 @@ class ComplexDDPMTrainer(object):
         """Per-file B=1 enhancement of ``data_path/*.wav`` into ``args.generated_wav``
         (:903-1018).  Returns the list of written paths instead of calling exit().
 
-        batch (default 1: the loop below, one file per pass): N > 1 enhances N files per pass as exact ragged batches
+        One loop (``_file_loop``) serves the three modes: the sorted paths are read, every readable file's x_T is drawn in path
+        order at its own shape and followed at once by its ``rng_fidelity`` discards, the files are enhanced, and the results
+        are written under the sources' names, in path order.  The modes differ only in how the files are enhanced, so file k's
+        noise, the names and the state the generator is left in are the same whatever ``batch`` and ``inflight`` are.
+
+        batch (default 1: one file per pass, ``enhance``, verified): N > 1 enhances N files per pass as exact ragged batches
         (``enhance_batch(exact=True)``; ``raggedplan``): the sorted paths are taken in windows of 8 N, a window is decoded at
-        once, every file's x_T is drawn in path order at its own shape - followed by its ``rng_fidelity`` discards, exactly as
-        here - so file k's noise is the same whatever ``batch`` is; the window is then sorted by length and enhanced N at a
-        time, padded to a multiple of 2560 samples.  The same files are written under the same names, in path order.
+        once and drawn as above; the window is then sorted by length and enhanced N at a time, padded to a multiple of 2560
+        samples.
 
         rng_fidelity: the reference draws ``randn_like(audio)`` after every reverse step n > 0 (:986-987) and multiplies
         it by ``newsigma == 0``; the draws change nothing in a file's output but advance the generator, so file k's
-        x_T depends on them.  With the flag set the same number of same-shaped draws is made (and discarded) after each
-        file, which keeps a seeded ``--generate`` run on the reference's generator stream file for file.
+        x_T depends on them.  With the flag set the same number of same-shaped draws is made (and discarded) for each
+        file - behind its x_T and, as no pass draws from the generator, ahead of its pass instead of after it - which keeps a
+        seeded ``--generate`` run on the reference's generator stream file for file.
         Files that cannot be read (unsupported encoding) are logged and skipped instead of aborting the run.
         A file's PCM frames are decoded, mixed to mono and converted to 16 kHz on the device (``wavdev.load``); the waveform
         is ``wavio.read_wav``'s bit for bit, so the written files do not depend on which of the two produced it.
 
-        inflight (default 1: the loop below, untouched): N = 2 .. 4 with ``batch`` 1 sends the same loop through
-        ``enhance_stream(inflight=N)``: files are read and decoded as here, every file's x_T is drawn in path order and followed
-        at once by its ``rng_fidelity`` discards - the generator ends where this loop leaves it - unreadable files are skipped
-        with the same warning, and the same 16-bit files are written under the same names; every file is verified by its plan's
+        inflight (default 1: one file at a time): N = 2 .. 4 with ``batch`` 1 sends the files through
+        ``enhance_stream(inflight=N)``: they are read, decoded, drawn and skipped as in the default mode, file by file as the
+        stream asks for them, and the same files are written under the same names; every file is verified by its plan's
         own verdict instead of a synchronisation per file.  The bits are those of an ``exclusive=False`` trainer (see
         ``enhance_stream``).  With ``batch`` > 1: ValueError (streams of ragged windows are not built)."""
         inflight = _inflight_arg(inflight)
@@ -530,45 +556,95 @@ class ComplexDDPMTrainer(object):
         os.makedirs(self.args.generated_wav, exist_ok=True)
         if int(batch) > 1:
             return self._generate_wav_batched(data_path, rng_fidelity, int(batch))
-        if inflight > 1:
-            return self._generate_wav_stream(data_path, rng_fidelity, inflight)
+        one_by_one = lambda n: [(k, k + 1) for k in range(n)]   # noqa: E731  (a file is read when its turn comes)
+        return self._file_loop(data_path, rng_fidelity, one_by_one, partial(self._enhance_files, inflight=inflight))
+
+    def _generate_wav_batched(self, data_path, rng_fidelity, batch):
+        ragged_args(self.prior_name, 161, masked=self.masked_prior)
+        return self._file_loop(data_path, rng_fidelity, partial(raggedplan.windows, batch=batch), partial(self._enhance_windows, batch=batch))
+
+    def _file_loop(self, data_path, rng_fidelity, windows, enhance):
+        """The file loop of ``generate_wav``.  windows(n) -> [(lo, hi)]: the slices of the sorted paths that are read at once.
+        enhance: a generator function; it is handed an iterator of windows, each an iterator of the window's readable files as
+        ``(path, wav [len], x_T)``, and yields ``(path, enhanced [len])`` in path order.  Nothing is read or drawn before
+        ``enhance`` asks for it, and x_T and discards are drawn in the order it asks: path order."""
+        paths = sorted(glob.glob(data_path + "/*.wav"))
+        ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0   # a plan's steps less one
+
+        def drawn(window):
+            for path, wav in self._load_window(window):
+                shape = (1, 2, 1 + wav.numel() // 160, 161)
+                x_T = self._x_T(shape, None)                                  # :947-950 randn_like(init): the file's draw, kept for a repeat
+                for _ in range(ndiscard):
+                    torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
+                yield path, wav, x_T
+
         written = []
         with torch.no_grad():
-            for path in sorted(glob.glob(data_path + "/*.wav")):
-                try:
-                    wav = wavdev.load([path], self.device, 16000, formats=self.wav_formats)[0]            # [1, L] on the device, read_wav's bits
-                except (ValueError, EOFError, wavio.wave.Error) as e:
-                    logging.warning("skipping %s: %s", path, e)
-                    continue
-                L_ = wav.shape[1]
-                x_T = self._x_T((1, 2, 1 + L_ // 160, 161), None)             # :947-950 randn_like(init): the file's draw, kept for a repeat
-                out = self.enhance(wav, x_T=x_T)[0]                          # verified: SamplerPipeline.check(), f16x2 window fallback
-                if self.wav_out == "pcm16":
-                    out = out.cpu().numpy()
-                if rng_fidelity:
-                    shape = (1, 2, 1 + wav.shape[1] // 160, 161)
-                    for _ in range(len(self._pipes[next(reversed(self._pipes))].schedule[0]) - 1):
-                        torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
+            for path, out in enhance(drawn(paths[lo:hi]) for lo, hi in windows(len(paths))):
                 dst = os.path.join(self.args.generated_wav, path.split("/")[-1])
                 self._write_wav(dst, out, path)
                 written.append(dst)
         print("success!")
         return written
 
+    def _enhance_files(self, windows, inflight):
+        """``_file_loop``'s files one per pass: through ``enhance`` (verified: ``SamplerPipeline.check()``, f16x2 window fallback)
+        or, ``inflight`` > 1, through ``enhance_stream``, which asks for a file as a slot comes free."""
+        files = chain.from_iterable(windows)
+        if inflight == 1:
+            for path, wav, x_T in files:
+                yield path, self.enhance(wav[None], x_T=x_T)[0]
+            return
+        paths = deque()                              # of the files handed to the stream and not yet handed back
+
+        def items():
+            for path, wav, x_T in files:
+                paths.append(path)
+                yield wav[None], x_T
+
+        for out, _ in self.enhance_stream(items(), inflight=inflight):
+            yield paths.popleft(), out[0]
+
+    def _enhance_windows(self, windows, batch):
+        """``_file_loop``'s files ``batch`` per pass: a window sorted by length, in exact ragged batches (``raggedplan.buckets``)."""
+        for window in windows:
+            files = list(window)                     # path order: the generator sees what the B = 1 loop shows it
+            outs = [None] * len(files)
+            for idx, L_pad in raggedplan.buckets([wav.numel() for _, wav, _ in files], batch):
+                res = self._enhance_ragged([files[i][1] for i in idx], [files[i][2] for i in idx], L_pad)
+                for i, r in zip(idx, res):
+                    outs[i] = r
+            yield from zip((path for path, _, _ in files), outs)
+
+    def _load_window(self, paths):
+        """[(path, wav [len] on the device)] of the readable files of ``paths``, in order, decoded in one call ([B, Lmax] on the
+        device, ``read_wav``'s bits); where that fails at least one file cannot be read: they are then read one by one, and the
+        unreadable ones are logged and skipped."""
+        try:
+            wav, lens = wavdev.load(paths, self.device, 16000, formats=self.wav_formats)
+            return [(p, wav[i, :lens[i]]) for i, p in enumerate(paths)]
+        except (ValueError, EOFError, wavio.wave.Error) as e:
+            if len(paths) == 1:
+                logging.warning("skipping %s: %s", paths[0], e)
+                return []
+        return [f for p in paths for f in self._load_window([p])]
+
     def _write_wav(self, dst, out, src):
-        """The one writer of the three loops.  out: the enhanced waveform of the file ``src`` at 16 kHz, 1-D - a numpy array or a
+        """The writer of the file loop.  out: the enhanced waveform of the file ``src`` at 16 kHz, 1-D - a numpy array or a
         tensor.  "pcm16": ``wavio.write_wav``.  "source": the header of ``src`` is read again (``wavio.probe``), the waveform goes
         through ``wavdev.encode`` at the source's rate, cut to the source's frame count, and the frames are written behind a plain
         header (``wavio.write_payload``).  A source with more channels than the encoder interleaves (8) is written mono."""
-        if self.wav_out == "pcm16":
+        probe = None
+        if self.wav_out == "source":
+            try:
+                probe = wavio.probe(src)
+            except ValueError as e:                  # a header the loader's reader took and ``probe`` does not
+                logging.warning("%s: written at 16 kHz, 16-bit, mono: %s", dst, e)
+        if probe is None:
             wavio.write_wav(dst, out.cpu().numpy() if torch.is_tensor(out) else out, 16000)
             return
-        try:
-            rate, ch, tag, width, n_src = wavio.probe(src)
-        except ValueError as e:                      # a header the loader's reader took and ``probe`` does not
-            logging.warning("%s: written at 16 kHz, 16-bit, mono: %s", dst, e)
-            wavio.write_wav(dst, out.cpu().numpy() if torch.is_tensor(out) else out, 16000)
-            return
+        rate, ch, tag, width, n_src = probe
         tag, width = wavio.target_of((tag, width))
         fmt = wavio.WAV_FLOAT if tag == 3 else wavio.WAV_INT
         if ch > L.WAV_MAX_CH:
@@ -580,76 +656,6 @@ class ComplexDDPMTrainer(object):
         wavio.write_payload(dst, payload, rate, fmt, width, ch)
         if clipped:
             logging.warning("%s: %d of %d samples clipped at the %d-bit range", dst, clipped, keep, 8 * width)
-
-    def _generate_wav_stream(self, data_path, rng_fidelity, inflight):
-        ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0
-        read = []                                    # paths of the items handed to the stream, in order
-
-        def files():
-            for path in sorted(glob.glob(data_path + "/*.wav")):
-                try:
-                    wav = wavdev.load([path], self.device, 16000, formats=self.wav_formats)[0]            # [1, L] on the device, read_wav's bits
-                except (ValueError, EOFError, wavio.wave.Error) as e:
-                    logging.warning("skipping %s: %s", path, e)
-                    continue
-                shape = (1, 2, 1 + wav.shape[1] // 160, 161)
-                x_T = self._x_T(shape, None)                                  # :947-950 randn_like(init), path order
-                for _ in range(ndiscard):
-                    torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
-                read.append(path)
-                yield wav, x_T
-
-        written = []
-        with torch.no_grad():
-            for k, (out, _) in enumerate(self.enhance_stream(files(), inflight=inflight)):
-                dst = os.path.join(self.args.generated_wav, read[k].split("/")[-1])
-                self._write_wav(dst, out[0], read[k])
-                written.append(dst)
-        print("success!")
-        return written
-
-    def _load_window(self, paths):
-        """[(path, wav [len] on the device)] of the readable files of ``paths``, in order; the others are logged and skipped."""
-        errors = (ValueError, EOFError, wavio.wave.Error)
-        try:
-            wav, lens = wavdev.load(paths, self.device, 16000, formats=self.wav_formats)
-            return [(p, wav[i, :lens[i]]) for i, p in enumerate(paths)]
-        except errors:
-            pass                                     # at least one file cannot be read: find out which, one by one
-        out = []
-        for p in paths:
-            try:
-                wav, lens = wavdev.load([p], self.device, 16000, formats=self.wav_formats)
-                out.append((p, wav[0, :lens[0]]))
-            except errors as e:
-                logging.warning("skipping %s: %s", p, e)
-        return out
-
-    def _generate_wav_batched(self, data_path, rng_fidelity, batch):
-        ragged_args(self.prior_name, 161, masked=self.masked_prior)
-        paths = sorted(glob.glob(data_path + "/*.wav"))
-        ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0
-        written = []
-        with torch.no_grad():
-            for lo, hi in raggedplan.windows(len(paths), batch):
-                files = self._load_window(paths[lo:hi])
-                x_Ts = []
-                for _, wav in files:                 # path order: the generator sees what the B = 1 loop shows it
-                    shape = (1, 2, 1 + wav.numel() // 160, 161)
-                    x_Ts.append(self._x_T(shape, None))
-                    for _ in range(ndiscard):
-                        torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
-                outs = [None] * len(files)
-                for idx, L_pad in raggedplan.buckets([w.numel() for _, w in files], batch):
-                    res = self._enhance_ragged([files[i][1] for i in idx], [x_Ts[i] for i in idx], L_pad)
-                    for i, r in zip(idx, res):
-                        outs[i] = r
-                for (path, _), out in zip(files, outs):
-                    dst = os.path.join(self.args.generated_wav, path.split("/")[-1])
-                    self._write_wav(dst, out, path)
-                    written.append(dst)
-        print("success!")
-        return written
 
     def train_ddpm(self):
         raise NotImplementedError("training is outside the sampling path this package implements (SURVEY.md §8)")

@@ -38,9 +38,11 @@ def test_buckets_every_file_once_sorted_padded_and_deterministic():
     assert rp.padding_waste([2560] * 4, 4) == 1.0 and rp.padding_waste([2560, 5120], 2) == (2 * 33) / (17 + 33)
 
 
-def test_draw_order_is_path_order_whatever_the_batch(monkeypatch):
+def test_draw_order_is_path_order_whatever_the_batch(monkeypatch, tmp_path):
     """The batched loop on a stubbed trainer: the generator is asked for the same shapes in the same order as the one-file loop
-    asks for them (a draw per readable file in path order, each followed by its discards), and files are written in path order."""
+    asks for them (a draw per readable file in path order, each followed by its discards), and files are written in path order.
+    Then ``generate_wav`` itself in its three modes - one file per pass, files in flight, ragged batches: the same draws, the
+    same written paths and lengths in every mode, with and without the ``rng_fidelity`` discards."""
     import numpy as np
     import torch
 
@@ -65,6 +67,13 @@ def test_draw_order_is_path_order_whatever_the_batch(monkeypatch):
             batches.append(([w.numel() for w in wavs], L_))
             return [w.clone() for w in wavs]
 
+        def enhance(self, wav, x_T=None, verify=True):
+            return wav
+
+        def enhance_stream(self, items, inflight=3):
+            for wav, _ in items:
+                yield wav, None
+
     monkeypatch.setattr(tr_mod.glob, "glob", lambda pat: ["d/" + k for k in reversed(sorted(lens))])
     monkeypatch.setattr(tr_mod.wavio, "write_wav", lambda dst, out, sr: written.append((dst, len(out))))
     monkeypatch.setattr(torch, "randn", lambda *shape, **kw: calls.append(("discard", tuple(shape))) or torch.zeros(1))
@@ -84,6 +93,44 @@ def test_draw_order_is_path_order_whatever_the_batch(monkeypatch):
         assert sorted(n for b, _ in batches for n in b) == sorted(v for v in lens.values() if v)
         assert all(L_ % 2560 == 0 and L_ >= max(b) and len(b) <= batch for b, L_ in batches)
     assert np.isfinite(nd) and nd >= 1
+    tr.args.generated_wav = str(tmp_path)
+    readable = [n for n in sorted(lens) if lens[n] is not None]
+    for r in (True, False):
+        want, seen = [], []
+        for name in readable:
+            shape = (1, 2, 1 + lens[name] // 160, 161)
+            want += [("x_T", shape)] + [("discard", shape)] * (nd if r else 0)
+        for b, i in ((1, 1), (1, 3), (2, 1), (4, 1)):
+            del calls[:], written[:]
+            out = tr.generate_wav(load_pre_train=False, data_path="d", rng_fidelity=r, batch=b, inflight=i)
+            assert out == [w[0] for w in written]
+            seen.append((list(calls), [w[0] for w in written], [w[1] for w in written]))
+        assert all(s == seen[0] for s in seen)
+        assert seen[0] == (want, [str(tmp_path / n) for n in readable], [lens[n] for n in readable])
+        assert r or not any(c[0] == "discard" for c in seen[0][0])
+
+
+def test_plan_cache_drops_the_least_recently_used_before_it_builds():
+    """``_PlanCache`` alone, integers as plans: capacity 2 and takes of a, b, a, c, b."""
+    cache = pkg("trainer")._PlanCache(2)
+    built, alive = [], []
+
+    def build(key):
+        def make():
+            alive.append(len(cache))                   # what is alive while the new plan is made
+            built.append(key)
+            return len(built)
+        return make
+
+    met = [cache.take(k, build(k))[1] for k in "abac"]
+    assert met == [False, False, True, False] and built == ["a", "b", "c"]          # no build on the hit
+    assert list(cache) == ["a", "c"] and cache["a"] == 1 and cache["c"] == 3      # b went, not a
+    assert cache.hits == {"a": 1, "b": 0, "c": 0}
+    plan, again = cache.take("b", build("b"))
+    assert (plan, again) == (4, False) and built == ["a", "b", "c", "b"] and cache.hits["b"] == 0      # rebuilt: met_before False
+    assert list(cache) == ["c", "b"]                                                # a went
+    assert cache.take("b", build("b")) == (4, True) and cache.hits["b"] == 1 and len(built) == 4
+    assert max(alive) < cache.capacity and len(cache) <= cache.capacity             # the eviction came before every build
 
 
 def test_descriptors_match_the_library_after_the_new_fields():
