@@ -931,12 +931,20 @@ typedef struct pdse_metrics_desc {
  *   PDSE_WAV_ALAW   width 1: a = byte ^ 0x55, e = (a >> 4) & 7, m = a & 15, mag = (m << 4) + 8 when e == 0, else
  *                   ((m << 4) + 0x108) << (e - 1); positive when a & 0x80; / 32768
  *   mix             the fp32 sum of the channels in channel order, then one division by (float)ch (ch == 2: (a + b) / 2, as above)
- * Another width, a ch outside 1 .. 8 or an unknown fmt is refused before the launch. */
+ * Another width, a ch outside 1 .. 8 or an unknown fmt is refused before the launch.
+ *
+ * fmt | PDSE_WAV_SPLIT (a flag bit on one of PDSE_WAV_INT .. _ULAW; additive within ABI 9) keeps the channels apart: out then has
+ * B ch rows of Lmax samples, row b ch + c is channel c of utterance b - decoded alone, no mix arithmetic (binary32 keeps its bits
+ * in every channel), then the convert step above - and has utterance b's own length n_out[b] with zeros behind it.  The row is
+ * what the dense operator gives for a mono utterance holding that channel's samples (wavio.read_channels); with ch == 1 it is the
+ * dense row.  Every other field reads as above (offs, n_in and n_in_host stay per utterance); the grid's second index is the row,
+ * so B ch <= 65535, checked before the launch like everything else.  A row does not depend on B, on ch or on its place. */
 #define PDSE_RESAMPLE_BLOCK 256
 #define PDSE_WAV_INT 1
 #define PDSE_WAV_FLOAT 2
 #define PDSE_WAV_ALAW 3
 #define PDSE_WAV_ULAW 4
+#define PDSE_WAV_SPLIT 256
 #define PDSE_WAV_MAX_CH 8
 typedef struct pdse_resample_desc {
   const uint8_t* pcm;          /* device [pcm_bytes] */
@@ -946,7 +954,7 @@ typedef struct pdse_resample_desc {
   const double* taps;          /* device [2 half + 1], or NULL when up == down */
   float* out;                  /* device [B][Lmax] */
   int64_t pcm_bytes;
-  int32_t B, Lmax, up, down, half, width, ch, fmt;   /* fmt: 0 (integer PCM, width 1 / 2 / 4, ch 1 / 2) or PDSE_WAV_* */
+  int32_t B, Lmax, up, down, half, width, ch, fmt;   /* fmt: 0 (integer PCM, width 1 / 2 / 4, ch 1 / 2) or PDSE_WAV_* [| PDSE_WAV_SPLIT: out [B ch][Lmax]] */
 } pdse_resample_desc;
 
 /* Range audit of the f16x2 window (csrc/range.hip, additive within ABI 9): per-tensor histograms of the fp16 binade of
@@ -1105,6 +1113,29 @@ int pdse_wav_encode(const float* x,              /* device [B][Lmax] */
                     int32_t* clipped,            /* device [B][blocks] */
                     int64_t stride, int32_t B, int32_t Lmax, int32_t up, int32_t down, int32_t half, int32_t fmt, int32_t width,
                     int32_t ch, pdse_stream_t s);
+
+/* The channel encoder of the wav back end (csrc/wavout.hip, additive within ABI 9): the call above with ch different rows per
+ * file.  x[B ch][Lmax]: row b ch + c is channel c of file b, and all ch rows of a file hold n_in[b] valid samples; n_in, n_keep
+ * and their host copies stay per file ([B]).  Every row goes through the convert and encode steps above on its own - the float64
+ * sum of a channel in the order stated there - and frame n of out[b] holds sample n of channel 0, 1, .. ch - 1 (the host oracle:
+ * wavio.resample per row, then wavio.encode_channels); ch equal rows give the call above's bytes.  Row b of out[B][stride] holds
+ * n_keep[b] ch width bytes followed by zeros; every byte is written, a row may start at any byte, and no two workgroups write the
+ * same aligned word.  A workgroup encodes PDSE_RESAMPLE_BLOCK frames of a file from ch input windows staged in LDS and writes
+ * clipped[b][k][c], k < blocks = ceil(stride / (PDSE_RESAMPLE_BLOCK ch width)), c < ch: the clipped samples of channel c among its
+ * kept frames (plain stores; the caller sums over k).  A file's bytes do not depend on B or on its place in the batch.  The checks
+ * are the call above's, made before the launch and without a device, with two differences: the grid's rows are counted as
+ * B ch <= 65535, and the LDS budget takes the factor ch - ch windows of (PDSE_RESAMPLE_BLOCK - 1) down / up + 2 jmax + 2 fp32
+ * samples beside the 8 KB image within 64 KB. */
+int pdse_wav_encode_channels(const float* x,              /* device [B ch][Lmax] */
+                             const int32_t* n_in_host,    /* host [B] */
+                             const int32_t* n_keep_host,  /* host [B] */
+                             const int32_t* n_in,         /* device [B] */
+                             const int32_t* n_keep,       /* device [B] */
+                             const double* taps,          /* device [2 half + 1], or NULL when up == down */
+                             uint8_t* out,                /* device [B][stride] */
+                             int32_t* clipped,            /* device [B][blocks][ch] */
+                             int64_t stride, int32_t B, int32_t Lmax, int32_t up, int32_t down, int32_t half, int32_t fmt,
+                             int32_t width, int32_t ch, pdse_stream_t s);
 
 /* plans: a recorded operator sequence replayed by one call (and capturable in a hipGraph) */
 typedef struct pdse_plan pdse_plan;

@@ -274,8 +274,10 @@ RANGE_BIN_TOP = RANGE_BINS - 1               # hi leaves the fp16 range
 RESAMPLE_BLOCK = 256      # PDSE_RESAMPLE_BLOCK: outputs per workgroup
 # pdse_resample_desc.fmt: 0 is the integer-PCM operator as it was (width 1 / 2 / 4, one or two channels); the others (PDSE_WAV_*)
 WAV_INT, WAV_FLOAT, WAV_ALAW, WAV_ULAW = 1, 2, 3, 4
+WAV_SPLIT = 256           # PDSE_WAV_SPLIT: OR-ed onto WAV_INT .. WAV_ULAW, the channels kept apart (out [B ch][Lmax])
 WAV_MAX_CH = 8            # PDSE_WAV_MAX_CH: channels the kernel of fmt != 0 mixes
 WAVOUT_IMAGE_BYTES = RESAMPLE_BLOCK * WAV_MAX_CH * 4 + 16     # csrc/wavout.hip: LDS image of a block's bytes, beside its input window
+WAVCH_STATIC_BYTES = WAVOUT_IMAGE_BYTES + 256                 # csrc/wavout.hip: static LDS of the channel encoder, beside its ch windows
 
 METRICS_OFF_WIN, METRICS_OFF_BASIS = 0, 512
 METRICS_OFF_CRIT = METRICS_OFF_BASIS + 480 * 1024
@@ -352,7 +354,7 @@ EXPORTS = [
     "pdse_plan_run_range",
     "pdse_plan_build_graph", "pdse_plan_launch_graph", "pdse_plan_time_ops", "pdse_plan_time_tag",
     "pdse_plan_destroy", "pdse_plan_load", "pdse_plan_region", "pdse_prior_forward", "pdse_eps_forward", "pdse_enhance",
-    "pdse_wav_encode",
+    "pdse_wav_encode", "pdse_wav_encode_channels",
 ] + [name for _, _, name in OPS]
 
 
@@ -410,6 +412,8 @@ def load():
     lib.pdse_plan_destroy.restype = None
     lib.pdse_wav_encode.argtypes = [_fp] * 8 + [_i64] + [_i32] * 8 + [C.c_void_p]
     lib.pdse_wav_encode.restype = C.c_int
+    lib.pdse_wav_encode_channels.argtypes = lib.pdse_wav_encode.argtypes
+    lib.pdse_wav_encode_channels.restype = C.c_int
     if lib.pdse_abi_version() != ABI_VERSION:
         raise PdseError("libpdse.so ABI %d != binding ABI %d" % (lib.pdse_abi_version(), ABI_VERSION))
     for kind, typ in DESC_TYPES.items():
@@ -439,7 +443,7 @@ def launch(desc, stream=0, device=None):
 
 
 def wav_encode(x, n_in_host, n_keep_host, n_in, n_keep, taps, out, clipped, stride, B, Lmax, up, down, half, fmt, width, ch,
-               stream=0, device=None):
+               stream=0, device=None, entry="pdse_wav_encode"):
     """pdse_wav_encode (include/pdse.h: the wav back end, csrc/wavout.hip): pointers as integers, plain arguments."""
     lib = load()
     on = contextlib.nullcontext()
@@ -448,8 +452,14 @@ def wav_encode(x, n_in_host, n_keep_host, n_in, n_keep, taps, out, clipped, stri
 
         on = torch.cuda.device(device)
     with on:
-        check(lib.pdse_wav_encode(x, n_in_host, n_keep_host, n_in, n_keep, taps, out, clipped, int(stride), int(B), int(Lmax),
-                                  int(up), int(down), int(half), int(fmt), int(width), int(ch), C.c_void_p(stream)), "pdse_wav_encode")
+        check(getattr(lib, entry)(x, n_in_host, n_keep_host, n_in, n_keep, taps, out, clipped, int(stride), int(B), int(Lmax),
+                                  int(up), int(down), int(half), int(fmt), int(width), int(ch), C.c_void_p(stream)), entry)
+
+
+def wav_encode_channels(*args, **kw):
+    """pdse_wav_encode_channels (include/pdse.h: the channel encoder): ``wav_encode``'s arguments with x [B ch][Lmax] and
+    clipped [B][blocks][ch]."""
+    wav_encode(*args, entry="pdse_wav_encode_channels", **kw)
 
 
 class Plan:

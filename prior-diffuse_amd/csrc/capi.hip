@@ -156,6 +156,14 @@ int pdse_wav_encode(const float* x, const int32_t* n_in_host, const int32_t* n_k
                             (hipStream_t)s);
 }
 
+// the channel encoder of the wav back end (csrc/wavout.hip): ch different rows per file
+int pdse_wav_encode_channels(const float* x, const int32_t* n_in_host, const int32_t* n_keep_host, const int32_t* n_in,
+                             const int32_t* n_keep, const double* taps, uint8_t* out, int32_t* clipped, int64_t stride, int32_t B,
+                             int32_t Lmax, int32_t up, int32_t down, int32_t half, int32_t fmt, int32_t width, int32_t ch, pdse_stream_t s) {
+  return pdse_wavch_launch(x, n_in_host, n_keep_host, n_in, n_keep, taps, out, clipped, stride, B, Lmax, up, down, half, fmt, width, ch,
+                           (hipStream_t)s);
+}
+
 int pdse_plan_create(pdse_plan** out) {
   if (!out) {
     pdse_set_error("plan_create: null out");

@@ -78,5 +78,9 @@ int pdse_gru3_launch(const pdse_gru_desc* d, hipStream_t s);   /* csrc/gru3.hip,
 int pdse_wavout_launch(const float* x, const int32_t* n_in_host, const int32_t* n_keep_host, const int32_t* n_in, const int32_t* n_keep,
                        const double* taps, uint8_t* out, int32_t* clipped, int64_t stride, int32_t B, int32_t Lmax, int32_t up,
                        int32_t down, int32_t half, int32_t fmt, int32_t width, int32_t ch, hipStream_t s);
+// csrc/wavout.hip: the channel encoder behind pdse_wav_encode_channels (x [B ch][Lmax], clipped [B][blocks][ch]; plain arguments too)
+int pdse_wavch_launch(const float* x, const int32_t* n_in_host, const int32_t* n_keep_host, const int32_t* n_in, const int32_t* n_keep,
+                      const double* taps, uint8_t* out, int32_t* clipped, int64_t stride, int32_t B, int32_t Lmax, int32_t up,
+                      int32_t down, int32_t half, int32_t fmt, int32_t width, int32_t ch, hipStream_t s);
 int pdse_range_validate(const pdse_range_desc* d);               /* reads the row table back and checks it (direct launches, plan_add) */
 #endif

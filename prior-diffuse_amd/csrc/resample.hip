@@ -27,6 +27,8 @@
 //   binary64 one conversion to fp32, round to nearest even (v_cvt_f32_f64); beyond the fp32 range: infinity
 //   G.711    the 16-bit linear value of the code, / 32768
 //   mix      fp32 sum of the channels in channel order, one division by (float)ch (correctly rounded: hipcc's default)
+// wav_split_kernel<FMT, WIDTH> (fmt | PDSE_WAV_SPLIT) is wav_kernel without the mix: out has B ch rows, row b ch + c is channel
+// c of utterance b decoded alone (wavio.read_channels) and converted by the same steps; the row index comes from the grid.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -164,17 +166,19 @@ struct WavFrame {
 // with the frame decode as a parameter: frame(d, base, k) is frame k of the utterance at byte `base`, mixed to mono.  resample_kernel
 // itself is kept as written rather than rebuilt on this function: going through it changes the register allocation of the six
 // instantiations fmt == 0 launches, and those are to stay the code they were.
+// b is the utterance (n_in, offs) and y the row of out; the dense kernel passes blockIdx.y for both.
 template <class Frame>
-__device__ __forceinline__ void resample_block(const pdse_resample_desc& d, const int jmax, const int win, const Frame& frame) {
+__device__ __forceinline__ void resample_block(const pdse_resample_desc& d, const int jmax, const int win, const Frame& frame, const int b,
+                                               const int y) {
   extern __shared__ float xs[];   // [win] decoded samples k_lo .. k_lo + win - 1 (0 outside the utterance)
-  const int b = blockIdx.y, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   const int64_t n0 = (int64_t)blockIdx.x * RS_BLOCK;
   const int64_t n_in = d.n_in[b];
   const int64_t base = d.offs[b];
   const int64_t up = d.up, down = d.down;
   const int64_t n_full = (n_in * up + down - 1) / down;
   const int64_t n_out = n_full < d.Lmax ? n_full : (int64_t)d.Lmax;
-  float* const row = d.out + (int64_t)b * d.Lmax;
+  float* const row = d.out + (int64_t)y * d.Lmax;
   const int64_t n = n0 + tid;
   if (n0 >= n_out || n_in < 1) {   // the whole block lies in the row's zero tail (uniform over the workgroup)
     if (n < d.Lmax) row[n] = 0.0f;
@@ -217,7 +221,28 @@ __device__ __forceinline__ void resample_block(const pdse_resample_desc& d, cons
 
 template <int FMT, int WIDTH>
 __global__ __launch_bounds__(RS_BLOCK) void wav_kernel(const pdse_resample_desc d, const int jmax, const int win) {
-  resample_block(d, jmax, win, WavFrame<FMT, WIDTH>());
+  resample_block(d, jmax, win, WavFrame<FMT, WIDTH>(), blockIdx.y, blockIdx.y);
+}
+
+// ---- fmt | PDSE_WAV_SPLIT: the channels kept apart ---------------------------------------------------------------------------------
+// Channel c of frame k, decoded alone: no mix arithmetic touches the sample (wavio.read_channels).  The frame test is the dense
+// kernel's - a frame that would end beyond the buffer reads as zero in every channel.
+template <int FMT, int WIDTH>
+struct WavChannel {
+  int c;
+  __device__ __forceinline__ float operator()(const pdse_resample_desc& d, int64_t base, int64_t k) const {
+    const int ch = d.ch;
+    const int64_t at = base + k * (int64_t)(WIDTH * ch);
+    if (at < 0 || at + WIDTH * ch > d.pcm_bytes) return 0.0f;
+    return wav_sample<FMT, WIDTH>(d.pcm + at + c * WIDTH);
+  }
+};
+
+// Row blockIdx.y = b ch + c of out[B ch][Lmax] is channel c of utterance b: the dense kernel's steps on that channel's samples.
+template <int FMT, int WIDTH>
+__global__ __launch_bounds__(RS_BLOCK) void wav_split_kernel(const pdse_resample_desc d, const int jmax, const int win) {
+  const int y = blockIdx.y, b = y / d.ch;
+  resample_block(d, jmax, win, WavChannel<FMT, WIDTH>{y - b * d.ch}, b, y);
 }
 
 template <int WIDTH, int CH>
@@ -234,22 +259,33 @@ void launch_wav(const pdse_resample_desc& d, int jmax, int win, hipStream_t s) {
   hipLaunchKernelGGL((wav_kernel<FMT, WIDTH>), grid, dim3(RS_BLOCK), lds, s, d, jmax, win);
 }
 
+template <int FMT, int WIDTH>
+void launch_split(const pdse_resample_desc& d, int jmax, int win, hipStream_t s) {
+  const dim3 grid((unsigned)((d.Lmax + RS_BLOCK - 1) / RS_BLOCK), (unsigned)(d.B * d.ch));
+  const size_t lds = d.up == d.down ? 0 : (size_t)win * sizeof(float);
+  hipLaunchKernelGGL((wav_split_kernel<FMT, WIDTH>), grid, dim3(RS_BLOCK), lds, s, d, jmax, win);
+}
+
 }  // namespace
 
 int pdse_resample_launch(const pdse_resample_desc* d, hipStream_t s) {
   REQ(d && d->pcm && d->offs && d->n_in_host && d->n_in && d->out, "resample: null pointer");
   REQ(d->B >= 1 && d->B <= 65535, "resample: B < 1 (or above 65535)");
   REQ(d->up >= 1 && d->down >= 1 && d->half >= 0, "resample: up < 1, down < 1 or half < 0");
+  // fmt | PDSE_WAV_SPLIT (fmt one of PDSE_WAV_*): the channels kept apart, out[B ch][Lmax]
+  const bool split = d->fmt > 0 && (d->fmt & PDSE_WAV_SPLIT) != 0;
+  const int fmt = split ? d->fmt & ~PDSE_WAV_SPLIT : d->fmt;
   if (d->fmt == 0) {
     REQ(d->width == 1 || d->width == 2 || d->width == 4, "resample: width must be 1, 2 or 4 bytes");
     REQ(d->ch == 1 || d->ch == 2, "resample: ch must be 1 or 2");
   } else {
     const int w = d->width;
-    REQ(d->fmt >= PDSE_WAV_INT && d->fmt <= PDSE_WAV_ULAW, "resample: unknown fmt (0 or PDSE_WAV_INT, _FLOAT, _ALAW, _ULAW)");
-    REQ(d->fmt != PDSE_WAV_INT || (w >= 1 && w <= 4), "resample: fmt PDSE_WAV_INT takes a width of 1, 2, 3 or 4 bytes");
-    REQ(d->fmt != PDSE_WAV_FLOAT || w == 4 || w == 8, "resample: fmt PDSE_WAV_FLOAT takes a width of 4 or 8 bytes");
-    REQ((d->fmt != PDSE_WAV_ALAW && d->fmt != PDSE_WAV_ULAW) || w == 1, "resample: fmt PDSE_WAV_ALAW / _ULAW takes a width of 1 byte");
+    REQ(fmt >= PDSE_WAV_INT && fmt <= PDSE_WAV_ULAW, "resample: unknown fmt (0 or PDSE_WAV_INT, _FLOAT, _ALAW, _ULAW)");
+    REQ(fmt != PDSE_WAV_INT || (w >= 1 && w <= 4), "resample: fmt PDSE_WAV_INT takes a width of 1, 2, 3 or 4 bytes");
+    REQ(fmt != PDSE_WAV_FLOAT || w == 4 || w == 8, "resample: fmt PDSE_WAV_FLOAT takes a width of 4 or 8 bytes");
+    REQ((fmt != PDSE_WAV_ALAW && fmt != PDSE_WAV_ULAW) || w == 1, "resample: fmt PDSE_WAV_ALAW / _ULAW takes a width of 1 byte");
     REQ(d->ch >= 1 && d->ch <= PDSE_WAV_MAX_CH, "resample: with fmt != 0 ch must be 1 .. 8");
+    REQ(!split || (int64_t)d->B * d->ch <= 65535, "resample: with PDSE_WAV_SPLIT B ch must not pass 65535 rows");
   }
   REQ(d->Lmax >= 1 && d->pcm_bytes >= 0, "resample: Lmax < 1 or pcm_bytes < 0");
   for (int b = 0; b < d->B; ++b) {
@@ -262,6 +298,19 @@ int pdse_resample_launch(const pdse_resample_desc* d, hipStream_t s) {
   const int64_t win = ((int64_t)(RS_BLOCK - 1) * d->down) / d->up + 2 * (int64_t)jmax + 2;
   REQ(d->up == d->down || win * (int64_t)sizeof(float) <= RS_LDS_MAX,
       "resample: the input window of one block of outputs does not fit the LDS budget (down / up or half too large)");
+  if (split) {
+    switch (fmt * 16 + d->width) {
+      case PDSE_WAV_INT * 16 + 1: launch_split<PDSE_WAV_INT, 1>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_INT * 16 + 2: launch_split<PDSE_WAV_INT, 2>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_INT * 16 + 3: launch_split<PDSE_WAV_INT, 3>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_INT * 16 + 4: launch_split<PDSE_WAV_INT, 4>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_FLOAT * 16 + 4: launch_split<PDSE_WAV_FLOAT, 4>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_FLOAT * 16 + 8: launch_split<PDSE_WAV_FLOAT, 8>(*d, jmax, (int)win, s); break;
+      case PDSE_WAV_ALAW * 16 + 1: launch_split<PDSE_WAV_ALAW, 1>(*d, jmax, (int)win, s); break;
+      default: launch_split<PDSE_WAV_ULAW, 1>(*d, jmax, (int)win, s); break;
+    }
+    return pdse_check_launch("resample");
+  }
   if (d->fmt != 0) {
     switch (d->fmt * 16 + d->width) {
       case PDSE_WAV_INT * 16 + 1: launch_wav<PDSE_WAV_INT, 1>(*d, jmax, (int)win, s); break;

@@ -59,6 +59,11 @@ def parse_args_and_config(argv=None):
                    help="(not a flag of the reference) --generate: write every file at its source's rate, length and channel count, in "
                         "its source's encoding (16/24/32-bit PCM, float as binary32, 8-bit and G.711 as 16-bit PCM; every channel "
                         "carries the enhanced mono signal), encoded on the device; clipped files are logged; default: 16 kHz, 16-bit, mono")
+    p.add_argument("--per-channel", action="store_true",
+                   help="(not a flag of the reference) --generate: enhance every channel of a file with 2 .. 8 channels on its own "
+                        "(its own noise, one exact ragged pass per file; the DB-AIAT priors need --masked-prior) and write the file "
+                        "with that many different channels - at 16 kHz, 16-bit, or with --keep-format in the source's rate and "
+                        "encoding; mono files are untouched; default: the network enhances the mono mix")
     args = p.parse_args(argv)
     args.log = os.path.join(args.assets, "log", args.doc)
     args.checkpoint = os.path.join(args.assets, "checkpoint", args.doc)

@@ -26,7 +26,7 @@ import torch
 from . import _lib as L
 from . import nets, ops, raggedplan, wavdev, wavio
 from .params import PRIOR_SCALE_C, params as default_params
-from .pipeline import SamplerPipeline, _expect, ragged_args
+from .pipeline import RAGGED_PRIORS, SamplerPipeline, _expect, ragged_args
 from .schedule import inference_schedule as _inference_schedule
 
 
@@ -76,9 +76,10 @@ class ComplexDDPMTrainer(object):
     masked_prior = False   # exact ragged batches of the DB-AIAT priors on the length-masked kernels (constructor)
     wav_formats = "pcm"    # what generate_wav opens: "pcm" (the wave module's integer PCM) or "all" (constructor)
     wav_out = "pcm16"      # what generate_wav writes: "pcm16" (16 kHz, 16-bit, mono) or "source" (the file's own rate and format)
+    channels = "mix"       # what generate_wav enhances of a multichannel file: "mix" (the mono mix) or "each" (every channel)
 
     def __init__(self, args, config, device=None, prior_state_dict=None, ddpm_state_dict=None, params=None, exclusive=None,
-                 dtype=None, split=None, audit=None, masked_prior=None, wav_formats=None, wav_out=None):
+                 dtype=None, split=None, audit=None, masked_prior=None, wav_formats=None, wav_out=None, channels=None):
         """args: .retrain .joint .draw .sigma .checkpoint .generated_wav
         config: .model.name, .train.{fft_num, win_size, win_shift, feat_type}
         Weights come from ``<args.checkpoint>/best_checkpoint.pth`` under the reference's
@@ -118,7 +119,27 @@ class ComplexDDPMTrainer(object):
         (``wavdev.encode``: ``wavio.resample`` + ``wavio.encode`` byte for byte).  The network enhances the mono mix, so every
         channel of a written file carries the same signal.  A file in which the integer clamp changed samples - an enhancer's
         output is not bounded by +-1 - is written and logged with one warning that names it and the count.  None: "source" when
-        the CLI set ``args.keep_format`` (``main.py --keep-format``), else "pcm16"."""
+        the CLI set ``args.keep_format`` (``main.py --keep-format``), else "pcm16".
+        channels: what ``generate_wav`` enhances of a file with 2 .. 8 channels, in all three modes.  "mix": the mono mix, as
+        above.  "each": every channel on its own - the file is decoded with its channels kept apart (``wavdev.load(channels=
+        "each")``: the rows of ``wavio.read_channels``), channel c gets its own x_T (and its ``rng_fidelity`` discards), drawn in
+        channel order where the file's single draw stood, and the C channels are enhanced as C utterances of equal length: one
+        exact ragged pass of B = C (``batch=1``; the DB-AIAT priors need ``masked_prior=True`` for it, else the first
+        multichannel file raises their ValueError), rows of the ragged windows (``batch=N``), or one item [C, L] in flight
+        (``inflight=N``; GCRN and DiffUNet priors).  The file is written with C different channels through
+        ``wavdev.encode_channels``: at its source's rate, length and encoding with ``wav_out="source"``, at 16 kHz and 16 bits
+        with "pcm16".  Contract: channel c of every written file is what the same trainer writes for a mono file holding that
+        channel, given the same x_T - byte for byte on an ``exclusive=False`` trainer, whose kernels do not depend on the batch
+        size, and within the persistent-LSTM difference (1e-5, see ``enhance_stream``) on the default trainer, where ``enhance``
+        at B <= 4 may take the persistent launch.  A seeded run on a stereo file draws what the same run draws on its two
+        channels stored as mono files that sort next to each other.  Mono files behave exactly as under "mix"; a source with
+        more than 8 channels is enhanced as the mix and written as under "mix" (logged).  No x_T is shared between channels, and
+        the metrics score the mix.  None: "each" when the CLI set ``args.per_channel`` (``main.py --per-channel``), else "mix"."""
+        if channels is None:
+            channels = "each" if getattr(args, "per_channel", False) else "mix"
+        if channels not in ("mix", "each"):
+            raise ValueError("channels must be 'mix' or 'each'")
+        self.channels = channels
         if wav_out is None:
             wav_out = "source" if getattr(args, "keep_format", False) else "pcm16"
         if wav_out not in ("pcm16", "source"):
@@ -566,18 +587,21 @@ class ComplexDDPMTrainer(object):
     def _file_loop(self, data_path, rng_fidelity, windows, enhance):
         """The file loop of ``generate_wav``.  windows(n) -> [(lo, hi)]: the slices of the sorted paths that are read at once.
         enhance: a generator function; it is handed an iterator of windows, each an iterator of the window's readable files as
-        ``(path, wav [len], x_T)``, and yields ``(path, enhanced [len])`` in path order.  Nothing is read or drawn before
+        ``(path, wav [len], x_T)``, and yields ``(path, enhanced [len])`` in path order (``channels="each"``, a file of C > 1
+        channels: wav [C, len], x_T [C, 2, T, 161], enhanced [C, len]).  Nothing is read or drawn before
         ``enhance`` asks for it, and x_T and discards are drawn in the order it asks: path order."""
         paths = sorted(glob.glob(data_path + "/*.wav"))
         ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0   # a plan's steps less one
 
         def drawn(window):
             for path, wav in self._load_window(window):
-                shape = (1, 2, 1 + wav.numel() // 160, 161)
-                x_T = self._x_T(shape, None)                                  # :947-950 randn_like(init): the file's draw, kept for a repeat
-                for _ in range(ndiscard):
-                    torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
-                yield path, wav, x_T
+                shape = (1, 2, 1 + wav.shape[-1] // 160, 161)
+                x_T = []
+                for _ in range(1 if wav.dim() == 1 else wav.shape[0]):        # channels="each": a draw per channel, in channel order
+                    x_T.append(self._x_T(shape, None))                        # :947-950 randn_like(init): the file's draw, kept for a repeat
+                    for _ in range(ndiscard):
+                        torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
+                yield path, wav, x_T[0] if wav.dim() == 1 else torch.cat(x_T)
 
         written = []
         with torch.no_grad():
@@ -594,34 +618,49 @@ class ComplexDDPMTrainer(object):
         files = chain.from_iterable(windows)
         if inflight == 1:
             for path, wav, x_T in files:
-                yield path, self.enhance(wav[None], x_T=x_T)[0]
+                if wav.dim() == 1:
+                    yield path, self.enhance(wav[None], x_T=x_T)[0]
+                else:                                # a file's channels: one exact ragged pass of equal lengths, nothing padded
+                    yield path, torch.stack(self._enhance_ragged(list(wav), list(x_T), wav.shape[1]))
             return
-        paths = deque()                              # of the files handed to the stream and not yet handed back
+        paths = deque()                              # (path, mono) of the files handed to the stream and not yet handed back
 
         def items():
             for path, wav, x_T in files:
-                paths.append(path)
-                yield wav[None], x_T
+                if wav.dim() == 2 and self.prior_name not in RAGGED_PRIORS:
+                    raise ValueError("generate_wav(inflight=%d) with channels='each': the channels of %s would share a dense pass "
+                                     "of prior %r, which is built for %s only" % (inflight, path, self.prior_name, ", ".join(RAGGED_PRIORS)))
+                paths.append((path, wav.dim() == 1))
+                yield (wav[None] if wav.dim() == 1 else wav), x_T
 
         for out, _ in self.enhance_stream(items(), inflight=inflight):
-            yield paths.popleft(), out[0]
+            path, mono = paths.popleft()
+            yield path, out[0] if mono else out
 
     def _enhance_windows(self, windows, batch):
         """``_file_loop``'s files ``batch`` per pass: a window sorted by length, in exact ragged batches (``raggedplan.buckets``)."""
         for window in windows:
             files = list(window)                     # path order: the generator sees what the B = 1 loop shows it
-            outs = [None] * len(files)
-            for idx, L_pad in raggedplan.buckets([wav.numel() for _, wav, _ in files], batch):
-                res = self._enhance_ragged([files[i][1] for i in idx], [files[i][2] for i in idx], L_pad)
+            # the rows of the window: a file's waveform, or (channels="each") each of its channels, with its own x_T
+            rows = [(w, x) for _, wav, x_T in files for w, x in ([(wav, x_T)] if wav.dim() == 1 else zip(wav, x_T))]
+            outs = [None] * len(rows)
+            for idx, L_pad in raggedplan.buckets([w.numel() for w, _ in rows], batch):
+                res = self._enhance_ragged([rows[i][0] for i in idx], [rows[i][1] for i in idx], L_pad)
                 for i, r in zip(idx, res):
                     outs[i] = r
-            yield from zip((path for path, _, _ in files), outs)
+            r = 0
+            for path, wav, _ in files:               # regrouped per file
+                n = 1 if wav.dim() == 1 else wav.shape[0]
+                yield path, outs[r] if wav.dim() == 1 else torch.stack(outs[r:r + n])
+                r += n
 
     def _load_window(self, paths):
         """[(path, wav [len] on the device)] of the readable files of ``paths``, in order, decoded in one call ([B, Lmax] on the
         device, ``read_wav``'s bits); where that fails at least one file cannot be read: they are then read one by one, and the
         unreadable ones are logged and skipped."""
         try:
+            if self.channels == "each":
+                return self._load_channels(paths)
             wav, lens = wavdev.load(paths, self.device, 16000, formats=self.wav_formats)
             return [(p, wav[i, :lens[i]]) for i, p in enumerate(paths)]
         except (ValueError, EOFError, wavio.wave.Error) as e:
@@ -630,11 +669,63 @@ class ComplexDDPMTrainer(object):
                 return []
         return [f for p in paths for f in self._load_window([p])]
 
+    def _load_channels(self, paths):
+        """``_load_window``'s decode under ``channels="each"``: [(path, wav)] with wav [len] for a mono file and [C, len] for one
+        of C = 2 .. 8 channels, the rows of ``wavio.read_channels``.  A source with more channels (or a header ``wavio.probe``
+        does not take) goes through the mix's loader and is enhanced as the mix."""
+        def wide(path):
+            try:
+                return wavio.probe(path)[1] > L.WAV_MAX_CH
+            except (ValueError, OSError):
+                return True
+
+        mix = [p for p in paths if wide(p)]
+        each = [p for p in paths if p not in mix]
+        found = {}
+        if each:
+            wav, lens, chans = wavdev.load(each, self.device, 16000, formats=self.wav_formats, channels="each")
+            r = 0
+            for p, ch in zip(each, chans):
+                found[p] = wav[r, :lens[r]] if ch == 1 else wav[r:r + ch, :lens[r]]
+                r += ch
+        if mix:
+            wav, lens = wavdev.load(mix, self.device, 16000, formats=self.wav_formats)
+            for i, p in enumerate(mix):
+                logging.warning("%s: more than %d channels, enhanced as the mix", p, L.WAV_MAX_CH)
+                found[p] = wav[i, :lens[i]]
+        return [(p, found[p]) for p in paths]
+
+    def _write_channels(self, dst, out, src):
+        """The writer of a file whose C = 2 .. 8 channels were enhanced apart (``channels="each"``).  out: [C, len] at 16 kHz.
+        "source": ``_write_wav``'s steps with ``wavdev.encode_channels`` - the source's rate, frame count and encoding, channel
+        c from row c.  "pcm16" (or a header ``wavio.probe`` refuses): 16 kHz, 16-bit, C channels through the same encoder at
+        ratio 1 - per channel the payload ``wavio.write_wav`` writes.  One warning for a file that clipped, with the counts per
+        channel."""
+        out = torch.as_tensor(out, dtype=torch.float32).to(self.device)
+        C, n = int(out.shape[0]), int(out.shape[1])
+        rate, fmt, width, keep = 16000, wavio.WAV_INT, 2, n
+        if self.wav_out == "source":
+            try:
+                rate, _, tag, width, n_src = wavio.probe(src)
+                tag, width = wavio.target_of((tag, width))
+                fmt = wavio.WAV_FLOAT if tag == 3 else wavio.WAV_INT
+                keep = min(n_src, wavio.out_len(n, 16000, rate))
+            except ValueError as e:
+                logging.warning("%s: written at 16 kHz, 16-bit: %s", dst, e)
+                rate, fmt, width, keep = 16000, wavio.WAV_INT, 2, n
+        (payload,), (clipped,) = wavdev.encode_channels(out, [n] * C, [C], self.device, rate, fmt, width, n_keep=[keep])
+        wavio.write_payload(dst, payload, rate, fmt, width, C)
+        if any(clipped):
+            logging.warning("%s: %s of %d samples per channel clipped at the %d-bit range", dst, "/".join(str(c) for c in clipped), keep, 8 * width)
+
     def _write_wav(self, dst, out, src):
         """The writer of the file loop.  out: the enhanced waveform of the file ``src`` at 16 kHz, 1-D - a numpy array or a
         tensor.  "pcm16": ``wavio.write_wav``.  "source": the header of ``src`` is read again (``wavio.probe``), the waveform goes
         through ``wavdev.encode`` at the source's rate, cut to the source's frame count, and the frames are written behind a plain
-        header (``wavio.write_payload``).  A source with more channels than the encoder interleaves (8) is written mono."""
+        header (``wavio.write_payload``).  A source with more channels than the encoder interleaves (8) is written mono.
+        A 2-D ``out`` - [C, len], the channels of a file enhanced apart - goes to ``_write_channels``."""
+        if getattr(out, "ndim", 1) == 2:
+            return self._write_channels(dst, out, src)
         probe = None
         if self.wav_out == "source":
             try:

@@ -21,7 +21,16 @@ The way back (opt-in: ``generate_wav`` of a trainer built with ``wav_out="source
     encode(rows, lens, device, rate, fmt, width, ch, n_keep=None)   -> (list of bytes objects, list of clip counts)
 
 one launch of csrc/wavout.hip (include/pdse.h: pdse_wav_encode) converts enhanced waveforms to their sources' rate, encodes them
-as 16-, 24- or 32-bit PCM or binary32 and interleaves the channels; the oracle is ``wavio.resample`` + ``wavio.encode``."""
+as 16-, 24- or 32-bit PCM or binary32 and interleaves the channels; the oracle is ``wavio.resample`` + ``wavio.encode``.
+
+Per-channel enhancement (opt-in: a trainer built with ``channels="each"``) keeps a file's channels apart both ways:
+
+    load(paths, device, formats=..., channels="each")                 -> (wav [R, Lmax], lens [R], chans [len(paths)])
+    decode(..., split=True)                                           -> (wav [B * ch, Lmax], lens [B * ch])
+    encode_channels(rows, lens, chans, device, rate, fmt, width, n_keep=None) -> (list of bytes objects, list of per-channel counts)
+
+the split mode of the front end's second kernel (``L.WAV_SPLIT``; the oracle is ``wavio.read_channels``) and the channel encoder of
+csrc/wavout.hip (pdse_wav_encode_channels; ``wavio.resample`` per row + ``wavio.encode_channels``)."""
 import numpy as np
 
 from . import _lib as L
@@ -60,14 +69,17 @@ def _ratio(rate, sr, half_width=16):
     return up, down, half_width * max(up, down)
 
 
-def decode(pcm_list, channels, width, rate, device, sr=16000, fmt=0):
+def decode(pcm_list, channels, width, rate, device, sr=16000, fmt=0, split=False):
     """pcm_list: the interleaved little-endian PCM frames of B utterances of one format, each a uint8 array (or bytes) of whole
     frames (``wavio.read_pcm``); channels 1 or 2, width 1, 2 or 4 bytes, every utterance at least one frame long.
     Returns (wav, lens): wav [B, Lmax] fp32 on ``device`` with utterance b in wav[b, :lens[b]] - ``wavio.read_wav``'s samples bit
     for bit - and zeros behind it.  Two uploads and one launch on the current stream; asynchronous.
     fmt (default 0: the above): ``L.WAV_INT`` (width 1 .. 4), ``L.WAV_FLOAT`` (width 4 or 8), ``L.WAV_ALAW`` or ``L.WAV_ULAW``
     (width 1) with 1 .. 8 channels takes the kernel of the other encodings (``wavio.read_frames``); the rows are then
-    ``wavio.read_any``'s bits.  The library refuses every other combination before the launch."""
+    ``wavio.read_any``'s bits.  The library refuses every other combination before the launch.
+    split=True keeps the channels apart (``L.WAV_SPLIT``; fmt 0 is taken as ``L.WAV_INT``, which decodes the same widths): wav
+    [B * channels, Lmax] and lens [B * channels], row b * channels + c being channel c of utterance b at the utterance's length -
+    ``wavio.read_channels``'s rows bit for bit."""
     import torch
 
     device = torch.device(device)
@@ -98,7 +110,10 @@ def decode(pcm_list, channels, width, rate, device, sr=16000, fmt=0):
     with torch.cuda.device(device):
         pcm_dev = torch.from_numpy(pcm if pcm.flags.writeable else pcm.copy()).to(device)
         meta_dev = torch.from_numpy(meta).to(device)
-        out = torch.empty(B, Lmax, dtype=torch.float32, device=device)
+        if split:
+            fmt = (int(fmt) or L.WAV_INT) | L.WAV_SPLIT
+            lens = [n for n in lens for _ in range(int(channels))]
+        out = torch.empty(len(lens) if split else B, Lmax, dtype=torch.float32, device=device)
         d = L.ResampleDesc()
         d.pcm, d.offs, d.n_in, d.n_in_host = pcm_dev.data_ptr(), meta_dev.data_ptr(), meta_dev.data_ptr() + 8 * B, n_in32.ctypes.data
         d.taps, d.out = (taps.data_ptr() if taps is not None else None), out.data_ptr()
@@ -108,17 +123,29 @@ def decode(pcm_list, channels, width, rate, device, sr=16000, fmt=0):
     return out, lens
 
 
-def load(paths, device, sr=16000, formats="pcm"):
+def load(paths, device, sr=16000, formats="pcm", channels="mix"):
     """Read wav files and bring them to ``sr`` mono fp32 on the device: (wav [B, Lmax], lens) with file b in wav[b, :lens[b]],
     equal to ``wavio.read_wav(paths[b], sr)`` bit for bit, zeros behind it.  Raises what ``wavio.read_wav`` raises for a file it
     cannot read.
     formats="all": the files are opened with ``wavio.read_frames`` (24-bit, float, G.711, extensible headers, up to 8 channels on
     the device) and every row is ``wavio.read_any``'s; only files with more channels, without frames or with a rate pair beyond the
     kernel's window take ``read_any`` on the host.  A float file whose decoded samples are not all finite raises ValueError
-    naming it (one ``isfinite().all()`` per float row, a synchronisation; integer files are not looked at)."""
+    naming it (one ``isfinite().all()`` per float row, a synchronisation; integer files are not looked at).
+    channels="each" (default "mix": the above, with the above's return value) keeps the channels apart: (wav [R, Lmax], lens [R],
+    chans [len(paths)]) with one row per channel, in file order, then channel order - file i's rows start at sum(chans[:i]) - each
+    ``wavio.read_channels``'s row bit for bit.  Every file is opened with ``wavio.read_frames`` and decoded by the kernel's split
+    mode (``decode(split=True)``), whatever ``formats`` is; formats="pcm" still refuses, with the same exception, what
+    ``wavio.read_wav`` refuses.  More than 8 channels, no frames or a rate pair beyond the kernel's window:
+    ``wavio.read_channels`` on the host.  The finiteness check of float files applies per row."""
     import torch
 
     device = torch.device(device)
+    if channels == "each":
+        if formats not in ("pcm", "all"):
+            raise ValueError("formats must be 'pcm' or 'all', got %r" % (formats,))
+        return _load_each(paths, device, sr, formats)
+    if channels != "mix":
+        raise ValueError("channels must be 'mix' or 'each', got %r" % (channels,))
     if formats == "all":
         return _load_all(paths, device, sr)
     if formats != "pcm":
@@ -174,6 +201,44 @@ def _load_all(paths, device, sr):
     return out, lens
 
 
+def _load_each(paths, device, sr, formats):
+    """``load(channels="each")``: one split launch per (fmt, channels, width, rate)."""
+    import torch
+
+    files, groups, is_float = [None] * len(paths), {}, []    # files[i]: the [ch, n] rows of file i
+    for i, path in enumerate(paths):
+        if formats == "pcm":
+            wavio.read_pcm(path)                             # raises what ``read_wav`` raises; the frames are read_frames' below
+        frames, n, ch, width, rate, fmt = wavio.read_frames(path)
+        is_float.append(fmt == wavio.WAV_FLOAT)
+        if not kernel_covers(ch, n, rate, sr, max_channels=L.WAV_MAX_CH):
+            files[i] = torch.from_numpy(wavio.read_channels(path, sr)).to(device)
+        else:
+            groups.setdefault((fmt, ch, width, rate), []).append((i, frames))
+    chans = [None] * len(paths)
+    one = len(groups) == 1 and all(f is None for f in files)
+    for (fmt, ch, width, rate), items in groups.items():
+        wav, lens = decode([f for _, f in items], ch, width, rate, device, sr, fmt=fmt, split=True)
+        for k, (i, _) in enumerate(items):
+            files[i] = wav[k * ch:(k + 1) * ch, :lens[k * ch]]
+        if one:
+            result = wav, lens
+    for i, f in enumerate(files):
+        chans[i] = int(f.shape[0])
+        if is_float[i]:                                      # finite in every channel
+            for c in range(chans[i]):
+                _finite(f[c], "%s (channel %d)" % (paths[i], c) if chans[i] > 1 else paths[i])
+    if one:
+        return result[0], result[1], chans
+    lens = [int(f.shape[1]) for f in files for _ in range(f.shape[0])]
+    out = torch.zeros(len(lens), max(lens + [0]), dtype=torch.float32, device=device)
+    r = 0
+    for f in files:
+        out[r:r + f.shape[0], :f.shape[1]] = f
+        r += f.shape[0]
+    return out, lens, chans
+
+
 def _finite(row, path):
     import torch
 
@@ -182,10 +247,13 @@ def _finite(row, path):
 
 
 # ---- the way back (opt-in: generate_wav(wav_out="source")): csrc/wavout.hip, include/pdse.h: the wav back end -------------------
-def encoder_covers(rate, sr=16000):
+def encoder_covers(rate, sr=16000, ch=None):
     """Whether csrc/wavout.hip converts ``sr`` to ``rate``: the input window of one workgroup's frames ((RESAMPLE_BLOCK - 1) down /
-    up + 2 jmax + 2 fp32 samples) beside the 8 KB image of its bytes within 64 KB of LDS (output rates down to about 300 Hz)."""
+    up + 2 jmax + 2 fp32 samples) beside the 8 KB image of its bytes within 64 KB of LDS (output rates down to about 300 Hz).
+    ch: the question for the channel encoder (``encode_channels``), which stages ``ch`` such windows."""
     up, down, half = _ratio(sr, rate)
+    if ch is not None:
+        return up == down or 4 * int(ch) * ((L.RESAMPLE_BLOCK - 1) * down // up + 2 * (half // up + 1) + 2) + L.WAVCH_STATIC_BYTES <= 64 * 1024
     return up == down or 4 * ((L.RESAMPLE_BLOCK - 1) * down // up + 2 * (half // up + 1) + 2) + L.WAVOUT_IMAGE_BYTES + 64 <= 64 * 1024
 
 
@@ -252,3 +320,70 @@ def encode_rows(rows, lens, device, rate, fmt, width, ch, n_keep=None, sr=16000)
         host = buf.cpu().numpy()
     counts = host[counts_at:].view(np.int32).reshape(B, blocks).sum(axis=1)
     return host[:B * stride].reshape(B, stride), keep, [int(c) for c in counts]
+
+
+def encode_channels(rows, lens, chans, device, rate, fmt, width, n_keep=None, sr=16000):
+    """``encode`` for files whose channels differ: (list of bytes objects, list of per-channel clip-count lists), one of each per
+    file.  rows: a [R, Lmax] fp32 tensor on ``device`` (or a list of 1-D tensors) with one row per channel, in file order, then
+    channel order, as ``load(channels="each")`` returns them; lens [R]: the rows' lengths, equal within a file; chans: the files'
+    channel counts (1 .. 8 each, sum R); n_keep[i] (per file; default: all ``wavio.out_len(len_i, sr, rate)`` frames) cuts file i
+    to its first frames.  Element i is ``wavio.encode_channels`` of the file's rows after ``wavio.resample(row, sr, rate)[:n_keep[i]]``,
+    bytes and counts.  One upload (the lengths), one launch of csrc/wavout.hip's channel encoder (include/pdse.h:
+    pdse_wav_encode_channels) and one copy back per distinct channel count.  A rate pair whose ``ch`` windows the kernel's LDS
+    does not hold (``encoder_covers(rate, sr, ch)``) takes those host functions; the kernel itself has no CPU fallback."""
+    import torch
+
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.PdseError("wavdev.encode_channels runs on the GPU only (no CPU fallback); wavio.encode_channels is the host path")
+    chans = [int(c) for c in chans]
+    for ch in sorted(set(chans)):
+        wavio._check_target(fmt, width, ch)
+    if not torch.is_tensor(rows):
+        rows = torch.nn.utils.rnn.pad_sequence([torch.as_tensor(r, dtype=torch.float32).flatten().to(device) for r in rows], batch_first=True)
+    rows = rows.to(device, torch.float32).contiguous()
+    if rows.dim() != 2 or rows.shape[0] != len(lens) or rows.shape[0] != sum(chans) or rows.shape[0] < 1:
+        raise ValueError("rows: [R, Lmax] with one length per row and R the sum of the channel counts")
+    Lmax = int(rows.shape[1])
+    lens = [int(n) for n in lens]
+    if any(n < 1 or n > Lmax for n in lens):
+        raise ValueError("lens: 1 .. %d samples per row" % Lmax)
+    first = [sum(chans[:i]) for i in range(len(chans))]      # a file's first row
+    if any(len(set(lens[r:r + ch])) != 1 for r, ch in zip(first, chans)):
+        raise ValueError("lens: the rows of a file have one length")
+    flen = [lens[r] for r in first]
+    n_out = [wavio.out_len(n, sr, rate) for n in flen]
+    keep = n_out if n_keep is None else [int(k) for k in n_keep]
+    if len(keep) != len(chans) or any(k < 0 or k > n for k, n in zip(keep, n_out)):
+        raise ValueError("n_keep: one count per file, at most the frames the file converts to")
+    payloads, counts = [None] * len(chans), [None] * len(chans)
+    for ch in sorted(set(chans)):
+        ids = [i for i, c in enumerate(chans) if c == ch]
+        B, fb = len(ids), ch * int(width)
+        k_ch, n_ch = [keep[i] for i in ids], [flen[i] for i in ids]
+        x = rows if B == len(chans) else rows[[first[i] + c for i in ids for c in range(ch)]]
+        if not encoder_covers(rate, sr, ch):
+            host = x.cpu().numpy()
+            for b, i in enumerate(ids):
+                with np.errstate(over="ignore", invalid="ignore"):
+                    y = [wavio.resample(host[b * ch + c, :n_ch[b]], sr, rate)[:k_ch[b]] for c in range(ch)]
+                payloads[i], counts[i] = wavio.encode_channels(np.stack(y), fmt, width)
+            continue
+        stride = max(max(k_ch) * fb, 1)
+        taps, up, down, half = _device_taps(device, sr, rate)
+        blocks = -(-stride // (L.RESAMPLE_BLOCK * fb))
+        counts_at = -(-B * stride // 4) * 4                  # the int32 counts behind the files' bytes, in the same buffer: one copy back
+        meta = np.array(n_ch + k_ch, dtype=np.int32)
+        with torch.cuda.device(device):
+            meta_dev = torch.from_numpy(meta).to(device)
+            buf = torch.empty(counts_at + 4 * B * blocks * ch, dtype=torch.uint8, device=device)
+            L.wav_encode_channels(x.data_ptr(), meta.ctypes.data, meta.ctypes.data + 4 * B, meta_dev.data_ptr(), meta_dev.data_ptr() + 4 * B,
+                                  taps.data_ptr() if taps is not None else None, buf.data_ptr(), buf.data_ptr() + counts_at,
+                                  stride, B, Lmax, up, down, half, fmt, width, ch,
+                                  stream=torch.cuda.current_stream(device).cuda_stream, device=device)
+            host = buf.cpu().numpy()
+        per = host[counts_at:].view(np.int32).reshape(B, blocks, ch).sum(axis=1)
+        for b, i in enumerate(ids):
+            payloads[i] = host[b * stride:b * stride + k_ch[b] * fb].tobytes()
+            counts[i] = [int(c) for c in per[b]]
+    return payloads, counts

@@ -229,6 +229,24 @@ def read_any(path, sr=16000):
     return x
 
 
+def read_channels(path, sr=16000):
+    """fp32 [ch, n]: the channels of a file ``read_frames`` opens, kept apart (opt-in: ``wavdev.load(channels="each")``,
+    ``generate_wav`` of a trainer built with ``channels="each"``).  Row c is channel c's samples de-interleaved, decoded alone
+    (``decode_frames`` with ``ch == 1``) and run through ``resample``: ``read_any`` of a mono file that holds channel c's samples
+    in the same encoding, bit for bit.  No mix arithmetic touches a sample, so binary32 NaN payloads survive as they do for a
+    mono file; the single row of a mono file is ``read_any(path)``."""
+    frames, n, ch, width, rate, fmt = read_frames(path)
+    samples = frames.reshape(n, ch, width)
+    rows = []
+    for c in range(ch):
+        x = decode_frames(np.ascontiguousarray(samples[:, c]), 1, width, fmt)
+        if rate != sr:
+            with np.errstate(over="ignore", invalid="ignore"):
+                x = resample(x, rate, sr)
+        rows.append(x)
+    return np.stack(rows) if rows[0].size else np.zeros((ch, 0), dtype=np.float32)
+
+
 # ---- the way back: a waveform at 16 kHz written in its source's rate and encoding (opt-in: generate_wav(wav_out="source")) ----
 # The host oracle of csrc/wavout.hip (include/pdse.h: the wav back end; prior-diffuse_amd/wavdev.py: encode).
 _FMT_TAG = {WAV_INT: 1, WAV_FLOAT: 3}                        # what write_any writes: WAVE_FORMAT_PCM, WAVE_FORMAT_IEEE_FLOAT
@@ -265,6 +283,26 @@ def encode(x, fmt, width, ch):
     if width == 3:
         return np.ascontiguousarray(v.view(np.uint8).reshape(-1, 4)[:, :3]).tobytes(), clipped
     return v.tobytes(), clipped
+
+
+def encode_channels(rows, fmt, width):
+    """(payload, clipped_per_channel): the fp32 rows [ch, n] as interleaved little-endian frames, channel c from row c (1 .. 8
+    rows; the targets of ``encode``).  Every row goes through ``encode``'s arithmetic on its own - float64 clamp, exact scale,
+    round half to even, NaN written as 0 and counted - and the samples are then interleaved in channel order:
+    clipped_per_channel[c] is ``encode(rows[c], fmt, width, 1)[1]``, and ch equal rows give ``encode(row, fmt, width, ch)[0]``
+    byte for byte.  The host oracle of csrc/wavout.hip's channel encoder (``wavdev.encode_channels``)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2:
+        raise ValueError("rows: [ch, n], got shape %r" % (rows.shape,))
+    ch, n = rows.shape
+    _check_target(fmt, width, ch)
+    image = np.zeros((n, ch, width), dtype=np.uint8)
+    clipped = []
+    for c in range(ch):
+        payload, k = encode(rows[c], fmt, width, 1)
+        image[:, c] = np.frombuffer(payload, dtype=np.uint8).reshape(n, width)
+        clipped.append(k)
+    return image.tobytes(), clipped
 
 
 def wav_header(n_bytes, sr, fmt, width, ch):

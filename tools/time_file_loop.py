@@ -4,7 +4,8 @@ one untimed run (weights, plan, graph capture), then three timed runs; prints th
 highest run.  Only the public interface is used, so the same script times any checkout of the project:
 
     python tools/time_file_loop.py [--rates 16000 44100 48000] [--root OTHER_CHECKOUT] [--files 16] [--seconds 4] [--runs 3]
-                                   [--format s16|s24|f32|f64|ulaw] [--channels N] [--wav-out pcm16|source]
+                                   [--format s16|s24|f32|f64|ulaw] [--channels N] [--wav-out pcm16|source] [--per-channel]
+                                   [--distinct-channels]
 
 --format other than s16, or --channels above 1, writes the files with a RIFF writer of this script's own and times
 ``generate_wav`` of a trainer built with ``wav_formats="all"`` (s16 with more channels goes through the same trainer, so the
@@ -14,6 +15,12 @@ before ``wav_formats`` lacks.
 --wav-out source times the same loop of a trainer built with ``wav_out="source"``: every file is written at its source's rate,
 length, channel count and encoding, converted and encoded on the device (``wavdev.encode``), instead of 16 kHz, 16-bit, mono.
 The default passes nothing, so a checkout before ``wav_out`` is timed by the same command (profiles/wav_out_timing.txt).
+
+--per-channel times the loop of a trainer built with ``channels="each"``: every channel of a file is enhanced on its own (one exact
+ragged pass of B = channels per file) and the file is written with that many different channels (``wavdev.encode_channels``).  The
+files' channels then differ - channel c is the signal of seed 100 + i + 1000 c - so that nothing can be shared between them; without
+the flag the files are written as before, or with --distinct-channels as --per-channel writes them, so that both loops read the
+same files (profiles/wav_channels_timing.txt).
 
 Lines of several invocations (say, this commit and its parent, alternating) are collected in profiles/wav_frontend_timing.txt
 and profiles/wav_formats_timing.txt.
@@ -36,8 +43,12 @@ FORMATS = {"s16": (1, 2), "s24": (1, 3), "f32": (3, 4), "f64": (3, 8), "ulaw": (
 
 
 def write_file(path, x, rate, fmt, channels, np):
-    """x: mono float samples in [-1, 1); every channel holds them (the mix is then x again up to the encoding's rounding)."""
+    """x: mono float samples in [-1, 1); every channel holds them (the mix is then x again up to the encoding's rounding).
+    x [channels, n]: the channels' own samples."""
     tag, width = FORMATS[fmt]
+    repeat = channels
+    if np.ndim(x) == 2:
+        x, repeat = np.asarray(x).T.reshape(-1), 1            # interleaved here; nothing to repeat
     x = np.clip(np.asarray(x, dtype=np.float64), -1.0, 1.0 - 2.0 ** -15)
     if fmt == "s16":
         data = np.round(x * 32768.0).astype("<i2")
@@ -50,7 +61,7 @@ def write_file(path, x, rate, fmt, channels, np):
         data = (~(np.where(v < 0, 0x80, 0) | (seg << 4) | ((mag >> (seg + 3)) & 15)) & 0xFF).astype(np.uint8)
     else:
         data = x.astype("<f4" if fmt == "f32" else "<f8")
-    data = np.repeat(data.reshape(x.size, -1), channels, axis=0).tobytes()
+    data = np.repeat(data.reshape(x.size, -1), repeat, axis=0).tobytes()
     head = struct.pack("<HHIIHH", tag, channels, rate, rate * channels * width, channels * width, 8 * width)
     body = b"WAVEfmt " + struct.pack("<I", 16) + head + b"data" + struct.pack("<I", len(data)) + data + b"\0" * (len(data) & 1)
     with open(path, "wb") as f:
@@ -68,6 +79,8 @@ def main():
     ap.add_argument("--format", choices=sorted(FORMATS), default="s16")
     ap.add_argument("--channels", type=int, default=1)
     ap.add_argument("--wav-out", choices=("pcm16", "source"), default="pcm16")
+    ap.add_argument("--per-channel", action="store_true")
+    ap.add_argument("--distinct-channels", action="store_true", help="the files --per-channel writes, for the loop without it")
     args = ap.parse_args()
     root = os.path.abspath(args.root)
     sys.path.insert(0, root)
@@ -85,18 +98,22 @@ def main():
     label = args.label or os.path.basename(root)
     work = tempfile.mkdtemp(prefix="file_loop_")
     try:
-        all_wav = args.format != "s16" or args.channels > 1
+        all_wav = args.format != "s16" or args.channels > 1 or args.per_channel
         tr = trainer.ComplexDDPMTrainer(
             ns(retrain=False, joint=True, draw=False, sigma=False, checkpoint="x", generated_wav=os.path.join(work, "out")),
             ns(model=ns(name="GCRN"), train=ns(fft_num=320, win_size=320, win_shift=160, feat_type="sqrt")),
             device="cuda:0", prior_state_dict=synth.make_state_dict("GCRN"), ddpm_state_dict=synth.make_state_dict("DiffUNet1"),
-            **({"wav_formats": "all"} if all_wav else {}), **({"wav_out": "source"} if args.wav_out == "source" else {}))
+            **({"wav_formats": "all"} if all_wav else {}), **({"wav_out": "source"} if args.wav_out == "source" else {}),
+            **({"channels": "each"} if args.per_channel else {}))
         for rate in args.rates:
             src = os.path.join(work, "in_%d" % rate)
             os.makedirs(src)
             n = int(round(args.seconds * rate))
             for i in range(args.files):
-                if all_wav:
+                if args.per_channel or args.distinct_channels:
+                    x = np.stack([np.asarray(synth.speechlike(1, n, 100 + i + 1000 * c)[0]) for c in range(args.channels)])
+                    write_file(os.path.join(src, "f%02d.wav" % i), x, rate, args.format, args.channels, np)
+                elif all_wav:
                     write_file(os.path.join(src, "f%02d.wav" % i), synth.speechlike(1, n, 100 + i)[0], rate, args.format, args.channels, np)
                 else:
                     wavio.write_wav(os.path.join(src, "f%02d.wav" % i), synth.speechlike(1, n, 100 + i)[0], rate)
@@ -111,11 +128,12 @@ def main():
                 torch.cuda.synchronize()
                 ms.append(1e3 * (time.perf_counter() - t0) / args.files)
             res = {"label": label, "rate": rate, "format": args.format, "channels": args.channels,
-                   "loop": "wav_formats=all" if all_wav else "default", "wav_out": args.wav_out, "files": args.files, "seconds_per_file": args.seconds,
+                   "loop": "wav_formats=all" if all_wav else "default", "wav_out": args.wav_out,
+                   "channel_mode": "each" if args.per_channel else "mix", "files": args.files, "seconds_per_file": args.seconds,
                    "ms_per_file_median": round(statistics.median(ms), 3), "ms_per_file_min": round(min(ms), 3),
                    "ms_per_file_max": round(max(ms), 3), "runs": args.runs}
-            print("%-10s %-4s x%d %6d Hz -> %-6s: %8.3f ms per file (%.3f .. %.3f over %d runs of %d files of %.1f s)" % (
-                label, args.format, args.channels, rate, args.wav_out, res["ms_per_file_median"], res["ms_per_file_min"], res["ms_per_file_max"], args.runs, args.files,
+            print("%-10s %-4s x%d %6d Hz -> %-6s %-4s: %8.3f ms per file (%.3f .. %.3f over %d runs of %d files of %.1f s)" % (
+                label, args.format, args.channels, rate, args.wav_out, res["channel_mode"], res["ms_per_file_median"], res["ms_per_file_min"], res["ms_per_file_max"], args.runs, args.files,
                 args.seconds), flush=True)
             print("RESULT " + json.dumps(res), flush=True)
     finally:
