@@ -1137,6 +1137,61 @@ int pdse_wav_encode_channels(const float* x,              /* device [B ch][Lmax]
                              int64_t stride, int32_t B, int32_t Lmax, int32_t up, int32_t down, int32_t half, int32_t fmt,
                              int32_t width, int32_t ch, pdse_stream_t s);
 
+/* Validation epoch (csrc/valid.hip, additive within ABI 9): the pair front end and the masked losses of the reference's validation
+ * loop (trainer/complex_ddpm_trainer.py:399-580).  Plain arguments like the wav back end: no descriptor, no operator kind, not
+ * recordable in a plan; everything is validated before the launch and without a device.
+ *
+ * Pair front end (Collate.collate_fn, utils/dataset.py:45-58): B zero-padded utterance pairs noisy[B][L], clean[B][L] with lens[b]
+ * own samples each.  c[b] = sqrt(sum noisy[b][i]^2 / lens[b]) over the noisy row's own samples; both rows are written divided by
+ * that one c[b] and reflect-padded by pad samples on each side ([B][L + 2 pad]) for the centred STFT.  The arithmetic and the
+ * summation order are those of the wavprep operator with a lens table, and reflect_own selects the same two padding conventions
+ * as pdse_wavprep_desc.reflect_own: noisy_pad and c are bit for bit what pdse_wavprep_f32 writes for the same wav, lens, pad and
+ * reflect_own with normalize set; clean_pad is the same arithmetic on the clean row with the noisy row's c.  One workgroup per
+ * utterance. */
+int pdse_pair_prep(const float* noisy,      /* device [B][L] */
+                   const float* clean,      /* device [B][L] */
+                   const int32_t* lens,     /* device [B] */
+                   float* noisy_pad,        /* device [B][L + 2 pad] */
+                   float* clean_pad,        /* device [B][L + 2 pad] */
+                   float* c,                /* device [B] */
+                   int32_t B, int32_t L, int32_t pad, int32_t reflect_own, pdse_stream_t s);
+
+/* Masked losses (utils/loss.py: com_mse_loss :34-44, mag_mse_loss :10-19, com_mag_mse_loss :59-71) of esti, label [B][2][T][F] fp32
+ * over the frames t < frames[b] of every utterance:
+ *   complex term    per element: d = esti - label, then d d, both rounded to fp32;
+ *   magnitude term  per (b, t, f): m = sqrt(re re + im im) of esti and of label, every operation rounded to fp32 (IEEE square
+ *                   root: the fp32 norm over the channel axis), then dm = m_e - m_l and dm dm in fp32.
+ * The fp32 terms are added in double, in a fixed order: a thread adds its own quads of four consecutive (t, f) positions in
+ * ascending order (per position re, im, then the magnitude term), a workgroup adds its threads through a shuffle tree,
+ * PDSE_SPECLOSS_BLOCKS workgroups per utterance leave partials, and one workgroup adds an utterance's partials in index order
+ * and the utterances in batch order.  No atomics: a numerator depends on the utterance's data, frames[b] and F alone.
+ *   per_utt[b][0], per_utt[b][1]  the complex and the magnitude numerator of utterance b (double);
+ *   loss[0] = com_mse = sum_b per_utt[b][0] / (2 F sum_b frames[b]),  loss[1] = mag_mse = sum_b per_utt[b][1] / (F sum_b frames[b]),
+ *   loss[2] = com_mag_mse = (com_mse + mag_mse) / 2, the three divided in double and rounded to fp32 once.
+ * frames_host is the host copy of frames, read by the call itself: 0 <= frames[b] <= T, and a batch whose frames sum to 0 is an
+ * argument error (no launch, no division).  partial: scratch of B * PDSE_SPECLOSS_BLOCKS * 2 doubles.  B <= 65535. */
+#define PDSE_SPECLOSS_BLOCKS 32
+int pdse_spec_losses(const float* esti,            /* device [B][2][T][F] */
+                     const float* label,           /* device [B][2][T][F] */
+                     const int32_t* frames_host,   /* host [B] */
+                     const int32_t* frames,        /* device [B] */
+                     double* partial,              /* device [B][PDSE_SPECLOSS_BLOCKS][2] */
+                     double* per_utt,              /* device [B][2] */
+                     float* loss,                  /* device [3] */
+                     int32_t B, int32_t T, int32_t F, pdse_stream_t s);
+
+/* Frames for the waveforms the quality measures of a validation pass compare (csrc/valid.hip, additive within ABI 9; plain
+ * arguments): the compressed spectrogram spec [B][2][T][161] is decompressed - |X| (re, im), the magnitude squared with the phase
+ * kept - and taken through the windowed inverse real DFT of n_fft = 320 in double, one sum of 322 products in k order per
+ * sample, rounded to fp32 once: frames[b][r][t], the layout the overlap-add operator reads.  basis: 322 x 320 doubles, row
+ * k = ri * 161 + f, the inverse-DFT coefficient of bin f times the periodic Hann window over n_fft.  The sampling path's own
+ * back end (fp32 decompression and GEMM) is 2e-6 from a double transform; a score of 20 - 27 dB over a few frames shows that
+ * in its fifth decimal, so the scored waveforms do not go through it.  F must be 161; B <= 65535. */
+int pdse_spec_frames(const float* spec,     /* device [B][2][T][161] */
+                     const double* basis,   /* device [322][320] */
+                     float* frames,         /* device [B][320][T] */
+                     int32_t B, int32_t T, int32_t F, pdse_stream_t s);
+
 /* plans: a recorded operator sequence replayed by one call (and capturable in a hipGraph) */
 typedef struct pdse_plan pdse_plan;
 int pdse_plan_create(pdse_plan** out);

@@ -19,6 +19,7 @@ EW_DIV, EW_UPDATE, EW_UPDATE_FINAL, EW_COPY, EW_ADD_MUL = 0, 1, 2, 3, 4
  OP_ROWLN, OP_CHLN, OP_ATTN, OP_GRU, OP_GNCOMB, OP_AHAM, OP_QSAMPLE, OP_TRANSPOSE, OP_TCM, OP_CRM, OP_GCRNLAST,
  OP_MASKLOSS, OP_GLSTM, OP_TCM2, OP_BGLU, OP_PLANES, OP_GLSTMP, OP_TCM2S, OP_DENSE, OP_ROWLNB, OP_METRICS, OP_RESAMPLE, OP_RANGE) = range(32)
 MASKLOSS_BLOCKS = 32
+SPECLOSS_BLOCKS = 32      # PDSE_SPECLOSS_BLOCKS: workgroups per utterance of pdse_spec_losses (partial [B][32][2] doubles)
 
 _fp = C.c_void_p  # device pointers travel as integers
 _i32, _i64, _f32 = C.c_int32, C.c_int64, C.c_float
@@ -354,7 +355,7 @@ EXPORTS = [
     "pdse_plan_run_range",
     "pdse_plan_build_graph", "pdse_plan_launch_graph", "pdse_plan_time_ops", "pdse_plan_time_tag",
     "pdse_plan_destroy", "pdse_plan_load", "pdse_plan_region", "pdse_prior_forward", "pdse_eps_forward", "pdse_enhance",
-    "pdse_wav_encode", "pdse_wav_encode_channels",
+    "pdse_wav_encode", "pdse_wav_encode_channels", "pdse_pair_prep", "pdse_spec_losses", "pdse_spec_frames",
 ] + [name for _, _, name in OPS]
 
 
@@ -414,6 +415,12 @@ def load():
     lib.pdse_wav_encode.restype = C.c_int
     lib.pdse_wav_encode_channels.argtypes = lib.pdse_wav_encode.argtypes
     lib.pdse_wav_encode_channels.restype = C.c_int
+    lib.pdse_pair_prep.argtypes = [_fp] * 6 + [_i32] * 4 + [C.c_void_p]
+    lib.pdse_pair_prep.restype = C.c_int
+    lib.pdse_spec_losses.argtypes = [_fp] * 7 + [_i32] * 3 + [C.c_void_p]
+    lib.pdse_spec_losses.restype = C.c_int
+    lib.pdse_spec_frames.argtypes = [_fp] * 3 + [_i32] * 3 + [C.c_void_p]
+    lib.pdse_spec_frames.restype = C.c_int
     if lib.pdse_abi_version() != ABI_VERSION:
         raise PdseError("libpdse.so ABI %d != binding ABI %d" % (lib.pdse_abi_version(), ABI_VERSION))
     for kind, typ in DESC_TYPES.items():
@@ -460,6 +467,37 @@ def wav_encode_channels(*args, **kw):
     """pdse_wav_encode_channels (include/pdse.h: the channel encoder): ``wav_encode``'s arguments with x [B ch][Lmax] and
     clipped [B][blocks][ch]."""
     wav_encode(*args, entry="pdse_wav_encode_channels", **kw)
+
+
+def _on(device):
+    if device is None:
+        return contextlib.nullcontext()
+    import torch
+
+    return torch.cuda.device(device)
+
+
+def pair_prep(noisy, clean, lens, noisy_pad, clean_pad, c, B, L, pad=160, reflect_own=0, stream=0, device=None):
+    """pdse_pair_prep (include/pdse.h: the pair front end of the validation epoch, csrc/valid.hip): pointers as integers."""
+    lib = load()
+    with _on(device):
+        check(lib.pdse_pair_prep(noisy, clean, lens, noisy_pad, clean_pad, c, int(B), int(L), int(pad), int(reflect_own),
+                                 C.c_void_p(stream)), "pdse_pair_prep")
+
+
+def spec_losses(esti, label, frames_host, frames, partial, per_utt, loss, B, T, F, stream=0, device=None):
+    """pdse_spec_losses (include/pdse.h: the masked losses of the validation epoch, csrc/valid.hip): pointers as integers."""
+    lib = load()
+    with _on(device):
+        check(lib.pdse_spec_losses(esti, label, frames_host, frames, partial, per_utt, loss, int(B), int(T), int(F),
+                                   C.c_void_p(stream)), "pdse_spec_losses")
+
+
+def spec_frames(spec, basis, frames, B, T, F, stream=0, device=None):
+    """pdse_spec_frames (include/pdse.h: decompression and inverse DFT in double for the scored waveforms, csrc/valid.hip)."""
+    lib = load()
+    with _on(device):
+        check(lib.pdse_spec_frames(spec, basis, frames, int(B), int(T), int(F), C.c_void_p(stream)), "pdse_spec_frames")
 
 
 class Plan:

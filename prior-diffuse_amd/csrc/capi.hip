@@ -164,6 +164,21 @@ int pdse_wav_encode_channels(const float* x, const int32_t* n_in_host, const int
                            (hipStream_t)s);
 }
 
+// the validation epoch's pair front end and masked losses (csrc/valid.hip): plain arguments, outside the operator table
+int pdse_pair_prep(const float* noisy, const float* clean, const int32_t* lens, float* noisy_pad, float* clean_pad, float* c, int32_t B,
+                   int32_t L, int32_t pad, int32_t reflect_own, pdse_stream_t s) {
+  return pdse_pair_prep_launch(noisy, clean, lens, noisy_pad, clean_pad, c, B, L, pad, reflect_own, (hipStream_t)s);
+}
+
+int pdse_spec_losses(const float* esti, const float* label, const int32_t* frames_host, const int32_t* frames, double* partial,
+                     double* per_utt, float* loss, int32_t B, int32_t T, int32_t F, pdse_stream_t s) {
+  return pdse_spec_losses_launch(esti, label, frames_host, frames, partial, per_utt, loss, B, T, F, (hipStream_t)s);
+}
+
+int pdse_spec_frames(const float* spec, const double* basis, float* frames, int32_t B, int32_t T, int32_t F, pdse_stream_t s) {
+  return pdse_spec_frames_launch(spec, basis, frames, B, T, F, (hipStream_t)s);
+}
+
 int pdse_plan_create(pdse_plan** out) {
   if (!out) {
     pdse_set_error("plan_create: null out");

@@ -82,5 +82,11 @@ int pdse_wavout_launch(const float* x, const int32_t* n_in_host, const int32_t* 
 int pdse_wavch_launch(const float* x, const int32_t* n_in_host, const int32_t* n_keep_host, const int32_t* n_in, const int32_t* n_keep,
                       const double* taps, uint8_t* out, int32_t* clipped, int64_t stride, int32_t B, int32_t Lmax, int32_t up,
                       int32_t down, int32_t half, int32_t fmt, int32_t width, int32_t ch, hipStream_t s);
+// csrc/valid.hip: the pair front end and the masked losses of the validation epoch behind pdse_pair_prep / pdse_spec_losses (plain arguments too)
+int pdse_pair_prep_launch(const float* noisy, const float* clean, const int32_t* lens, float* noisy_pad, float* clean_pad, float* c,
+                          int32_t B, int32_t L, int32_t pad, int32_t reflect_own, hipStream_t s);
+int pdse_spec_losses_launch(const float* esti, const float* label, const int32_t* frames_host, const int32_t* frames, double* partial,
+                            double* per_utt, float* loss, int32_t B, int32_t T, int32_t F, hipStream_t s);
+int pdse_spec_frames_launch(const float* spec, const double* basis, float* frames, int32_t B, int32_t T, int32_t F, hipStream_t s);
 int pdse_range_validate(const pdse_range_desc* d);               /* reads the row table back and checks it (direct launches, plan_add) */
 #endif

@@ -1,7 +1,11 @@
-"""CLI mirror of the reference's ``main.py`` for the ``--generate`` path
+"""CLI mirror of the reference's ``main.py`` for the ``--generate`` and ``--eval`` paths
 (main.py:20-101): same flags, same derived directories, YAML config -> Namespace.
 
     python -m prior_diffuse_amd.main --retrain --assets A --sigma --joint --generate
+    python -m prior_diffuse_amd.main --retrain --assets A --joint --eval --data NOISY --clean CLEAN
+
+``--eval`` runs one validation epoch (``ComplexDDPMTrainer.validate``), logs its line and writes the dictionary to
+``<assets>/log/<doc>/eval.json``; with ``--generate`` the generation runs, as the reference tests ``generate`` first (:97).
 """
 import argparse
 import logging
@@ -31,6 +35,8 @@ def parse_args_and_config(argv=None):
     for flag in ("generate", "retrain", "joint", "eval", "sigma", "noisy", "draw"):
         p.add_argument("--" + flag, action="store_true")
     p.add_argument("--data", type=str, default="data/noisy_testset_wav", help="directory of noisy wavs")
+    p.add_argument("--clean", type=str, default="data/clean_testset_wav",
+                   help="(not a flag of the reference) --eval: directory of the clean partners of --data, matched by file name")
     p.add_argument("--bf16", action="store_true",
                    help="(not a flag of the reference) the opt-in reduced-precision mode: plain bf16 operands and bf16 block-boundary "
                         "tensors in the eps-net's blocks and the priors' GEMM-shaped convolutions, tolerance 3e-2 rel-L2 against the fp32 path; default: fp32-equivalent arithmetic")
@@ -65,6 +71,11 @@ def parse_args_and_config(argv=None):
                         "with that many different channels - at 16 kHz, 16-bit, or with --keep-format in the source's rate and "
                         "encoding; mono files are untouched; default: the network enhances the mono mix")
     args = p.parse_args(argv)
+    import sys
+
+    given = sys.argv[1:] if argv is None else list(argv)
+    # --eval: --batch is the validation batch size where it was given; else config.train.batch_size
+    args.eval_batch = args.batch if any(a == "--batch" or a.startswith("--batch=") for a in given) else None
     args.log = os.path.join(args.assets, "log", args.doc)
     args.checkpoint = os.path.join(args.assets, "checkpoint", args.doc)
     args.generated_wav = os.path.join(args.assets, "wav", args.doc)
@@ -93,7 +104,12 @@ def main(argv=None):
     trainer = ComplexDDPMTrainer(args, config)
     if args.generate:
         return trainer.generate_wav(load_pre_train=True, data_path=args.data, batch=args.batch, inflight=args.inflight)
-    trainer.train_ddpm()
+    res = trainer.train_ddpm()          # --eval: one validation epoch (raises NotImplementedError otherwise: training)
+    import json
+
+    with open(os.path.join(args.log, "eval.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    return res
 
 
 if __name__ == "__main__":

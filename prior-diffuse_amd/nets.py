@@ -1373,14 +1373,17 @@ class StftPlan(PlanBase):
         self.normalize = normalize
         self.reflect_own = bool(reflect_own)
 
-    def build(self, feat=None):
+    def build(self, feat=None, prep=True):
+        """prep False: ``xpad`` is filled by the caller (the label leg of a validation pass: pdse_pair_prep, which a plan cannot
+        record) and the plan starts at the framing GEMM."""
         B, L_, T = self.B, self.L, self.T
         feat = self.feat if feat is None else feat
-        d = L.WavprepDesc()
-        d.wav, d.xpad, d.c, d.lens = self.wav.data_ptr(), self.xpad.data_ptr(), self.c.data_ptr(), self.lens.data_ptr()
-        d.B, d.L, d.pad, d.normalize = B, L_, 160, 1 if self.normalize else 0
-        d.reflect_own = 1 if self.reflect_own else 0
-        self.add(d, TAG_SIGNAL)
+        if prep:
+            d = L.WavprepDesc()
+            d.wav, d.xpad, d.c, d.lens = self.wav.data_ptr(), self.xpad.data_ptr(), self.c.data_ptr(), self.lens.data_ptr()
+            d.B, d.L, d.pad, d.normalize = B, L_, 160, 1 if self.normalize else 0
+            d.reflect_own = 1 if self.reflect_own else 0
+            self.add(d, TAG_SIGNAL)
         Lp = L_ + 320
         # a frame's 320 samples as 320 "channels" of stride 1 at position 160 j: one GEMM [B T, 320] x [320, 322] (as 320
         # taps of one channel the gather loop ran 320 tap iterations of a 1-deep contraction: 294 us at B=32, 4 s)

@@ -256,3 +256,130 @@ def com_mse_loss(esti, label, frame_list):
     d.B, d.C, d.T, d.F = B, C_, T, F_
     L.launch(d, torch.cuda.current_stream(esti.device).cuda_stream, device=esti.device)
     return out[0]
+
+
+def spec_losses(esti, label, frame_list):
+    """The three masked losses of utils/loss.py over the first ``frame_list[b]`` frames of every utterance of two fp32
+    [B,2,T,F] tensors (trainer/complex_ddpm_trainer.py:537; conf/gcrn.yml and conf/dbaiat.yml name ``com_mag_mse_loss``), in one
+    call of csrc/valid.hip (include/pdse.h: pdse_spec_losses):
+
+        com_mse      ((esti - label) * mask) ** 2).sum() / (2 F sum frames)                              :34-44
+        mag_mse      ((|esti| - |label|) * mask) ** 2).sum() / (F sum frames), |x| = torch.norm(x, dim=1)  :10-19
+        com_mag_mse  0.5 * (com_mse + mag_mse)                                                            :59-71
+
+    Returns a dict of 0-dim fp32 device tensors under those names plus ``per_utt``, float64 [B,2]: every utterance's two
+    numerators, which depend on the utterance alone (an epoch's per-frame loss is their sum over the summed denominators).
+    The element terms are the reference's fp32 terms, added in double in a fixed order.  frame_list: host integers in [0, T], not
+    all zero (ValueError).  No host synchronisation."""
+    import numpy as np
+
+    if esti.device.type != "cuda":
+        raise L.PdseError("spec_losses runs on the GPU only (no CPU fallback)")
+    if esti.dim() != 4 or esti.shape[1] != 2 or esti.shape != label.shape or esti.dtype != torch.float32 or label.dtype != torch.float32:
+        raise ValueError("esti, label: fp32 tensors of one [B,2,T,F] shape")
+    if not (esti.is_contiguous() and label.is_contiguous()) or label.device != esti.device:
+        raise ValueError("esti, label must be contiguous tensors of one device")
+    B, _, T, F_ = esti.shape
+    frames_h = np.ascontiguousarray(np.asarray(list(frame_list), dtype=np.int64).reshape(-1))
+    if frames_h.size != B or frames_h.min() < 0 or frames_h.max() > T:
+        raise ValueError("frame_list: one frame count in [0, T] per utterance")
+    if frames_h.sum() == 0:
+        raise ValueError("frame_list: no frame in the batch, the losses have no denominator")
+    frames_h = frames_h.astype(np.int32)
+    dev = esti.device
+    frames = torch.from_numpy(frames_h).to(dev)
+    partial = torch.empty(B * L.SPECLOSS_BLOCKS * 2, dtype=torch.float64, device=dev)
+    per_utt = torch.empty(B, 2, dtype=torch.float64, device=dev)
+    loss = torch.empty(3, dtype=torch.float32, device=dev)
+    L.spec_losses(esti.data_ptr(), label.data_ptr(), frames_h.ctypes.data, frames.data_ptr(), partial.data_ptr(), per_utt.data_ptr(),
+                  loss.data_ptr(), B, T, F_, torch.cuda.current_stream(dev).cuda_stream, device=dev)
+    return {"com_mse": loss[0], "mag_mse": loss[1], "com_mag_mse": loss[2], "per_utt": per_utt}
+
+
+_LABEL_PLANS = OrderedDict()     # (device, B, L, reflect_own) -> (context, plan, front end) of label_spec; a few geometries
+
+
+def label_spec(noisy, clean, lens=None, reflect_own=False):
+    """The label of a validation batch, on the device: noisy, clean fp32 [B,L] (zero-padded utterance pairs), lens the
+    utterances' own lengths (host integers; None: every utterance spans L) -> (label [B,2,T,161], c [B]).  Collate.collate_fn
+    (utils/dataset.py:45-74) scales the clean utterance by the NOISY utterance's c and takes the STFT of the padded batch; the
+    validation loop sqrt-compresses it (trainer/complex_ddpm_trainer.py:414-435).  Here: pdse_pair_prep (csrc/valid.hip), then
+    the framing GEMM and the compression of the sampling path's front end on the clean rows.  c is this package's
+    sqrt(sum x^2 / len), the divisor (the reference multiplies by its reciprocal).  reflect_own: reflect at every utterance's
+    own end, the convention of exact ragged batches.  No host synchronisation; a (B, L) records its small plan once."""
+    if noisy.device.type != "cuda":
+        raise L.PdseError("label_spec runs on the GPU only (no CPU fallback)")
+    if noisy.dim() != 2 or noisy.shape != clean.shape or noisy.dtype != torch.float32 or clean.dtype != torch.float32:
+        raise ValueError("noisy, clean: fp32 tensors of one [B,L] shape")
+    B, L_ = noisy.shape
+    dev = noisy.device
+    key = (str(dev), B, L_, bool(reflect_own))
+    hit = _LABEL_PLANS.get(key)
+    if hit is None:
+        while len(_LABEL_PLANS) >= 3:
+            _LABEL_PLANS.popitem(last=False)
+        ctx = nets.Ctx(dev)
+        st = nets.StftPlan(ctx, B, L_, reflect_own=reflect_own)
+        st.build(prep=False)
+        st.finish()
+        hit = _LABEL_PLANS[key] = (ctx, st, ctx.alloc(B, L_ + 320))
+    else:
+        _LABEL_PLANS.move_to_end(key)
+    _, st, noisy_pad = hit
+    if lens is None:
+        st.lens.fill_(L_)
+    else:
+        lens_t = torch.as_tensor(lens, dtype=torch.int32).reshape(-1)
+        if lens_t.numel() != B or int(lens_t.min()) < 161 or int(lens_t.max()) > L_:
+            raise ValueError("lens: one length in 161 .. L per utterance")
+        st.lens.copy_(lens_t)
+    noisy, clean = noisy.contiguous(), clean.contiguous()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    L.pair_prep(noisy.data_ptr(), clean.data_ptr(), st.lens.data_ptr(), noisy_pad.data_ptr(), st.xpad.data_ptr(), st.c.data_ptr(),
+                B, L_, 160, 1 if reflect_own else 0, stream, device=dev)
+    st.plan.run(stream)
+    return st.feat.clone(), st.c.clone()
+
+
+_FRAME_TABLES = {}      # device -> (basis [322, 320] float64, win2 [320] fp32) of spec_to_wav and the label leg
+
+
+def frame_tables(device):
+    """The constant tables of the scored waveforms, uploaded once per device: the double inverse-DFT basis of pdse_spec_frames
+    (row k = ri * 161 + f, window and 1 / n_fft folded in) and the squared window the overlap-add divides by."""
+    import numpy as np
+
+    from . import packing as P
+
+    key = str(torch.device(device))
+    if key not in _FRAME_TABLES:
+        k = P.istft_kmat(320)
+        basis = torch.from_numpy(np.ascontiguousarray(np.concatenate([k[0::2], k[1::2]]), dtype=np.float64)).to(device)
+        win2 = torch.from_numpy((P.hann_periodic(320) ** 2).astype(np.float32)).to(device)
+        _FRAME_TABLES[key] = (basis, win2)
+    return _FRAME_TABLES[key]
+
+
+def spec_to_wav(spec):
+    """Compressed spectrogram fp32 [B,2,T,161] -> waveforms [B, (T - 1) * 160] in the normalised domain, as the quality measures
+    compare them (utils/metrics.py:531-561: magnitude squared with the phase kept, torch.istft): pdse_spec_frames - decompression
+    and windowed inverse DFT in double, frames rounded to fp32 once (csrc/valid.hip) - then the path's overlap-add operator without
+    the rescale by c.  The waveforms of a validation pass (``SamplerPipeline(label=True)``) are made the same way.  No host
+    synchronisation."""
+    if spec.device.type != "cuda":
+        raise L.PdseError("spec_to_wav runs on the GPU only (no CPU fallback)")
+    if spec.dim() != 4 or spec.shape[1] != 2 or spec.shape[3] != nets.F0 or spec.dtype != torch.float32 or spec.shape[2] < 2:
+        raise ValueError("spec: an fp32 [B,2,T,161] tensor with T >= 2")
+    spec = spec.contiguous()
+    B, _, T, _ = spec.shape
+    dev, L_ = spec.device, (T - 1) * 160
+    basis, win2 = frame_tables(dev)
+    frames = torch.empty(B, 320, T, dtype=torch.float32, device=dev)
+    wav = torch.empty(B, L_, dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    L.spec_frames(spec.data_ptr(), basis.data_ptr(), frames.data_ptr(), B, T, nets.F0, stream, device=dev)
+    o = L.OlaDesc()
+    o.frames, o.win2, o.c, o.out = frames.data_ptr(), win2.data_ptr(), 0, wav.data_ptr()
+    o.B, o.T, o.L, o.n_fft, o.hop = B, T, L_, 320, 160
+    L.launch(o, stream, device=dev)
+    return wav

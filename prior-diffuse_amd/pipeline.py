@@ -62,7 +62,7 @@ class SamplerPipeline:
     def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, T=None, L_=None, fast_sampling=True,
                  use_sigma=False, params=default_params, with_signal=None, deltamu=False, cond="init", bank=None,
                  split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False, ragged=False,
-                 verdict=False, masked_prior=False):
+                 verdict=False, masked_prior=False, label=False):
         """deltamu: the alternative parameterisation of utils/params.py:36 — ddpm_sd is a ``Nocon`` state_dict,
         x_T = noise + X_init/11 (:947-948), eps = Nocon(x, t) (:970-971), no final ``+ X_init`` (:995).
         cond (deltamu False): what conditions DiffUNet1 — "init": X_init/11 (pirorgrad, :967-969, + X_init at the end,
@@ -122,7 +122,12 @@ class SamplerPipeline:
         length-masked forms of its four operators that reach across frames - attention and the bidirectional GRU along the
         frames, the GroupNorm statistics of the layer update and the AHAM average pool (csrc/aia.hip, csrc/gru3.hip; DESIGN.md
         4.8) - on ``frames_tab``, so that ``ragged=True`` accepts these priors with the same contract.  False (default): they
-        are refused as before; for the other priors the flag changes nothing."""
+        are refused as before; for the other priors the flag changes nothing.
+        label (needs L_): the label leg of a validation pass (``LabelLeg``, ``self.label``): ``enhance(wav, x_T, clean=...)`` then
+        also leaves on the device the clean utterances' compressed spectrogram - scaled by the noisy utterances' c, as
+        Collate.collate_fn scales them (utils/dataset.py:45-58) - and the normalised-domain waveforms utils/metrics.py's
+        compare_complex compares.  The leg is a second, small plan beside this one: False (default), and every pass without
+        ``clean``, records and runs exactly the operators of a pipeline without the flag."""
         if L_ is not None:
             T = 1 + L_ // 160
         if with_signal is None:
@@ -332,6 +337,12 @@ class SamplerPipeline:
                 range_launch(L.RANGE_NONFINITE, rows, tab=self.verdict_tab)
 
             mark("verdict", count)                                 # last launch of the plan
+        self.label = None
+        if label:
+            if not with_signal:
+                raise ValueError("the label leg needs the signal front / back end (pass L_)")
+            if self.plan is not None:
+                self.label = LabelLeg(self)
         if self.plan is not None:
             self.plan.keep(ctx.keep, ctx.bank)
         self._graph_stream = None
@@ -410,6 +421,12 @@ class SamplerPipeline:
         return tuple(int(v) & 0xffffffff for v in self._verdict_host[:, 0].tolist())
 
     @property
+    def init_spec(self):
+        """X_init of the last pass, [B,2,T,161], at the scale of the label and of ``spec``: the prior's output as it is (the
+        reverse loop runs on ``init`` = X_init / 11; the reference multiplies it back, :495)."""
+        return self.prior.out
+
+    @property
     def windowed(self):
         """True where the pass multiplies f16x2 operands: the arithmetic with an fp16 window, which a pass can leave."""
         return self.split == "f16x2" and bool(self.split_bf16) and self.dtype == "f32"
@@ -464,17 +481,27 @@ class SamplerPipeline:
             self.run("prior", "step0")
         return self.spec.clone(), self.prior.out.clone()
 
-    def enhance(self, wav, x_T, graph=False, lens=None, exact=False):
+    def enhance(self, wav, x_T, graph=False, lens=None, exact=False, clean=None):
         """wav [B,L], x_T [B,2,T,161] -> (enhanced wav [B,L], spectrogram [B,2,T,161]).
         lens: true lengths of zero-padded utterances (RMS normalisation over each utterance's own samples,
         utils/dataset.py:45-58); default: every utterance fills L.
         exact (pipelines built with ``ragged=True``, and only those): every utterance as if enhanced alone - see ``ragged`` in
         the constructor; samples behind ``lens[b]`` and frames behind ``1 + lens[b] // 160`` are zeros in both results.
-        False on a ragged pipeline: the padding takes part, as on a dense one (its tables are set to the full length)."""
+        False on a ragged pipeline: the padding takes part, as on a dense one (its tables are set to the full length).
+        clean (pipelines built with ``label=True``): the clean partners of ``wav``, [B,L], zero-padded like it.  The pass then
+        also runs the label leg and leaves its results on the device, in buffers the next pass overwrites: ``label.spec`` (the
+        label spectrogram), ``spec`` (the final one, as ever), ``init_spec`` (the prior's output at the label's scale, what the
+        reference's loop holds after ``init_audio *= self.c``) and the waveforms ``label.wav``, ``label.init_wav`` and
+        ``label.est_wav`` - label, X_init and the final spectrogram decompressed and inverted, in the normalised domain (not
+        rescaled by c).  The returned pair is what it is without ``clean``."""
         if self.stft is None:
             raise ValueError("pipeline was built without the signal front/back end (pass L_)")
         _expect(wav, self.stft.wav, "wav")
         _expect(x_T, self.xT_in, "x_T")
+        if clean is not None:
+            if self.label is None:
+                raise ValueError("clean= needs a pipeline recorded with label=True")
+            _expect(clean, self.label.clean, "clean")
         if exact:
             if not self.ragged:
                 raise ValueError("exact=True needs a pipeline recorded with ragged=True (the dense plan has no length tables)")
@@ -492,12 +519,76 @@ class SamplerPipeline:
             else:
                 self.frames_tab.fill_(self.T)
                 self.valid_tab.fill_(self.T * F0)
+        if clean is not None:
+            self.label.clean.copy_(clean)
+            self.label.prepare(self._stream())     # behind the copies of wav, clean and lens, ahead of the pass
         self.run(graph=graph)
+        if clean is not None:
+            self.label.run(self._stream())
         wav_out, spec = self.istft.wav.clone(), self.spec.clone()
         if exact:     # frames behind an utterance's own: zeros in the returned tensor (the overlap-add zeroed the samples itself)
             dead = torch.arange(self.T, device=self.device)[None, :] >= self.frames_tab[:, None]
             spec.masked_fill_(dead[:, None, :, None], 0.0)
         return wav_out, spec
+
+
+class LabelLeg:
+    """The label leg of a validation pass (``SamplerPipeline(label=True)``): what the reference's validation loop needs beside
+    the enhancement (trainer/complex_ddpm_trainer.py:408-559, utils/dataset.py:45-74, utils/metrics.py:528-566), as direct
+    calls and two small plans beside the pipeline's:
+
+        prepare   pdse_pair_prep (csrc/valid.hip; a plain-argument call, not recordable): the noisy rows' c, both rows / c,
+                  reflect-padded.  The noisy outputs go where the pipeline's own wavprep launch writes the same bits (its
+                  ``stft.xpad``, ``stft.c``); the clean rows into this leg's STFT input.
+        front     (plan) STFT GEMM + sqrt-compression of the clean rows -> ``spec`` (the label).
+        frames    pdse_spec_frames (csrc/valid.hip, plain arguments) on the label, on the prior's output and on the final
+                  spectrogram: decompression and windowed inverse DFT in double, frames rounded to fp32 once.
+        back      (plan) the overlap-add operator on the three frame tensors, without the rescale by c -> ``wav`` (label),
+                  ``init_wav``, ``est_wav``.
+
+    All waveforms are in the normalised domain, as compare_complex compares them.  They do not reuse the pipeline's own ISTFT
+    frames: its fp32 decompression and GEMM lie 2e-6 from a double transform, which a score of 20 - 27 dB over a few frames
+    shows in its fifth decimal.  On a ragged pipeline the leg uses its length tables: the clean rows reflect
+    at their own end and the overlap-adds stop at an utterance's own frames and samples in an exact pass."""
+
+    def __init__(self, pipe):
+        from . import ops
+
+        ctx, B, T, L_ = pipe.ctx, pipe.B, pipe.T, pipe.L
+        self.pipe = pipe
+        self.plan = L.Plan(pipe.device)
+        self.stft = nets.StftPlan(ctx, B, L_, plan=self.plan, split_bf16=pipe.stft.split_bf16, reflect_own=pipe.ragged)
+        self.clean, self.spec = self.stft.wav, self.stft.feat
+        self.stft.build(prep=False)
+        self.plan.keep(ctx.keep, ctx.bank)
+        self.basis, win2 = ops.frame_tables(pipe.device)
+        lens = pipe.stft.lens if pipe.ragged else None
+        self.back = nets.PlanBase(ctx, L.Plan(pipe.device))
+        self.frames, wavs = [], []
+        for _ in range(3):
+            fr, wav = ctx.alloc(B, 320, T), ctx.alloc(B, L_)
+            o = L.OlaDesc()
+            o.frames, o.win2, o.c, o.out = fr.data_ptr(), win2.data_ptr(), 0, wav.data_ptr()
+            o.B, o.T, o.L, o.n_fft, o.hop = B, T, L_, 320, 160
+            o.nframes, o.lens = nets.Ctx.ptr(pipe.frames_tab), nets.Ctx.ptr(lens)
+            self.back.add(o, nets.TAG_SIGNAL)
+            self.frames.append(fr)
+            wavs.append(wav)
+        self.wav, self.init_wav, self.est_wav = wavs
+        self.back.plan.keep(ctx.keep, win2, self.basis)
+        self.descs = self.stft.descs + self.back.descs
+
+    def prepare(self, stream):
+        p = self.pipe.stft
+        L.pair_prep(p.wav.data_ptr(), self.clean.data_ptr(), p.lens.data_ptr(), p.xpad.data_ptr(), self.stft.xpad.data_ptr(),
+                    p.c.data_ptr(), p.B, p.L, 160, 1 if p.reflect_own else 0, stream, device=self.pipe.device)
+
+    def run(self, stream):
+        pipe = self.pipe
+        self.plan.run(stream)
+        for spec, fr in zip((self.spec, pipe.prior.out, pipe.spec), self.frames):
+            L.spec_frames(spec.data_ptr(), self.basis.data_ptr(), fr.data_ptr(), pipe.B, pipe.T, F0, stream, device=pipe.device)
+        self.back.plan.run(stream)
 
 
 class ConcurrentSampler:

@@ -234,9 +234,10 @@ class ComplexDDPMTrainer(object):
         return _inference_schedule(self.params, fast_sampling)
 
     # ---- batched entry points ----------------------------------------------
-    def _key(self, B, T=None, L_=None, ragged=False):
+    def _key(self, B, T=None, L_=None, ragged=False, label=False):
         """The key of a geometry in the plan caches and in ``_range_fallback`` / ``_audit_clean``."""
-        return (B, T, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling)) + ((True,) if ragged else ())
+        return ((B, T, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling)) + ((True,) if ragged else ())
+                + (("label",) if label else ()))
 
     def _split_of(self, key, split):
         """The operand split a plan of the geometry ``key`` is built with, where ``split`` is what it was asked for."""
@@ -257,15 +258,15 @@ class ComplexDDPMTrainer(object):
         replay a plan from its hipGraph, one host call instead of ~770 launches, do so then; a length seen once is not worth
         the capture."""
         key = self._key(**geom)
-        ragged = len(key) == 6
+        ragged, label = True in key[5:], "label" in key[5:]
         build = partial(self._build, key, self._split_of(key, self.split), exclusive=self.exclusive, audit=self.audit,
-                        ragged=ragged, masked_prior=ragged and self.masked_prior)
+                        ragged=ragged, masked_prior=ragged and self.masked_prior, **({"label": True} if label else {}))
         pipe, met = self._pipes.take(key, build)
         return pipe, key, met
 
-    def _pipe(self, B, T=None, L_=None, ragged=False):
+    def _pipe(self, B, T=None, L_=None, ragged=False, label=False):
         """The recorded plan of one geometry."""
-        return self._plan(B=B, T=T, L_=L_, ragged=ragged)[0]
+        return self._plan(B=B, T=T, L_=L_, ragged=ragged, label=label)[0]
 
     def _checked(self, run, **geom):
         """``run(pipe, graph) -> result`` on the plan of a geometry, verified (``SamplerPipeline.check``: synchronises); graph:
@@ -748,7 +749,142 @@ class ComplexDDPMTrainer(object):
         if clipped:
             logging.warning("%s: %d of %d samples clipped at the %d-bit range", dst, clipped, keep, 8 * width)
 
+    # ---- the validation epoch (:399-580) -------------------------------------
+    def validate_batch(self, noisy_wavs, clean_wavs, x_T=None, exact=False, prior=True, stoi=False):
+        """One batch of the validation loop, scored on the device (:408-559).  noisy_wavs, clean_wavs: lists of 1-D
+        waveforms, pair by pair of one length.  The pass is ``enhance_batch``'s - every noisy utterance RMS-normalised over its
+        own samples, zero-padded to the longest, the padding takes part (exact=True: the exact ragged pass, every utterance as
+        if enhanced alone; the label then reflects at the utterance's own end too) - on a plan with the label leg
+        (``SamplerPipeline(label=True)``).  x_T: [B, 2, T, 161] of the padded batch; None: one draw of that shape.
+        Scored: the final spectrogram and, with ``prior``, X_init against the label spectrogram (``ops.spec_losses`` over
+        ``frame_num = len // 160 + 1`` frames), and their normalised-domain waveforms against the label's, all three the ISTFT of
+        a decompressed spectrogram cut to ``(frame_num - 1) * 160`` samples, as compare_complex cuts them
+        (``metrics.quality(..., stoi=stoi)``).
+        Returns (enhanced, scores): enhanced is ``enhance_batch(..., trim_to_frames=True)``'s list; scores holds ``frames``
+        (host list) and, under "x" and "init", device tensors: ``loss`` [3] (com_mse, mag_mse, com_mag_mse), ``per_utt`` [B, 2]
+        float64 numerators and one [B] tensor per measure.  One synchronisation: the pass's own check (``_checked``)."""
+        from . import metrics, validation as V
+
+        noisy = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in noisy_wavs]
+        clean = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in clean_wavs]
+        lens = [int(w.numel()) for w in noisy]
+        if len(clean) != len(noisy) or any(c.numel() != n for c, n in zip(clean, lens)):
+            raise ValueError("every noisy utterance needs a clean partner of its own length")
+        if min(lens) < 161:
+            raise ValueError("utterances must be longer than the reflect padding (160 samples)")
+        frames, cut = [V.frame_num(n) for n in lens], [V.trim_len(n) for n in lens]
+        if min(cut) < metrics.MIN_LEN:
+            raise ValueError("utterances must keep at least %d samples after trimming to frames" % metrics.MIN_LEN)
+        B, L_ = len(noisy), max(lens)
+        if exact:
+            ragged_args(self.prior_name, L_, masked=self.masked_prior)
+        batch = torch.zeros(B, L_, dtype=torch.float32, device=self.device)
+        cbatch = torch.zeros(B, L_, dtype=torch.float32, device=self.device)
+        for b, (w, c) in enumerate(zip(noisy, clean)):
+            batch[b, :lens[b]] = w.to(self.device)
+            cbatch[b, :lens[b]] = c.to(self.device)
+        x_T = self._x_T((B, 2, 1 + L_ // 160, 161), x_T)
+
+        def run(pipe, graph):
+            out, spec = pipe.enhance(batch, x_T, lens=lens, exact=exact, clean=cbatch)           # never replayed
+            leg, scores = pipe.label, {"frames": frames}
+            with torch.cuda.device(self.device):
+                for name, sp, wav in (("x", spec, leg.est_wav), ("init", pipe.init_spec, leg.init_wav))[:2 if prior else 1]:
+                    ls = ops.spec_losses(sp, leg.spec, frames)
+                    q = metrics.quality(leg.wav, wav, lens=cut, stoi=stoi)
+                    scores[name] = dict(q, loss=torch.stack([ls[k] for k in V.LOSSES]), per_utt=ls["per_utt"])
+            return [out[i, :cut[i]].clone() for i in range(B)], scores
+
+        return self._checked(run, B=B, L_=L_, ragged=bool(exact), label=True)
+
+    def validate(self, noisy_dir="data/noisy_testset_wav", clean_dir="data/clean_testset_wav", batch_size=None, order="sorted",
+                 drop_last=False, exact=False, prior=True, stoi=False, rng_fidelity=True, x_T=None):
+        """One validation epoch over the (noisy, clean) pairs of two directories: what ``train_ddpm`` runs after an epoch of
+        training, and all it runs under ``--eval`` (:387, :399-580).  Returns the dictionary of ``validation.aggregate``.
+
+        Pairs are matched by file name (VBCvDataset, utils/dataset.py:133-153), decoded on the device (``wavdev.load``, the
+        trainer's ``wav_formats``); a noisy file without a partner and a pair of unequal length raise ValueError naming the
+        file.  batch_size: None is ``config.train.batch_size``.  Batches are windows of the sorted names, the last one partial:
+        every file is scored, in a reproducible order.  The reference shuffles and drops the last partial batch: order=
+        "shuffled" takes one ``torch.randperm`` from the global generator, drop_last=True drops the tail.
+        Per batch (``validate_batch``): x_T is one draw of the batch's shape, followed with ``rng_fidelity`` by the reverse loop's
+        discarded draws (:448, :484); x_T: None, or a list with one [B, 2, T, 161] tensor per batch, in batch order (nothing is
+        drawn then).  The scores stay on the device until the epoch ends and come back in one copy; a batch synchronises once,
+        for its pass's own check.
+        ``loss``: the mean of the batches' com_mse - the reference's cv_loss / test_com_mse_loss; ``loss_per_frame``: summed
+        numerators over summed denominators; the same pair under ``mag_mse`` and ``com_mag_mse``; ``mean_ssnr``, ``mean_llr``,
+        ``mean_wss``, ``mean_fwsnrseg`` (``mean_stoi``, ``mean_estoi`` with ``stoi``): means of batch means; with ``prior`` all of it
+        again under "init", for X_init - what the diffusion adds over its prior; ``files``: per file its name, frames, loss
+        numerators and measures.  PESQ and the composite figures that need it stay out, as in ``metrics``."""
+        from . import validation as V
+
+        pairs = V.pair_names(noisy_dir, clean_dir)
+        if batch_size is None:
+            batch_size = self.config.train.batch_size
+        batches = V.windows(len(pairs), batch_size, order=order, drop_last=drop_last)
+        if x_T is not None and len(x_T) != len(batches):
+            raise ValueError("x_T: expected one tensor per batch (%d), got %d" % (len(batches), len(x_T)))
+        ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0
+        held = []
+        with torch.no_grad():
+            for k, idx in enumerate(batches):
+                part = [pairs[i] for i in idx]
+                nwav, nlens = wavdev.load([p for p, _ in part], self.device, 16000, formats=self.wav_formats)
+                cwav, clens = wavdev.load([c for _, c in part], self.device, 16000, formats=self.wav_formats)
+                V.check_lengths(part, nlens, clens)
+                shape = (len(idx), 2, 1 + max(int(n) for n in nlens) // 160, 161)
+                if x_T is None:
+                    draw = self._x_T(shape, None)                                  # :448 randn_like(init_audio)
+                    for _ in range(ndiscard):
+                        torch.randn(*shape, device=self.device, dtype=torch.float32)   # :484 randn_like(audio), scaled by 0
+                else:
+                    draw = x_T[k]
+                _, scores = self.validate_batch([nwav[j, :nlens[j]] for j in range(len(idx))],
+                                                [cwav[j, :clens[j]] for j in range(len(idx))], x_T=draw, exact=exact, prior=prior,
+                                                stoi=stoi)
+                held.append((idx, scores))
+        return self._collect_validation(held, [os.path.basename(p) for p, _ in pairs], prior, stoi)
+
+    def _collect_validation(self, held, names, prior, stoi):
+        """The epoch's scores in one copy to the host, then ``validation.aggregate``."""
+        from . import validation as V
+
+        measures = V.MEASURES + (V.STOI_MEASURES if stoi else ())
+        sections = ("x", "init") if prior else ("x",)
+        flat = [t.double().flatten() for _, sc in held for s in sections
+                for t in [sc[s]["loss"], sc[s]["per_utt"]] + [sc[s][m] for m in measures]]
+        host = torch.cat(flat).cpu().numpy() if flat else None
+        batches, at = [], 0
+        for idx, sc in held:
+            B = len(idx)
+            row = {"names": idx, "frames": sc["frames"]}
+            for s in sections:
+                d = {"loss": host[at:at + 3], "per_utt": host[at + 3:at + 3 + 2 * B].reshape(B, 2)}
+                at += 3 + 2 * B
+                for m in measures:
+                    d[m] = host[at:at + B]
+                    at += B
+                row[s] = d
+            batches.append(row)
+        return V.aggregate(batches, names, F=161, prior=prior, stoi=stoi)
+
     def train_ddpm(self):
+        """With ``args.eval``: one validation epoch (``validate`` over ``args.data`` / ``args.clean``, ``--batch`` as the batch
+        size where the CLI was given one), logged in one line, and its dictionary returned - the reference exits there
+        (:579-580).  Without it: training, which this package does not implement."""
+        if not getattr(self.args, "eval", False):
+            raise NotImplementedError("training is outside the sampling path this package implements (SURVEY.md §8)")
+        from . import validation as V
+
+        kw = {}
+        for arg, name in (("data", "noisy_dir"), ("clean", "clean_dir"), ("eval_batch", "batch_size")):
+            if getattr(self.args, arg, None) is not None:
+                kw[name] = getattr(self.args, arg)
+        res = self.validate(**kw)
+        logging.info(V.log_line(res))
+        return res
+
+    def _no_training(self, *a, **kw):
         raise NotImplementedError("training is outside the sampling path this package implements (SURVEY.md §8)")
 
-    train = train_step = draw_audio = train_ddpm
+    train = train_step = draw_audio = _no_training
