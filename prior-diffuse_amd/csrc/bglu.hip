@@ -43,64 +43,7 @@ __device__ unsigned long long g_bglu_slots[97];   // BGLU_SLOTSTAMP: shader cycl
 constexpr int popc(int m) { return m ? (m & 1) + popc(m >> 1) : 0; }
 constexpr int rank_of(int m, int tap) { return popc(m & ((1 << tap) - 1)); }
 
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l,
-                                   16, 0, 0);
-}
-
-// acc += A B: A = NP fragment planes at w[0], w[64], .. (this lane's entry), B = NP planes of the activation
-template <int NP>
-__device__ __forceinline__ f32x16 mm(const uint4* w, const uint4 (&b)[NP], f32x16 acc) {
-  if constexpr (NP == 3) {
-    const uint4 a1 = w[0], a2 = w[64], a3 = w[128];
-    acc = mfma_bf16(a1, b[2], acc);   // smallest terms first
-    acc = mfma_bf16(a3, b[0], acc);
-    acc = mfma_bf16(a2, b[1], acc);
-    acc = mfma_bf16(a1, b[1], acc);
-    acc = mfma_bf16(a2, b[0], acc);
-    acc = mfma_bf16(a1, b[0], acc);
-  } else if constexpr (NP == 2) {   // f16x2: a2 b1, a1 b2, a1 b1
-    const uint4 a1 = w[0], a2 = w[64];
-    acc = mfma_f16(a2, b[0], acc);
-    acc = mfma_f16(a1, b[1], acc);
-    acc = mfma_f16(a1, b[0], acc);
-  } else {
-    acc = mfma_bf16(w[0], b[0], acc);
-  }
-  return acc;
-}
-
-// the same with the A fragments already in registers (read from LDS one slot ahead)
-template <int NP>
-__device__ __forceinline__ f32x16 mmf(const uint4 (&a)[NP], const uint4 (&b)[NP], f32x16 acc) {
-  if constexpr (NP == 3) {
-    acc = mfma_bf16(a[0], b[2], acc);
-    acc = mfma_bf16(a[2], b[0], acc);
-    acc = mfma_bf16(a[1], b[1], acc);
-    acc = mfma_bf16(a[0], b[1], acc);
-    acc = mfma_bf16(a[1], b[0], acc);
-    acc = mfma_bf16(a[0], b[0], acc);
-  } else if constexpr (NP == 2) {
-    acc = mfma_f16(a[1], b[0], acc);
-    acc = mfma_f16(a[0], b[1], acc);
-    acc = mfma_f16(a[0], b[0], acc);
-  } else {
-    acc = mfma_bf16(a[0], b[0], acc);
-  }
-  return acc;
-}
-
-// round-to-nearest-even bf16 of two floats, packed (hipcc: v_cvt_pk_bf16_f32)
-__device__ __forceinline__ uint32_t pack_bf16(const float a, const float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  union { bf16x2 h; uint32_t u; } c;
-  c.h = __builtin_convertvector(v, bf16x2);
-  return c.u;
-}
-
-// sc: the power of two that takes the values to the plane exponent (NP == 2 only; gconv_common.h: split8h)
+// planes.h: split_planes behind this file's timing ablation
 template <int NP>
 __device__ __forceinline__ void split8p(const float (&x)[8], uint4 (&p)[NP], const float sc = 1.0f) {
 #if defined(BGLU_DIAG) && defined(BGLU_NO_SPLIT)   // timing ablation: no split arithmetic (results wrong)
@@ -111,32 +54,7 @@ __device__ __forceinline__ void split8p(const float (&x)[8], uint4 (&p)[NP], con
   }
   return;
 #endif
-  if constexpr (NP == 3) {
-    split8(x, p[0], p[1], p[2]);
-  } else if constexpr (NP == 2) {
-    split8h(x, sc, p[0], p[1]);
-  } else {
-    p[0] = make_uint4(pack_bf16(x[0], x[1]), pack_bf16(x[2], x[3]), pack_bf16(x[4], x[5]), pack_bf16(x[6], x[7]));
-  }
-}
-
-// a 32-channel accumulator tile as the B operand of the next contraction: two K blocks of 8 registers
-template <int NP>
-__device__ __forceinline__ void split16p(const f32x16& X, uint4 (&p)[2][NP], const float sc = 1.0f) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = X[8 * s + j];
-    split8p<NP>(x, p[s], sc);
-  }
-}
-
-template <int NP>
-__device__ __forceinline__ f32x16 chain(const uint4* w, const uint4 (&p)[2][NP], f32x16 acc) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s) acc = mm<NP>(w + s * NP * 64, p[s], acc);
-  return acc;
+  split_planes<NP>(x, p, sc);
 }
 
 __device__ __forceinline__ float sigm2(const float m) {   // sigmoid of a pre-activation that is already scaled by -log2 e
@@ -430,7 +348,7 @@ __global__ __launch_bounds__(512, 2) void bglu_kernel(const pdse_bglu_desc d) {
 #if defined(BGLU_DIAG) && defined(BGLU_NO_MM)   // timing ablation: no matrix instructions in the loop (results wrong)
 #define MM(buf, acc_, bp_) acc_[0] += __uint_as_float(fr[buf][0].x ^ bp_[0].x)
 #else
-#define MM(buf, acc_, bp_) acc_ = mmf<NP>(fr[buf], bp_, acc_)
+#define MM(buf, acc_, bp_) acc_ = plane_mma<NP>(fr[buf], bp_, acc_)
 #endif
 #define GL(tap, q) (img + CF::o_gL + ((tap) * 2 + (q)) * BS + lane)
 #define GR(tap, q) (img + CF::o_gR + ((tap) * 2 + (q)) * BS + lane)
@@ -487,7 +405,7 @@ __global__ __launch_bounds__(512, 2) void bglu_kernel(const pdse_bglu_desc d) {
       store_planes(S.zp, pc.valid, pc.t, pc.j);                                                        \
       if (d.nx_row0) { /* uniform: the explicit pad frame of the next encoder stage = the folded bias */ \
         uint4 bp_[2][NP];                                                                              \
-        split16p<NP>(ld16(fop + F_NXB + 4 * h), bp_, s_NX);                                            \
+        split_tile<NP>(ld16(fop + F_NXB + 4 * h), bp_, s_NX);                                            \
         store_planes(bp_, pc.valid && pc.t == 0, -1, pc.j);                                            \
       }                                                                                                \
     }                                                                                                  \
@@ -745,7 +663,7 @@ __global__ __launch_bounds__(256) void planes_conv_kernel(const pdse_planes_desc
   }
   if (!live) return;
   uint4 p[2][NP];
-  split16p<NP>(acc, p, NP == 2 ? pow2i(PDSE_F16_ACT_EXP) : 1.0f);
+  split_tile<NP>(acc, p, NP == 2 ? pow2i(PDSE_F16_ACT_EXP) : 1.0f);
   uint4* const base = reinterpret_cast<uint4*>((di ? d.hp1 : d.hp) + (int64_t)b * d.hp_sb) + ((int64_t)(t + d.hp_t0) * 4 + h) * (NP * d.hp_Fp) + f + d.hp_f0;
 #pragma unroll
   for (int q = 0; q < 2; ++q)

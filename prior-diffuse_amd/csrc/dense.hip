@@ -58,10 +58,6 @@ template <int OFF>
 __device__ __forceinline__ void dn_lds16(const unsigned addr, dn_u32x4& v) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(v) : "v"(addr), "i"(OFF) : "memory");
 }
-__device__ __forceinline__ void dn_glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l,
-                                   16, 0, 0);
-}
 __device__ __forceinline__ uint4 dn_u4(const dn_u32x4& a) { return make_uint4(a[0], a[1], a[2], a[3]); }
 
 template <int NP>
@@ -91,40 +87,17 @@ __device__ __forceinline__ void dn_wait(dn_ops<NP>& o) {
       asm volatile("" : "+v"(o.b[i][p]));
     }
 }
-// 4 accumulators (position tile k, channel tile m); the six products smallest first, the accumulators interleaved so that
-// dependent MFMAs are three instructions apart
-__device__ __forceinline__ void dn_mm(const dn_ops<3>& o, f32x16 (&acc)[2][2]) {
-  constexpr int pa[6] = {0, 2, 1, 0, 1, 0}, pb[6] = {2, 0, 1, 1, 0, 0};
+// 4 accumulators (position tile k, channel tile m); the products in the order of planes.h: plane_terms, the accumulators
+// interleaved so that dependent MFMAs are three instructions apart
+template <int NP>
+__device__ __forceinline__ void dn_mm(const dn_ops<NP>& o, f32x16 (&acc)[2][2]) {
+  using T = plane_terms<NP>;
 #pragma unroll
-  for (int q = 0; q < 6; ++q)
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-#pragma unroll
-      for (int m = 0; m < 2; ++m) acc[k][m] = mfma_bf16(dn_u4(o.a[m][pa[q]]), dn_u4(o.b[k][pb[q]]), acc[k][m]);
-}
-// f16x2 (gconv_common.h: split8h): a2 b1, a1 b2, a1 b1 on the f16 matrix cores
-__device__ __forceinline__ void dn_mm(const dn_ops<2>& o, f32x16 (&acc)[2][2]) {
-  constexpr int pa[3] = {1, 0, 0}, pb[3] = {0, 1, 0};
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
+  for (int q = 0; q < T::n; ++q)
 #pragma unroll
     for (int k = 0; k < 2; ++k)
 #pragma unroll
-      for (int m = 0; m < 2; ++m) acc[k][m] = mfma_f16(dn_u4(o.a[m][pa[q]]), dn_u4(o.b[k][pb[q]]), acc[k][m]);
-}
-__device__ __forceinline__ void dn_mm(const dn_ops<1>& o, f32x16 (&acc)[2][2]) {
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[k][m] = mfma_bf16(dn_u4(o.a[m][0]), dn_u4(o.b[k][0]), acc[k][m]);
-}
-__device__ __forceinline__ uint32_t dn_pack_bf16(const float a, const float b) {   // round to nearest even (v_cvt_pk_bf16_f32)
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  union { bf16x2 h; uint32_t u; } c;
-  c.h = __builtin_convertvector(v, bf16x2);
-  return c.u;
+      for (int m = 0; m < 2; ++m) acc[k][m] = plane_mfma<NP>(dn_u4(o.a[m][T::a[q]]), dn_u4(o.b[k][T::b[q]]), acc[k][m]);
 }
 
 struct dn_geom {   // launch geometry the host derives from the descriptor
@@ -204,7 +177,7 @@ __global__ __launch_bounds__(512, 1) void dense_kernel(const pdse_dense_desc d, 
   auto dma = [&](const int ci, const int buf) {
     const char* src = reinterpret_cast<const char*>(d.w) + (size_t)ci * ACH + lane * 16;
     unsigned char* dst = lds + 2 * BBUF + buf * ACH;
-    for (int pc = wave; pc < 6 * NP; pc += 8) dn_glds16(src + pc * 1024, dst + pc * 1024);
+    for (int pc = wave; pc < 6 * NP; pc += 8) glds16(src + pc * 1024, dst + pc * 1024);
   };
   auto landed = [&]() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -220,21 +193,10 @@ __global__ __launch_bounds__(512, 1) void dense_kernel(const pdse_dense_desc d, 
       {
         const float x[8] = {sv[r][0][0], sv[r][0][1], sv[r][0][2], sv[r][0][3], sv[r][1][0], sv[r][1][1], sv[r][1][2], sv[r][1][3]};
         unsigned char* dst = lds + buf * BBUF + wr[r];
-        if constexpr (NP == 3) {
-          uint4 p1, p2, p3;
-          split8(x, p1, p2, p3);
-          *reinterpret_cast<uint4*>(dst) = p1;
-          *reinterpret_cast<uint4*>(dst + PSTR) = p2;
-          *reinterpret_cast<uint4*>(dst + 2 * PSTR) = p3;
-        } else if constexpr (NP == 2) {
-          uint4 p1, p2;
-          split8h(x, pow2i(PDSE_F16_ACT_EXP), p1, p2);
-          *reinterpret_cast<uint4*>(dst) = p1;
-          *reinterpret_cast<uint4*>(dst + PSTR) = p2;
-        } else {
-          *reinterpret_cast<uint4*>(dst) = make_uint4(dn_pack_bf16(x[0], x[1]), dn_pack_bf16(x[2], x[3]), dn_pack_bf16(x[4], x[5]),
-                                                      dn_pack_bf16(x[6], x[7]));
-        }
+        uint4 p[NP];
+        split_planes<NP>(x, p, pow2i(PDSE_F16_ACT_EXP));
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<uint4*>(dst + pl * PSTR) = p[pl];
       }
     }
   };

@@ -44,11 +44,6 @@ constexpr int nth_bit(int m, int n) {   // position of the n-th set bit of m
 }
 
 
-// one 16-byte LDS-DMA: LDS destination = wave-uniform base + lane * 16 (the fragment areas are lane-linear)
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l,
-                                   16, 0, 0);
-}
 #define S3_FLOATS 640   // float operands behind the fragment areas (see image layout in the kernel)
 
 // fragment counts (blocks of 3 planes x 64 lanes, 192 uint4 = 3 KB each)
@@ -183,11 +178,11 @@ __global__ __launch_bounds__(1024, 4) void gconv3_in4_kernel(const pdse_gconv_de
     float x[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) x[e] = ((live >> (2 * q + (e >> 2))) & 1u) ? raw[2 * q + (e >> 2)][e & 3] : 0.f;
-    uint4 b1, b2, b3;
-    split8(x, b1, b2, b3);
+    uint4 bp[3];
+    split_planes<3>(x, bp);
     const int blk = q * 192 + lane;
-    aL = mfma6(img + blk, b1, b2, b3, aL);
-    aR = mfma6(img + L.o_gR + blk, b1, b2, b3, aR);
+    aL = plane_mma_frag<3>(img + blk, bp, aL);
+    aR = plane_mma_frag<3>(img + L.o_gR + blk, bp, aR);
   }
   biglu_nx_epilogue(d, s3_tail(img, L), aL, aR, b, t, j, pvalid, lane, h);
 }
@@ -261,16 +256,16 @@ __global__ __launch_bounds__(64 * WV, WV / 4) void gconv3_kernel(const pdse_gcon
     for (int r = 0; r < 16; ++r) aL[r] = aR[r] = aL1[r] = aR1[r] = 0.f;
   };
   auto block = [&](const float (&x)[8], const int tap, const int q) {   // one 16-channel K block of one tap
-    uint4 b1, b2, b3;
-    split8(x, b1, b2, b3);
+    uint4 bp[3];
+    split_planes<3>(x, bp);
     const int blk = (tap * 2 + q) * 192 + lane;
-    aL = mfma6(img + blk, b1, b2, b3, aL);
-    aR = mfma6(img + o_gR + blk, b1, b2, b3, aR);
+    aL = plane_mma_frag<3>(img + blk, bp, aL);
+    aR = plane_mma_frag<3>(img + o_gR + blk, bp, aR);
     if constexpr (P1MASK != 0) {
       if ((P1MASK >> tap) & 1) {   // folds after unrolling
         const int blk1 = (rank3(P1MASK, tap) * 2 + q) * 192 + lane;
-        aL1 = mfma6(img + o_gL1 + blk1, b1, b2, b3, aL1);
-        aR1 = mfma6(img + o_gR1 + blk1, b1, b2, b3, aR1);
+        aL1 = plane_mma_frag<3>(img + o_gL1 + blk1, bp, aL1);
+        aR1 = plane_mma_frag<3>(img + o_gR1 + blk1, bp, aR1);
       }
     }
   };
@@ -331,14 +326,14 @@ __global__ __launch_bounds__(64 * WV, WV / 4) void gconv3_kernel(const pdse_gcon
       __builtin_amdgcn_sched_barrier(0);
       biglu_tail_values(d, tl, aL, aR, lane, h, [&](const int m2, const int r, const float v) {
         Yt[r] = v;
-        if (r == 15) Z0 = chain_s3(tl.nxw + m2 * 384 + lane, Yt, Z0);
+        if (r == 15) Z0 = chain_tile<3>(tl.nxw + m2 * 384 + lane, Yt, Z0);
       });
 #pragma unroll
       for (int r = 0; r < 16; ++r) Z1[r] = (ab && two) ? ab[(int64_t)PDSE_KR(r) * scz + nbin] : 0.f;
       __builtin_amdgcn_sched_barrier(0);
       biglu_tail_values(d, tl, aL1, aR1, lane, h, [&](const int m2, const int r, const float v) {
         Yt[r] = v;
-        if (r == 15) Z1 = chain_s3(tl.nxw + m2 * 384 + lane, Yt, Z1);
+        if (r == 15) Z1 = chain_tile<3>(tl.nxw + m2 * 384 + lane, Yt, Z1);
       });
       const f32x16 pb = ld16(tl.nxb + 4 * h);
       if (nbin == 1 && two) {

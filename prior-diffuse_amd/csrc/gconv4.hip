@@ -32,11 +32,6 @@
 #define G4_CH 3
 #endif
 
-__device__ __forceinline__ void glds16_g4(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l,
-                                   16, 0, 0);
-}
-
 // One gathered activation: global_load_dword (scalar base + 32-bit lane offset) written as inline asm.  While an LDS-DMA is
 // in flight hipcc puts s_waitcnt vmcnt(0) in front of the first use of ANY compiler-visible load result
 // (cdna_hip_programming.md §5, "Pipelining across barriers"), which made every K block wait for the next chunk's DMA and
@@ -110,39 +105,13 @@ __device__ __forceinline__ void g4_lds_wait(u32x4 (&a)[N][NP]) {
 #pragma unroll
     for (int p = 0; p < NP; ++p) asm volatile("" : "+v"(a[i][p]));
 }
-__device__ __forceinline__ f32x16 g4_mfma6(const u32x4 (&a)[3], const uint4 (&b)[3], f32x16 acc) {
-  const uint4 a1 = make_uint4(a[0][0], a[0][1], a[0][2], a[0][3]), a2 = make_uint4(a[1][0], a[1][1], a[1][2], a[1][3]),
-              a3 = make_uint4(a[2][0], a[2][1], a[2][2], a[2][3]);
-  acc = mfma_bf16(a1, b[2], acc);
-  acc = mfma_bf16(a3, b[0], acc);
-  acc = mfma_bf16(a2, b[1], acc);
-  acc = mfma_bf16(a1, b[1], acc);
-  acc = mfma_bf16(a2, b[0], acc);
-  acc = mfma_bf16(a1, b[0], acc);
-  return acc;
-}
-__device__ __forceinline__ f32x16 g4_mfma6(const u32x4 (&a)[2], const uint4 (&b)[2], f32x16 acc) {   // a2 b1, a1 b2, a1 b1 (gconv_common.h)
-  const uint4 a1 = make_uint4(a[0][0], a[0][1], a[0][2], a[0][3]), a2 = make_uint4(a[1][0], a[1][1], a[1][2], a[1][3]);
-  acc = mfma_f16(a2, b[0], acc);
-  acc = mfma_f16(a1, b[1], acc);
-  acc = mfma_f16(a1, b[0], acc);
-  return acc;
-}
-__device__ __forceinline__ f32x16 g4_mfma6(const u32x4 (&a)[1], const uint4 (&b)[1], f32x16 acc) {
-  return mfma_bf16(make_uint4(a[0][0], a[0][1], a[0][2], a[0][3]), b[0], acc);
-}
-__device__ __forceinline__ uint32_t g4_pack_bf16(const float a, const float b) {   // round to nearest even (v_cvt_pk_bf16_f32)
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  union { bf16x2 h; uint32_t u; } c;
-  c.h = __builtin_convertvector(v, bf16x2);
-  return c.u;
-}
-__device__ __forceinline__ void g4_split(const float (&x)[8], uint4 (&b)[3]) { split8(x, b[0], b[1], b[2]); }
-__device__ __forceinline__ void g4_split(const float (&x)[8], uint4 (&b)[2]) { split8h(x, pow2i(PDSE_F16_ACT_EXP), b[0], b[1]); }
-__device__ __forceinline__ void g4_split(const float (&x)[8], uint4 (&b)[1]) {
-  b[0] = make_uint4(g4_pack_bf16(x[0], x[1]), g4_pack_bf16(x[2], x[3]), g4_pack_bf16(x[4], x[5]), g4_pack_bf16(x[6], x[7]));
+// planes.h: plane_mma on A fragments held as the register quads above
+template <int NP>
+__device__ __forceinline__ f32x16 g4_mma(const u32x4 (&a)[NP], const uint4 (&b)[NP], f32x16 acc) {
+  uint4 a4[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) a4[p] = make_uint4(a[p][0], a[p][1], a[p][2], a[p][3]);
+  return plane_mma<NP>(a4, b, acc);
 }
 
 struct g4_chunk {
@@ -204,7 +173,7 @@ __global__ __launch_bounds__(512, 2) void gconv4_kernel(const pdse_gconv_desc d)
       if (mt0 + m < mtiles) {   // tiles past Cout keep stale fragments: their accumulators are never stored
         const uint4* src = reinterpret_cast<const uint4*>(br ? d.w1 : d.w0) + ((size_t)(c.kb0 + i) * mtiles + mt0 + m) * FB +
                            part * 64 + lane;
-        glds16_g4(src, ring + ((buf * G4_CH + i) * FR + f) * FB + part * 64);
+        glds16(src, ring + ((buf * G4_CH + i) * FR + f) * FB + part * 64);
       }
     }
   };
@@ -275,15 +244,15 @@ __global__ __launch_bounds__(512, 2) void gconv4_kernel(const pdse_gconv_desc d)
           for (int e = 0; e < 8; ++e) x[e] = x[e] < 0.f ? fast_exp(x[e]) - 1.0f : x[e];
         }
         uint4 bp[NP];
-        g4_split(x, bp);         // runs under the LDS latency of the block's fragments
+        split_planes<NP>(x, bp, pow2i(PDSE_F16_ACT_EXP));         // runs under the LDS latency of the block's fragments
         g4_lds_wait(af);
         const bool more = i + 1 < c.n;   // wave-uniform
         const unsigned wn = ring_base + (unsigned)((((buf * G4_CH + i + 1) * FR) * FB + lane) * 16);
 #pragma unroll
         for (int f = 0; f < FR; ++f) {
           const int m = f % MT;
-          if (f < MT) acc0[m] = g4_mfma6(af[f], bp, acc0[m]);
-          else acc1[m] = g4_mfma6(af[f], bp, acc1[m]);
+          if (f < MT) acc0[m] = g4_mma<NP>(af[f], bp, acc0[m]);
+          else acc1[m] = g4_mma<NP>(af[f], bp, acc1[m]);
           // (i + 1 < G4_CH is a compile-time fact once the loop is unrolled: no read is emitted behind the last possible block,
           // whose destination registers would be dead - free for the compiler to re-use - while the read is still in flight)
           if (i + 1 < G4_CH && more) g4_lds_read3(wn + f * (FB * 16), af[f]);
@@ -454,7 +423,7 @@ __global__ __launch_bounds__(512, NP == 2 ? 4 : 2) void gconv4_flat_kernel(const
       for (int e = 0; e < 8; ++e) x[e] = x[e] < 0.f ? fast_exp(x[e]) - 1.0f : x[e];
     }
     uint4 bp[NP];
-    g4_split(x, bp);
+    split_planes<NP>(x, bp, pow2i(PDSE_F16_ACT_EXP));
 #pragma unroll
     for (int p = 0; p < NP; ++p) bimg[(kb * NP + p) * 64 + lane] = bp[p];
   }
@@ -483,7 +452,7 @@ __global__ __launch_bounds__(512, NP == 2 ? 4 : 2) void gconv4_flat_kernel(const
     const int kn = min(kb + 1, nkb - 1);   // (the last block is requested once more instead of a branch in the loop)
 #pragma unroll
     for (int m = 0; m < MTW; ++m) {
-      acc[m] = g4_mfma6(a[m], bp, acc[m]);
+      acc[m] = g4_mma<NP>(a[m], bp, acc[m]);
       lda(kn, m);   // the next block's fragments of this tile, into the registers its products have just read
     }
   }
@@ -608,7 +577,7 @@ __global__ __launch_bounds__(512, 2) void gconv4_pair_kernel(const pdse_gconv_de
       if (mt0 + m < mtiles) {
         const float* const w = odd ? (br ? e.w1 : e.w0) : (br ? d.w1 : d.w0);
         const uint4* src = reinterpret_cast<const uint4*>(w) + ((size_t)((odd ? kb1 : c.kb0) + i) * mtiles + mt0 + m) * FB + part * 64 + lane;
-        glds16_g4(src, ring + ((buf * G4_CH + i) * FR2 + f) * FB + part * 64);
+        glds16(src, ring + ((buf * G4_CH + i) * FR2 + f) * FB + part * 64);
       }
     }
   };
@@ -677,7 +646,7 @@ __global__ __launch_bounds__(512, 2) void gconv4_pair_kernel(const pdse_gconv_de
           for (int q = 0; q < 8; ++q) x[q] = x[q] < 0.f ? fast_exp(x[q]) - 1.0f : x[q];
         }
         uint4 bp[NP];
-        g4_split(x, bp);
+        split_planes<NP>(x, bp, pow2i(PDSE_F16_ACT_EXP));
         g4_lds_wait(af);
         const bool more = i + 1 < c.n;
         const unsigned wi = ring_base + (unsigned)((((buf * G4_CH + i) * FR2) * FB + lane) * 16);
@@ -685,14 +654,14 @@ __global__ __launch_bounds__(512, 2) void gconv4_pair_kernel(const pdse_gconv_de
         if constexpr (NF == FR2) {
 #pragma unroll
           for (int f = 0; f < FR; ++f) {
-            acc[f] = g4_mfma6(af[f], bp, acc[f]);
+            acc[f] = g4_mma<NP>(af[f], bp, acc[f]);
             g4_lds_read3(wi + (FR + f) * (FB * 16), af[f]);
           }
           g4_lds_wait(af);
         }
 #pragma unroll
         for (int f = 0; f < FR; ++f) {
-          acc[NF - FR + f] = g4_mfma6(af[f], bp, acc[NF - FR + f]);
+          acc[NF - FR + f] = g4_mma<NP>(af[f], bp, acc[NF - FR + f]);
           if (i + 1 < G4_CH && more) g4_lds_read3(wn + f * (FB * 16), af[f]);
         }
       }

@@ -7,8 +7,8 @@
 #include <stdint.h>
 
 #include "pdse.h"
+#include "planes.h"   // the split-operand arithmetic: f32x16, split_planes, plane_mma, split_tile / chain_tile
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // row of accumulator register r on lane-half h (32x32 C/D layout, cdna_hip_programming.md §3)
@@ -98,139 +98,10 @@ __device__ __forceinline__ pdse_tail tail_from_desc(const pdse_gconv_desc& d) {
                    d.bias0, d.bias1};
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Split-bf16 operands (csrc/gconv3.hip, packing.split_bf16x3): an fp32 value is the exact sum of three bf16 numbers
-// (8 + 8 + 8 significand bits, by truncation), and a product is evaluated as its six leading cross terms on the bf16
-// matrix cores with fp32 accumulation.  Fragments are 8 bf16 per lane (one uint4) per plane.
-// ---------------------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 mfma_bf16(const uint4& a, const uint4& b, const f32x16 c) {
-  union { uint4 u; bf16x8 v; } A, B;
-  A.u = a;
-  B.u = b;
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.v, B.v, c, 0, 0, 0);
-}
-
-// x[0..7] -> three planes of 8 bf16 (element j in the low / high half of dword j >> 1), x == p1 + p2 + p3 exactly.
-// 11 VALU instructions per pair of values: two masked residuals each, and one v_perm_b32 per plane picks the high
-// halves of the pair (the bf16 of a truncation IS the high half, masked or not); 15 per pair with shift / or packing.
-// Two thirds of the VALU instructions of a block kernel's tail are this function, yet a quarter fewer of them moved
-// the tail by 5 % only (22.4k -> 21.1k cycles per round, PDSE_S3_TRACE): the tail is a serial chain of split ->
-// fragment read -> six dependent MFMAs, not an issue-bound stream.
-__device__ __forceinline__ void split8(const float (&x)[8], uint4& p1, uint4& p2, uint4& p3) {
-#ifdef PDSE_ABLATE_SPLIT   // diagnostic build only (wrong results): the cost of the splits
-  p1 = make_uint4(__float_as_uint(x[0]), __float_as_uint(x[1]), __float_as_uint(x[2]), __float_as_uint(x[3]));
-  p2 = make_uint4(__float_as_uint(x[4]), __float_as_uint(x[5]), __float_as_uint(x[6]), __float_as_uint(x[7]));
-  p3 = make_uint4(p1.x ^ p2.x, p1.y ^ p2.y, p1.z ^ p2.z, p1.w ^ p2.w);
-  return;
-#endif
-  uint32_t q1[4], q2[4], q3[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = x[2 * i], b = x[2 * i + 1];
-    const float ra = a - __uint_as_float(__float_as_uint(a) & 0xffff0000u);
-    const float rb = b - __uint_as_float(__float_as_uint(b) & 0xffff0000u);
-    const float sa = ra - __uint_as_float(__float_as_uint(ra) & 0xffff0000u);
-    const float sb = rb - __uint_as_float(__float_as_uint(rb) & 0xffff0000u);
-    q1[i] = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-    q2[i] = __builtin_amdgcn_perm(__float_as_uint(rb), __float_as_uint(ra), 0x07060302u);
-    q3[i] = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
-  }
-  p1 = make_uint4(q1[0], q1[1], q1[2], q1[3]);
-  p2 = make_uint4(q2[0], q2[1], q2[2], q2[3]);
-  p3 = make_uint4(q3[0], q3[1], q3[2], q3[3]);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Split-f16 operands (round 4; include/pdse.h "f16x2"): an fp32 value x, scaled by a power of two into the fp16 range,
-// is carried as hi = RN16(x), lo = RN16(x - hi): 11 + 11 significand bits and the sign of lo, |x - hi - lo| <= 2^-23 |x|
-// (half an fp32 ulp at worst) while lo is a normal fp16, i.e. for |x| >= 2^-2 in scaled units; below that the absolute
-// error is <= 2^-25 of the scaled unit.  A product is its three leading cross terms (a1 b1, a1 b2, a2 b1; what is dropped
-// is a2 b2 <= 2^-22 |a b|) on the f16 matrix cores with fp32 accumulation: half the matrix instructions and two thirds
-// of the operand bytes of the three-plane bf16 split.  Every product of two fp16 numbers is exact in fp32.
-// Scaling is by exact powers of two: activations by 2^PDSE_F16_ACT_EXP, every weight matrix by its own 2^q chosen on
-// the host (packing.f16_wexp); accumulators therefore hold (true value) * 2^(P + q) and are re-scaled where they are
-// split for the next contraction (one multiply, merged with the split's own).
-// ---------------------------------------------------------------------------------------------------------------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 mfma_f16(const uint4& a, const uint4& b, const f32x16 c) {
-  union { uint4 u; f16x8 v; } A, B;
-  A.u = a;
-  B.u = b;
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(A.v, B.v, c, 0, 0, 0);
-}
-
-// 2^e as a float (|e| < 127)
-__device__ __forceinline__ float pow2i(const int e) { return __uint_as_float((uint32_t)(127 + e) << 23); }
-
-// Conversions are IEEE (MODE.FP16_OVFL stays 0): a scaled value beyond the fp16 range becomes an infinity in its planes and a
-// non-finite number in every sum it enters - it surfaces at the end of the path (SamplerPipeline.check) instead of passing for a value.
-
-// x[0..7] * sc -> two planes of 8 fp16 (element j in the low / high half of dword j >> 1): v_pk_mul, v_cvt_pk_f16_f32,
-// two v_cvt_f32_f16, v_pk_add, v_cvt_pk_f16_f32 per pair of values (the bf16 three-way split takes eleven)
-__device__ __forceinline__ void split8h(const float (&x)[8], const float sc, uint4& p1, uint4& p2) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  uint32_t q1[4], q2[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f32x2 t = {x[2 * i] * sc, x[2 * i + 1] * sc};
-    union { f16x2 h; uint32_t u; } hi, lo;
-    hi.h = __builtin_convertvector(t, f16x2);
-    const f32x2 r = t - __builtin_convertvector(hi.h, f32x2);
-    lo.h = __builtin_convertvector(r, f16x2);
-    q1[i] = hi.u;
-    q2[i] = lo.u;
-  }
-  p1 = make_uint4(q1[0], q1[1], q1[2], q1[3]);
-  p2 = make_uint4(q2[0], q2[1], q2[2], q2[3]);
-}
-
-// acc += A B with A given as three fragment planes at w[0], w[64], w[128] (uint4 units, this lane's entry) and B as
-// the three planes of an exact split: smallest terms first
-__device__ __forceinline__ f32x16 mfma6(const uint4* w, const uint4& b1, const uint4& b2, const uint4& b3, f32x16 acc) {
-  const uint4 a1 = w[0], a2 = w[64], a3 = w[128];
-  acc = mfma_bf16(a1, b3, acc);
-  acc = mfma_bf16(a3, b1, acc);
-  acc = mfma_bf16(a2, b2, acc);
-  acc = mfma_bf16(a1, b2, acc);
-  acc = mfma_bf16(a2, b1, acc);
-  acc = mfma_bf16(a1, b1, acc);
-  return acc;
-}
-
-// Y = W X for a 32-channel accumulator tile X used as the B operand (two k-blocks of 8 registers each);
-// w: LDS fragments [2 blocks][3 planes][64 lanes] of this output tile, already offset by the lane
-__device__ __forceinline__ f32x16 chain_s3(const uint4* w, const f32x16& X, f32x16 acc) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = X[8 * s + j];
-    uint4 b1, b2, b3;
-    split8(x, b1, b2, b3);
-    acc = mfma6(w + s * 192, b1, b2, b3, acc);
-  }
-  return acc;
-}
-
-// The same with the operand split once and used for several output tiles: p[k-block][plane]
-__device__ __forceinline__ void split16(const f32x16& X, uint4 (&p)[2][3]) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = X[8 * s + j];
-    split8(x, p[s][0], p[s][1], p[s][2]);
-  }
-}
-
-__device__ __forceinline__ f32x16 chain_s3p(const uint4* w, const uint4 (&p)[2][3], f32x16 acc) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s) acc = mfma6(w + s * 192, p[s][0], p[s][1], p[s][2], acc);
-  return acc;
+// one 16-byte LDS-DMA: LDS destination = wave-uniform base + lane * 16 (the fragment areas are lane-linear)
+__device__ __forceinline__ void glds16(const void* g, void* l) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l,
+                                   16, 0, 0);
 }
 
 // LDS image of the split-bf16 BIGLU tail (gconv3.hip fills it): fragment areas in uint4 units, then the float operands
@@ -551,8 +422,8 @@ __device__ __forceinline__ void biglu_tail_values(const pdse_gconv_desc& d, cons
   L += ld16((frame0 ? tl.bl0 : tl.bl) + 4 * h);
   R += ld16((frame0 ? tl.br0 : tl.br) + 4 * h);
   f32x16 mL = ld16(tl.blc + 4 * h), mR = ld16(tl.brc + 4 * h);    // the biases seed the accumulators
-  mL = chain_s3(tl.wlc + lane, L, mL);
-  mR = chain_s3(tl.wrc + lane, R, mR);
+  mL = chain_tile<3>(tl.wlc + lane, L, mL);
+  mR = chain_tile<3>(tl.wrc + lane, R, mR);
   f32x16 G;
 #pragma unroll
   for (int r = 0; r < 16; ++r) G[r] = L[r] * sigmoid_f(mR[r]) + R[r] * sigmoid_f(mL[r]);
@@ -566,12 +437,12 @@ __device__ __forceinline__ void biglu_tail_values(const pdse_gconv_desc& d, cons
     sink(0, 0, v > 0.f ? v : slope * v);
   } else {
     uint4 gp[2][3];     // the gate is split once for both output tiles
-    split16(G, gp);
+    split_tile<3>(G, gp);
 #pragma unroll
     for (int m2 = 0; m2 < 2; ++m2) {
       const int c0 = 32 * m2 + 4 * h;
       f32x16 O = ld16(tl.bc2 + c0);
-      O = chain_s3p(tl.wc2 + m2 * 384 + lane, gp, O);
+      O = chain_tile<3>(tl.wc2 + m2 * 384 + lane, gp, O);
       const f32x16 vs = ld16(tl.ps + c0), vt = ld16(tl.pt + c0);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -590,7 +461,7 @@ __device__ __forceinline__ f32x16 nx_tile_acc(const pdse_tail_s3& tl, const int 
     f32x16 X;
 #pragma unroll
     for (int r = 0; r < 16; ++r) X[r] = Y[m2][r];
-    Z = chain_s3(w + m2 * 384, X, Z);
+    Z = chain_tile<3>(w + m2 * 384, X, Z);
   }
   return Z;
 }
@@ -613,7 +484,7 @@ __device__ __forceinline__ nx_operand_s3 nx_operand(const pdse_tail_s3&, const f
     f32x16 X;
 #pragma unroll
     for (int r = 0; r < 16; ++r) X[r] = Y[m2][r];
-    split16(X, o.p[m2]);
+    split_tile<3>(X, o.p[m2]);
   }
   return o;
 }
@@ -623,7 +494,7 @@ __device__ __forceinline__ f32x16 nx_tile(const pdse_tail_s3& tl, const int i, c
   for (int r = 0; r < 16; ++r) Z[r] = 0.f;
   const uint4* w = tl.nxw + (size_t)i * 768 + lane;
 #pragma unroll
-  for (int m2 = 0; m2 < 2; ++m2) Z = chain_s3p(w + m2 * 384, o.p[m2], Z);
+  for (int m2 = 0; m2 < 2; ++m2) Z = chain_tile<3>(w + m2 * 384, o.p[m2], Z);
   return Z;
 }
 

@@ -1,6 +1,6 @@
 // gru3.hip — the bidirectional GRU of the DB-AIAT transformer layers (model/dbaiat.py:45,83; H = 64, d_model 32) with the
 // input projection fused (csrc/aia.hip: gru_kernel<64, true>), on the bf16 matrix cores with exact three-way operand
-// splits (gconv_common.h: six bf16 products per fp32 multiply-add, fp32 accumulation, fp32-level accuracy).
+// splits (planes.h: six bf16 products per fp32 multiply-add, fp32 accumulation, fp32-level accuracy).
 //
 // What bounded the fp32 kernel (1.57 ms per layer at B=32, T=401; 3.9 us per sequential step): six 32-row gate tiles x
 // (32 + 16) dependent v_mfma_f32_32x32x2_f32 = 18.4k matrix-pipe cycles per step on the workgroup's ONE CU (4.6k per SIMD
@@ -29,34 +29,6 @@ __device__ __forceinline__ float g3_tanh(const float x) { return tanhf(x); }
 // tanh x = 1 - 2 / (1 + e^{2x}): exp2 + rcp (absolute error ~1e-7; e^{2x} = inf gives 1, 0 gives -1)
 __device__ __forceinline__ float g3_tanh(const float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + g3_exp(2.0f * x)); }
 #endif
-
-__device__ __forceinline__ f32x16 g3_mfma6(const uint4 (&a)[3], const uint4 (&b)[3], f32x16 acc) {
-  acc = mfma_bf16(a[0], b[2], acc);
-  acc = mfma_bf16(a[2], b[0], acc);
-  acc = mfma_bf16(a[1], b[1], acc);
-  acc = mfma_bf16(a[0], b[1], acc);
-  acc = mfma_bf16(a[1], b[0], acc);
-  acc = mfma_bf16(a[0], b[0], acc);
-  return acc;
-}
-
-// four values -> their three bf16 planes, 8 bytes each (element i in half i & 1 of dword i >> 1)
-__device__ __forceinline__ void g3_split4(const float (&x)[4], uint2 (&p)[3]) {
-  uint32_t q[3][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const float a = x[2 * i], b = x[2 * i + 1];
-    const uint32_t a1 = __float_as_uint(a) & 0xffff0000u, b1 = __float_as_uint(b) & 0xffff0000u;
-    const float ra = a - __uint_as_float(a1), rb = b - __uint_as_float(b1);
-    const uint32_t a2 = __float_as_uint(ra) & 0xffff0000u, b2 = __float_as_uint(rb) & 0xffff0000u;
-    const float sa = ra - __uint_as_float(a2), sb = rb - __uint_as_float(b2);
-    q[0][i] = (a1 >> 16) | b1;
-    q[1][i] = (a2 >> 16) | b2;
-    q[2][i] = (__float_as_uint(sa) >> 16) | (__float_as_uint(sb) & 0xffff0000u);
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) p[k] = make_uint2(q[k][0], q[k][1]);
-}
 
 constexpr int H = 64, G3 = 192;
 
@@ -149,7 +121,7 @@ __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
   };
   auto publish = [&](const int buf) {   // xr -> planes of K block (wave - 6)
     uint4 p[3];
-    split8(xr, p[0], p[1], p[2]);
+    split_planes<3>(xr, p);
 #pragma unroll
     for (int k = 0; k < 3; ++k) xP[buf][wave - 6][k][lane] = p[k];
   };
@@ -176,7 +148,7 @@ __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
           uint4 b3[3];
 #pragma unroll
           for (int p = 0; p < 3; ++p) b3[p] = xP[buf][kb][p][lane];
-          acc = g3_mfma6(wi[kb], b3, acc);
+          acc = plane_mma<3>(wi[kb], b3, acc);
         }
       }
       if (has_h) {
@@ -185,7 +157,7 @@ __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
           uint4 b3[3];
 #pragma unroll
           for (int p = 0; p < 3; ++p) b3[p] = hsP[kb][p][lane];
-          acc = g3_mfma6(wh[kb], b3, acc);
+          acc = plane_mma<3>(wh[kb], b3, acc);
         }
       }
       if (xw) {
@@ -211,7 +183,7 @@ __global__ __launch_bounds__(512) void gru3_kernel(const pdse_gru_desc d) {
       hreg[k] = hn[k];
     }
     uint2 hp[3];
-    g3_split4(hn, hp);
+    split_planes<3>(hn, hp);
     // every matrix wave has read hsP before it reached the barrier above
 #pragma unroll
     for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(hs_w + p * 1024) = hp[p];

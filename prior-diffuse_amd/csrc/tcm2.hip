@@ -1,5 +1,5 @@
 // tcm2.hip — the fused TCM residual block of tcm.hip (model/diff3.py:215-257) in split-bf16 arithmetic
-// (gconv_common.h: an fp32 value is the exact sum of three bf16, a product its six leading cross terms on the bf16
+// (planes.h: an fp32 value is the exact sum of three bf16, a product its six leading cross terms on the bf16
 // matrix cores with fp32 accumulation), restructured around what bounded the fp32 kernel: its waves spent 58 % of
 // their life in s_waitcnt (4 waves, each walking a long chain of weight loads with 4 groups in flight).
 //
@@ -59,87 +59,7 @@ constexpr int GL_ROW = 144;        // bytes of one frame of one plane of the con
 __device__ __forceinline__ float prelu2(float v, float slope) { return v > 0.f ? v : slope * v; }
 
 // NP = 3: exact three-way splits, six products; NP = 1: plain bf16 operands, one product (the opt-in bf16 mode, round 3);
-// NP = 2 (round 4): fp16 hi + lo of the power-of-two scaled operands, three f16 products (gconv_common.h: split8h)
-template <int NP>
-__device__ __forceinline__ f32x16 mfma6r(const uint4 (&a)[NP], const uint4 (&b)[NP], f32x16 acc) {
-  if constexpr (NP == 2) {
-    acc = mfma_f16(a[1], b[0], acc);
-    acc = mfma_f16(a[0], b[1], acc);
-    acc = mfma_f16(a[0], b[0], acc);
-  } else if constexpr (NP == 3) {
-    acc = mfma_bf16(a[0], b[2], acc);
-    acc = mfma_bf16(a[2], b[0], acc);
-    acc = mfma_bf16(a[1], b[1], acc);
-    acc = mfma_bf16(a[0], b[1], acc);
-    acc = mfma_bf16(a[1], b[0], acc);
-    acc = mfma_bf16(a[0], b[0], acc);
-  } else {
-    acc = mfma_bf16(a[0], b[0], acc);
-  }
-  return acc;
-}
-
-__device__ __forceinline__ uint32_t pack_bf16_rne(const float a, const float b) {   // v_cvt_pk_bf16_f32
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  union { bf16x2 h; uint32_t u; } c;
-  c.h = __builtin_convertvector(v, bf16x2);
-  return c.u;
-}
-template <int NP>
-__device__ __forceinline__ void split8n(const float (&x)[8], uint4 (&p)[NP], const float sc = 1.0f) {
-  if constexpr (NP == 3) split8(x, p[0], p[1], p[2]);
-  else if constexpr (NP == 2) split8h(x, sc, p[0], p[1]);
-  else p[0] = make_uint4(pack_bf16_rne(x[0], x[1]), pack_bf16_rne(x[2], x[3]), pack_bf16_rne(x[4], x[5]), pack_bf16_rne(x[6], x[7]));
-}
-
-template <int NP>
-__device__ __forceinline__ void split4n(const float (&x)[4], uint2 (&p)[NP], const float sc = 1.0f);
-// four values -> their three bf16 planes, 8 bytes each (element i in half i & 1 of dword i >> 1)
-__device__ __forceinline__ void split4(const float (&x)[4], uint2& p1, uint2& p2, uint2& p3) {
-  uint32_t q[3][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const float a = x[2 * i], b = x[2 * i + 1];
-    const uint32_t a1 = __float_as_uint(a) & 0xffff0000u, b1 = __float_as_uint(b) & 0xffff0000u;
-    const float ra = a - __uint_as_float(a1), rb = b - __uint_as_float(b1);
-    const uint32_t a2 = __float_as_uint(ra) & 0xffff0000u, b2 = __float_as_uint(rb) & 0xffff0000u;
-    const float sa = ra - __uint_as_float(a2), sb = rb - __uint_as_float(b2);
-    q[0][i] = (a1 >> 16) | b1;
-    q[1][i] = (a2 >> 16) | b2;
-    q[2][i] = (__float_as_uint(sa) >> 16) | (__float_as_uint(sb) & 0xffff0000u);
-  }
-  p1 = make_uint2(q[0][0], q[0][1]);
-  p2 = make_uint2(q[1][0], q[1][1]);
-  p3 = make_uint2(q[2][0], q[2][1]);
-}
-
-// four values * sc -> fp16 hi / lo planes, 8 bytes each
-__device__ __forceinline__ void split4h(const float (&x)[4], const float sc, uint2& p1, uint2& p2) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  uint32_t q1[2], q2[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const f32x2 t = {x[2 * i] * sc, x[2 * i + 1] * sc};
-    union { f16x2 h; uint32_t u; } hi, lo;
-    hi.h = __builtin_convertvector(t, f16x2);
-    const f32x2 r = t - __builtin_convertvector(hi.h, f32x2);
-    lo.h = __builtin_convertvector(r, f16x2);
-    q1[i] = hi.u;
-    q2[i] = lo.u;
-  }
-  p1 = make_uint2(q1[0], q1[1]);
-  p2 = make_uint2(q2[0], q2[1]);
-}
-
-template <int NP>
-__device__ __forceinline__ void split4n(const float (&x)[4], uint2 (&p)[NP], const float sc) {
-  if constexpr (NP == 3) split4(x, p[0], p[1], p[2]);
-  else if constexpr (NP == 2) split4h(x, sc, p[0], p[1]);
-  else p[0] = make_uint2(pack_bf16_rne(x[0], x[1]), pack_bf16_rne(x[2], x[3]));
-}
+// NP = 2 (round 4): fp16 hi + lo of the power-of-two scaled operands, three f16 products (planes.h: split_planes, plane_mma)
 
 // two idle issue slots behind a wide store, ordered behind the store and in front of every later write of its data registers
 __device__ __forceinline__ void store_pad(const uint4& x) {
@@ -282,7 +202,7 @@ __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int n = 0; n < NT; ++n) acc[mi][n] = mfma6r<NP>(qa[j % D][mi], qb[j % D][n], acc[mi][n]);
+        for (int n = 0; n < NT; ++n) acc[mi][n] = plane_mma<NP>(qa[j % D][mi], qb[j % D][n], acc[mi][n]);
       __builtin_amdgcn_sched_barrier(0);
       if (j + D < 5) request(j + D);
       __builtin_amdgcn_sched_barrier(0);
@@ -344,7 +264,7 @@ __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const
         v[i] = gp[2] * prelu2(m * sigmoid_f(k), d.slope2) + gp[3];
       }
       uint2 pp[NP];
-      split4n<NP>(v, pp, s_pl);
+      split_planes<NP>(v, pp, s_pl);
       char* g = gls[n] + f * GL_ROW + cg * 8;
 #pragma unroll
       for (int p = 0; p < NP; ++p) *(uint2*)(g + p * 32 * GL_ROW) = pp[p];
@@ -363,7 +283,7 @@ __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const
         uint4 bp[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p) bp[p] = *(const uint4*)(gb + p * 32 * GL_ROW + kb * 32);
-        a2[n] = mfma6r<NP>(w2[kb], bp, a2[n]);
+        a2[n] = plane_mma<NP>(w2[kb], bp, a2[n]);
       }
     }
 #pragma unroll
@@ -425,9 +345,9 @@ __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const
 #pragma unroll
       for (int j = 0; j < 8; ++j) xv[j] = a2[n][8 * s + j];
       uint4 bp[NP];
-      split8n<NP>(xv, bp, s_pl);
-      a1[n][0] = mfma6r<NP>(wn[0][s], bp, a1[n][0]);
-      a1[n][1] = mfma6r<NP>(wn[1][s], bp, a1[n][1]);
+      split_planes<NP>(xv, bp, s_pl);
+      a1[n][0] = plane_mma<NP>(wn[0][s], bp, a1[n][0]);
+      a1[n][1] = plane_mma<NP>(wn[1][s], bp, a1[n][1]);
     }
   STAMP(6);
   // part is free: every thread passed the barrier behind G
@@ -477,7 +397,7 @@ __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const
       const int plane = TP * 16;
       const uint32_t ho = (uint32_t)(cg * NP * plane + (t + HS_PAD) * 16);
       uint4 pq[NP];
-      split8n<NP>(vm, pq, s_pl);
+      split_planes<NP>(vm, pq, s_pl);
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         bstore16<TCM2_ST_AUX>(pq[p], r_ho, ho, p * plane);
@@ -486,7 +406,7 @@ __device__ __forceinline__ void tcm2_block(const pdse_tcm2_desc& d, float* const
         // pad names the stored registers as inputs, so nothing may overwrite them in front of it.
         if constexpr (RAGGED) store_pad(pq[p]);
       }
-      split8n<NP>(vk, pq, s_pl);
+      split_planes<NP>(vk, pq, s_pl);
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         bstore16<TCM2_ST_AUX>(pq[p], r_ho, ho, (8 * NP + p) * plane);

@@ -558,7 +558,7 @@ def bf16_to_f32(u):
     return (np.asarray(u, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
-# f16x2 operands (np == 2; include/pdse.h: PDSE_F16_ACT_EXP, csrc/gconv_common.h: split8h): a value, scaled by a power of two
+# f16x2 operands (np == 2; include/pdse.h: PDSE_F16_ACT_EXP, csrc/planes.h: split8h): a value, scaled by a power of two
 # into the fp16 range, is hi = RN16(x), lo = RN16(x - hi) - 22 significand bits and the sign of lo, |x - hi - lo| <= 2^-23 |x|
 # while lo is a normal fp16 - and a product is a1 b1 + a1 b2 + a2 b1 on the f16 matrix cores (fp32 accumulation).
 F16_ACT_EXP = 4            # activations: planes hold value * 2^4 (exact for 2^-6 <= |value| < 4094; include/pdse.h)

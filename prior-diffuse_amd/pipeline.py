@@ -165,8 +165,6 @@ class SamplerPipeline:
         self.ranges = {}
         self.descs = []
         self.audit = bool(audit)
-        # the audit is recorded only where f16x2 operands are multiplied
-        self.audited = self.audit and split == "f16x2" and dtype == "f32" and bool(split_bf16) and self.plan is not None
         self.range_rows = []          # (range name, tensor name) of every histogram row, in table order
         self.range_hist = None        # device int32 [RANGE_CAP][32] (the kernel's uint32 counters)
 
@@ -182,20 +180,21 @@ class SamplerPipeline:
             self.valid_tab = torch.full((2 * B,), T * F0, dtype=torch.int32, device=self.device)
             ctx.keep += [self.frames_tab, self.valid_tab]
         self.stft = adopt(nets.StftPlan(ctx, B, L_, plan=self.plan, split_bf16=split_bf16, reflect_own=self.ragged)) if with_signal else None
-        pplanes = 1 if dtype == "bf16" else None     # bf16 mode: the priors' GEMM-shaped convolutions on plain bf16 operands too (korder 4)
-        aplanes = pplanes if pplanes is not None else ((2 if split == "f16x2" else 3) if split_bf16 else None)   # DB-AIAT: dense blocks (np) and GEMM convolutions
+        # operand planes of the matrix-core kernels (csrc/planes.h): 1 = plain bf16 (the bf16 mode), 2 = f16x2, 3 = bf16x3
+        nplanes = 1 if dtype == "bf16" else (2 if split == "f16x2" else 3)
+        # the priors' GEMM-shaped convolutions (csrc/gconv4.hip: korder 4 / 5 / 3) and DB-AIAT's dense blocks (np); None: their fp32 kernels
+        pplanes = nplanes if (split_bf16 or dtype == "bf16") else None
         if prior_name == "GCRN":
-            gplanes = pplanes if pplanes is not None else ((2 if split == "f16x2" else 3) if split_bf16 else None)   # korder 5 / 3 (csrc/gconv4.hip)
             self.prior = adopt(nets.GcrnPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", exclusive=exclusive,
-                                             planes=gplanes))
+                                             planes=pplanes))
         elif prior_name == "DiffUNet":
             self.prior = adopt(nets.EpsNetPlan(ctx, prior_sd, B, T, time_cond=False, plan=self.plan, split_bf16=split_bf16, exclusive=exclusive,
                                                frames=self.frames_tab))
         elif prior_name == "aia_complex_trans_ri":
-            self.prior = adopt(nets.AiaPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", planes=aplanes,
+            self.prior = adopt(nets.AiaPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", planes=pplanes,
                                             frames=self.frames_tab))
         elif prior_name == "dual_aia_trans_merge_crm":
-            self.prior = adopt(nets.DualAiaPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", planes=aplanes,
+            self.prior = adopt(nets.DualAiaPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", planes=pplanes,
                                                 frames=self.frames_tab))
         else:
             raise ValueError("prior %r not built (GCRN, DiffUNet, aia_complex_trans_ri, dual_aia_trans_merge_crm)" % prior_name)
@@ -203,9 +202,11 @@ class SamplerPipeline:
             split_bf16 = True
         self.eps = adopt(nets.EpsNetPlan(ctx, ddpm_sd, B, T, time_cond=True, nsteps=S, plan=self.plan,
                                          with_pre=not deltamu, split_bf16=split_bf16,
-                                         planes=1 if dtype == "bf16" else (2 if split == "f16x2" else 3),
+                                         planes=nplanes,
                                          exclusive=exclusive, frames=self.frames_tab))
         self.split_bf16 = self.eps.split_bf16
+        # the audit is recorded only where f16x2 operands are multiplied
+        self.audited = self.audit and self.windowed and self.plan is not None
         self.deltamu = deltamu
         self.xT_plus_init = xT_plus_init = bool(deltamu if xT_plus_init is None else xT_plus_init)
         self.cond_feat = cond_feat = (cond == "feat") and not deltamu
@@ -453,7 +454,7 @@ class SamplerPipeline:
                     st.zero_()
                     raise L.PdseError((what % (code - 1)) + ": its workgroups wait for each other and were not all resident in time (is "
                                       "another workload sharing the GPU?); build the pipeline with exclusive=False")
-        if self.split == "f16x2" and self.split_bf16 and self.dtype == "f32" and not bool(torch.isfinite(self.spec).all()):
+        if self.windowed and not bool(torch.isfinite(self.spec).all()):
             where = ""
             if self.audited:
                 top = self.range_report().above()
