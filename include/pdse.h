@@ -1192,6 +1192,49 @@ int pdse_spec_frames(const float* spec,     /* device [B][2][T][161] */
                      float* frames,         /* device [B][320][T] */
                      int32_t B, int32_t T, int32_t F, pdse_stream_t s);
 
+/* Denoising objective (csrc/objective.hip, additive within ABI 9; plain arguments): the forward noising of the reference's training
+ * step (trainer/complex_ddpm_trainer.py:699-733) for a whole batch, and the --sigma loss (utils/loss.py:46-56).  Everything is
+ * validated before the launch and without a device.
+ *
+ * Noising.  label, init [B][2][T][F] fp32, both already divided by 11; noise of the same shape; t[b] the diffusion step of utterance
+ * b; a_tab[n] = sqrt(alpha_bar_n) and s_tab[n] = sqrt(1 - alpha_bar_n), fp32.  The kernel reads a_tab[t[b]] and s_tab[t[b]] without
+ * a clamp: the caller answers for 0 <= t[b] < the tables' length.  Per element, every operation rounded to fp32 on its own in the
+ * reference's order:
+ *   sigma 1:  max[b][ch] = max |init[b][ch]| over the whole [T][F] plane, padding frames included; mask = |init| / max / 2 + 0.5;
+ *             target = noise sqrt(mask).        sigma 0:  target = noise.
+ *   mode 0 (pirorgrad):  noisy = a (label - init) + s target
+ *   mode 1 (deltamu):    noisy = a label + s (target + init)
+ *   mode 2 (plain):      noisy = a label + s target                        (the numbering of pdse_qsample_desc.mode)
+ * maxbuf [B][2] receives the maxima (zeros with sigma 0).  B <= 32767. */
+int pdse_objective_noise(const float* label,    /* device [B][2][T][F] */
+                         const float* init,     /* device [B][2][T][F] */
+                         const float* noise,    /* device [B][2][T][F] */
+                         const int32_t* t,      /* device [B] */
+                         const float* a_tab,    /* device [steps] */
+                         const float* s_tab,    /* device [steps] */
+                         float* noisy,          /* device [B][2][T][F] */
+                         float* target,         /* device [B][2][T][F] */
+                         float* maxbuf,         /* device [B][2] */
+                         int32_t B, int32_t T, int32_t F, int32_t mode, int32_t sigma, pdse_stream_t s);
+
+/* com_mse_sigma_loss of predicted against target over the frames t < frames[b]: per element d = predicted - target, mask
+ * recomputed from init and maxbuf as the noising formed it, and the fp32 term (d / mask) d - the reference's (((d m) / mask) d) m
+ * with its frame mask m = 1.  The terms are added in double in a fixed order, as the masked losses above add theirs: thread, shuffle
+ * tree, PDSE_SPECLOSS_BLOCKS partials per utterance, one workgroup over the partials in index order and the utterances in batch
+ * order.  No atomics.  per_utt[b]: the numerator of utterance b; loss[0] = sum_b per_utt[b] / (2 F sum_b frames[b]), divided in
+ * double and rounded to fp32 once.  frames_host as above: 0 <= frames[b] <= T, not all zero.  partial: scratch of
+ * B * PDSE_SPECLOSS_BLOCKS doubles.  B <= 32767. */
+int pdse_sigma_loss(const float* predicted,       /* device [B][2][T][F] */
+                    const float* target,          /* device [B][2][T][F] */
+                    const float* init,            /* device [B][2][T][F] */
+                    const float* maxbuf,          /* device [B][2] */
+                    const int32_t* frames_host,   /* host [B] */
+                    const int32_t* frames,        /* device [B] */
+                    double* partial,              /* device [B][PDSE_SPECLOSS_BLOCKS] */
+                    double* per_utt,              /* device [B] */
+                    float* loss,                  /* device [1] */
+                    int32_t B, int32_t T, int32_t F, pdse_stream_t s);
+
 /* plans: a recorded operator sequence replayed by one call (and capturable in a hipGraph) */
 typedef struct pdse_plan pdse_plan;
 int pdse_plan_create(pdse_plan** out);

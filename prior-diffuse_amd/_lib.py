@@ -356,6 +356,7 @@ EXPORTS = [
     "pdse_plan_build_graph", "pdse_plan_launch_graph", "pdse_plan_time_ops", "pdse_plan_time_tag",
     "pdse_plan_destroy", "pdse_plan_load", "pdse_plan_region", "pdse_prior_forward", "pdse_eps_forward", "pdse_enhance",
     "pdse_wav_encode", "pdse_wav_encode_channels", "pdse_pair_prep", "pdse_spec_losses", "pdse_spec_frames",
+    "pdse_objective_noise", "pdse_sigma_loss",
 ] + [name for _, _, name in OPS]
 
 
@@ -421,6 +422,10 @@ def load():
     lib.pdse_spec_losses.restype = C.c_int
     lib.pdse_spec_frames.argtypes = [_fp] * 3 + [_i32] * 3 + [C.c_void_p]
     lib.pdse_spec_frames.restype = C.c_int
+    lib.pdse_objective_noise.argtypes = [_fp] * 9 + [_i32] * 5 + [C.c_void_p]
+    lib.pdse_objective_noise.restype = C.c_int
+    lib.pdse_sigma_loss.argtypes = [_fp] * 9 + [_i32] * 3 + [C.c_void_p]
+    lib.pdse_sigma_loss.restype = C.c_int
     if lib.pdse_abi_version() != ABI_VERSION:
         raise PdseError("libpdse.so ABI %d != binding ABI %d" % (lib.pdse_abi_version(), ABI_VERSION))
     for kind, typ in DESC_TYPES.items():
@@ -498,6 +503,22 @@ def spec_frames(spec, basis, frames, B, T, F, stream=0, device=None):
     lib = load()
     with _on(device):
         check(lib.pdse_spec_frames(spec, basis, frames, int(B), int(T), int(F), C.c_void_p(stream)), "pdse_spec_frames")
+
+
+def objective_noise(label, init, noise, t, a_tab, s_tab, noisy, target, maxbuf, B, T, F, mode=0, sigma=0, stream=0, device=None):
+    """pdse_objective_noise (include/pdse.h: the forward noising of the denoising objective, csrc/objective.hip): pointers as integers."""
+    lib = load()
+    with _on(device):
+        check(lib.pdse_objective_noise(label, init, noise, t, a_tab, s_tab, noisy, target, maxbuf, int(B), int(T), int(F), int(mode),
+                                       int(sigma), C.c_void_p(stream)), "pdse_objective_noise")
+
+
+def sigma_loss(predicted, target, init, maxbuf, frames_host, frames, partial, per_utt, loss, B, T, F, stream=0, device=None):
+    """pdse_sigma_loss (include/pdse.h: com_mse_sigma_loss of the denoising objective, csrc/objective.hip): pointers as integers."""
+    lib = load()
+    with _on(device):
+        check(lib.pdse_sigma_loss(predicted, target, init, maxbuf, frames_host, frames, partial, per_utt, loss, int(B), int(T), int(F),
+                                  C.c_void_p(stream)), "pdse_sigma_loss")
 
 
 class Plan:

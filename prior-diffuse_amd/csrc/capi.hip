@@ -179,6 +179,19 @@ int pdse_spec_frames(const float* spec, const double* basis, float* frames, int3
   return pdse_spec_frames_launch(spec, basis, frames, B, T, F, (hipStream_t)s);
 }
 
+// the denoising objective's forward noising and --sigma loss (csrc/objective.hip): plain arguments, outside the operator table
+int pdse_objective_noise(const float* label, const float* init, const float* noise, const int32_t* t, const float* a_tab,
+                         const float* s_tab, float* noisy, float* target, float* maxbuf, int32_t B, int32_t T, int32_t F, int32_t mode,
+                         int32_t sigma, pdse_stream_t s) {
+  return pdse_objective_noise_launch(label, init, noise, t, a_tab, s_tab, noisy, target, maxbuf, B, T, F, mode, sigma, (hipStream_t)s);
+}
+
+int pdse_sigma_loss(const float* predicted, const float* target, const float* init, const float* maxbuf, const int32_t* frames_host,
+                    const int32_t* frames, double* partial, double* per_utt, float* loss, int32_t B, int32_t T, int32_t F,
+                    pdse_stream_t s) {
+  return pdse_sigma_loss_launch(predicted, target, init, maxbuf, frames_host, frames, partial, per_utt, loss, B, T, F, (hipStream_t)s);
+}
+
 int pdse_plan_create(pdse_plan** out) {
   if (!out) {
     pdse_set_error("plan_create: null out");

@@ -3,9 +3,12 @@
 
     python -m prior_diffuse_amd.main --retrain --assets A --sigma --joint --generate
     python -m prior_diffuse_amd.main --retrain --assets A --joint --eval --data NOISY --clean CLEAN
+    python -m prior_diffuse_amd.main --retrain --assets A --joint --eval --objective --draws 4 --data NOISY --clean CLEAN
 
 ``--eval`` runs one validation epoch (``ComplexDDPMTrainer.validate``), logs its line and writes the dictionary to
 ``<assets>/log/<doc>/eval.json``; with ``--generate`` the generation runs, as the reference tests ``generate`` first (:97).
+``--eval --objective`` runs one epoch of the denoising objective instead (``ComplexDDPMTrainer.objective``: the eps-net's loss
+on the held-out pairs, by diffusion step) and writes ``<assets>/log/<doc>/objective.json``.
 """
 import argparse
 import logging
@@ -70,7 +73,18 @@ def parse_args_and_config(argv=None):
                         "(its own noise, one exact ragged pass per file; the DB-AIAT priors need --masked-prior) and write the file "
                         "with that many different channels - at 16 kHz, 16-bit, or with --keep-format in the source's rate and "
                         "encoding; mono files are untouched; default: the network enhances the mono mix")
+    p.add_argument("--objective", action="store_true",
+                   help="(not a flag of the reference) --eval: instead of the validation epoch, evaluate the denoising objective on the "
+                        "pairs of --data / --clean - the reference's ddpm_loss, dis_loss and loss_sum with both networks in eval "
+                        "mode, and ddpm_loss by diffusion step; written to objective.json")
+    p.add_argument("--draws", type=int, default=1,
+                   help="(not a flag of the reference) --eval --objective: evaluate every batch this many times, each with a fresh "
+                        "diffusion step per utterance and fresh noise; default 1")
     args = p.parse_args(argv)
+    if args.objective and not args.eval:
+        p.error("--objective evaluates a held-out set: it needs --eval")
+    if args.draws < 1:
+        p.error("--draws must be at least 1")
     import sys
 
     given = sys.argv[1:] if argv is None else list(argv)
@@ -104,10 +118,10 @@ def main(argv=None):
     trainer = ComplexDDPMTrainer(args, config)
     if args.generate:
         return trainer.generate_wav(load_pre_train=True, data_path=args.data, batch=args.batch, inflight=args.inflight)
-    res = trainer.train_ddpm()          # --eval: one validation epoch (raises NotImplementedError otherwise: training)
+    res = trainer.train_ddpm()          # --eval: one validation epoch, or with --objective one of the denoising objective (raises NotImplementedError otherwise: training)
     import json
 
-    with open(os.path.join(args.log, "eval.json"), "w") as f:
+    with open(os.path.join(args.log, "objective.json" if args.objective else "eval.json"), "w") as f:
         json.dump(res, f, indent=1)
     return res
 

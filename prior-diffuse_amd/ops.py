@@ -233,6 +233,113 @@ def q_sample(label, init, t, noise, noise_schedule=None, mode="pirorgrad", sigma
     return out
 
 
+NOISING_MODES = {"pirorgrad": 0, "deltamu": 1, "plain": 2}     # the numbering of pdse_qsample_desc.mode
+_NOISE_TABLES = OrderedDict()     # (device, schedule bytes) -> (a, s) of ``noise_tables``; a few schedules
+
+
+def noise_tables(device, noise_schedule=None):
+    """-> (a, s, steps): the fp32 device tables a[n] = sqrt(alpha_bar_n) and s[n] = sqrt(1 - alpha_bar_n) of a schedule of betas
+    (None: ``params.noise_schedule``), with the reference's own arithmetic - the float32 cast of numpy's float64 cumprod the
+    trainer keeps in ``noise_level`` (trainer/complex_ddpm_trainer.py:42-44), then ``** 0.5`` and ``(1.0 - x) ** 0.5`` in fp32
+    (:710, :726) - computed once per (device, schedule).  The square roots are numpy's: correctly rounded, as ``q_sample``'s are
+    on the device, which torch's vectorised CPU square root is not."""
+    import numpy as np
+
+    from .params import params as _p
+
+    beta = np.ascontiguousarray(np.array(_p.noise_schedule if noise_schedule is None else noise_schedule, dtype=np.float64))
+    key = (str(torch.device(device)), beta.tobytes())
+    hit = _NOISE_TABLES.get(key)
+    if hit is None:
+        while len(_NOISE_TABLES) >= 4:
+            _NOISE_TABLES.popitem(last=False)
+        level = np.cumprod(1 - beta).astype(np.float32)
+        hit = _NOISE_TABLES[key] = tuple(torch.from_numpy(x).to(device) for x in (np.sqrt(level), np.sqrt(np.float32(1.0) - level)))
+    else:
+        _NOISE_TABLES.move_to_end(key)
+    return hit[0], hit[1], beta.size
+
+
+def noising(label, init, t, noise, mode="pirorgrad", sigma=False, noise_schedule=None, out=None):
+    """Forward noising of the denoising objective for a whole batch in one call of csrc/objective.hip (include/pdse.h:
+    pdse_objective_noise; trainer/complex_ddpm_trainer.py:709-733): ``q_sample``'s formulas with the schedule indexed on the device
+    by ``t`` and, with ``sigma``, the mask taken over every (b, channel) plane of ``init``, padding frames included.
+
+    label, init, noise: contiguous fp32 [B,2,T,F] on the GPU, label and init already divided by 11.  t: [B] integers; a host
+    tensor (or a list) is range-checked here (IndexError, as the reference's indexing raises), a device tensor is used as it is -
+    the kernel walks the tables without a clamp, like the step embedding (``_PlannedOp._steps``; ``PDSE_CHECK_STEPS=1`` checks it
+    at the price of a synchronisation).  mode: "pirorgrad", "deltamu" or "plain".
+    Returns (noisy, target, maxbuf): target = noise * sqrt(mask) with ``sigma`` and a copy of noise without, maxbuf [B*2] the
+    maxima of |init| (zeros without ``sigma``).  out: three tensors to write instead of new ones.  Bit-exact with the
+    reference's fp32 tensor arithmetic; no host synchronisation."""
+    import os
+
+    if label.device.type != "cuda":
+        raise L.PdseError("noising runs on the GPU only (no CPU fallback)")
+    if mode not in NOISING_MODES:
+        raise ValueError("mode must be one of %s" % sorted(NOISING_MODES))
+    if label.dim() != 4 or label.shape[1] != 2:
+        raise ValueError("label, init, noise: fp32 tensors of one [B,2,T,F] shape")
+    for x in (label, init, noise):
+        if not x.is_contiguous() or x.dtype != torch.float32 or x.shape != label.shape or x.device != label.device:
+            raise ValueError("label, init, noise must be contiguous fp32 tensors of one shape and device")
+    B, _, T, F_ = label.shape
+    dev = label.device
+    a, s, steps = noise_tables(dev, noise_schedule)
+    t = torch.as_tensor(t)
+    if t.shape != (B,) or t.dtype.is_floating_point:
+        raise ValueError("t must be [B] integers")
+    if (not t.is_cuda) or os.environ.get("PDSE_CHECK_STEPS", "0") == "1":
+        if int(t.min()) < 0 or int(t.max()) >= steps:
+            raise IndexError("diffusion step outside the %d-entry noise schedule" % steps)
+    t = t.to(dev, torch.int32)
+    if out is None:
+        out = (torch.empty_like(label), torch.empty_like(label), torch.empty(2 * B, dtype=torch.float32, device=dev))
+    noisy, target, maxbuf = out
+    L.objective_noise(label.data_ptr(), init.data_ptr(), noise.data_ptr(), t.data_ptr(), a.data_ptr(), s.data_ptr(), noisy.data_ptr(),
+                      target.data_ptr(), maxbuf.data_ptr(), B, T, F_, NOISING_MODES[mode], 1 if sigma else 0,
+                      torch.cuda.current_stream(dev).cuda_stream, device=dev)
+    return noisy, target, maxbuf
+
+
+def sigma_loss(predicted, target, init, maxbuf, frame_list):
+    """``com_mse_sigma_loss`` (utils/loss.py:46-56; trainer/complex_ddpm_trainer.py:736) of ``predicted`` against ``target`` over the
+    first ``frame_list[b]`` frames of every utterance, in one call of csrc/objective.hip (include/pdse.h: pdse_sigma_loss):
+
+        com_mse_sigma    ((predicted - target) * m / mask * (predicted - target) * m).sum() / (2 F sum frames)
+
+    with mask = |init| / max / 2 + 0.5 recomputed from ``init`` and ``noising``'s ``maxbuf``.  Returns a dict: ``com_mse_sigma``, a
+    0-dim fp32 device tensor, and ``per_utt``, float64 [B]: every utterance's numerator, which depends on the utterance alone.
+    The element terms are the reference's fp32 terms, added in double in a fixed order.  frame_list: host integers in [0, T], not
+    all zero (ValueError).  No host synchronisation."""
+    import numpy as np
+
+    if predicted.device.type != "cuda":
+        raise L.PdseError("sigma_loss runs on the GPU only (no CPU fallback)")
+    if predicted.dim() != 4 or predicted.shape[1] != 2:
+        raise ValueError("predicted, target, init: fp32 tensors of one [B,2,T,F] shape")
+    for x in (predicted, target, init):
+        if not x.is_contiguous() or x.dtype != torch.float32 or x.shape != predicted.shape or x.device != predicted.device:
+            raise ValueError("predicted, target, init must be contiguous fp32 tensors of one shape and device")
+    B, _, T, F_ = predicted.shape
+    dev = predicted.device
+    if maxbuf.dtype != torch.float32 or maxbuf.numel() != 2 * B or not maxbuf.is_contiguous() or maxbuf.device != dev:
+        raise ValueError("maxbuf: the contiguous fp32 [B*2] tensor of noising()")
+    frames_h = np.ascontiguousarray(np.asarray(list(frame_list), dtype=np.int64).reshape(-1))
+    if frames_h.size != B or frames_h.min() < 0 or frames_h.max() > T:
+        raise ValueError("frame_list: one frame count in [0, T] per utterance")
+    if frames_h.sum() == 0:
+        raise ValueError("frame_list: no frame in the batch, the loss has no denominator")
+    frames_h = frames_h.astype(np.int32)
+    frames = torch.from_numpy(frames_h).to(dev)
+    partial = torch.empty(B * L.SPECLOSS_BLOCKS, dtype=torch.float64, device=dev)
+    per_utt = torch.empty(B, dtype=torch.float64, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    L.sigma_loss(predicted.data_ptr(), target.data_ptr(), init.data_ptr(), maxbuf.data_ptr(), frames_h.ctypes.data, frames.data_ptr(),
+                 partial.data_ptr(), per_utt.data_ptr(), loss.data_ptr(), B, T, F_, torch.cuda.current_stream(dev).cuda_stream, device=dev)
+    return {"com_mse_sigma": loss[0], "per_utt": per_utt}
+
+
 def com_mse_loss(esti, label, frame_list):
     """Masked complex MSE of the validation loop (utils/loss.py:34-44; trainer/complex_ddpm_trainer.py:490):
     ``((esti - label) * mask) ** 2).sum() / mask.sum()`` over [B,2,T,F] with mask = 1 on the first ``frame_list[b]``

@@ -62,7 +62,7 @@ class SamplerPipeline:
     def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, T=None, L_=None, fast_sampling=True,
                  use_sigma=False, params=default_params, with_signal=None, deltamu=False, cond="init", bank=None,
                  split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False, ragged=False,
-                 verdict=False, masked_prior=False, label=False):
+                 verdict=False, masked_prior=False, label=False, objective=False):
         """deltamu: the alternative parameterisation of utils/params.py:36 — ddpm_sd is a ``Nocon`` state_dict,
         x_T = noise + X_init/11 (:947-948), eps = Nocon(x, t) (:970-971), no final ``+ X_init`` (:995).
         cond (deltamu False): what conditions DiffUNet1 — "init": X_init/11 (pirorgrad, :967-969, + X_init at the end,
@@ -127,7 +127,18 @@ class SamplerPipeline:
         also leaves on the device the clean utterances' compressed spectrogram - scaled by the noisy utterances' c, as
         Collate.collate_fn scales them (utils/dataset.py:45-58) - and the normalised-domain waveforms utils/metrics.py's
         compare_complex compares.  The leg is a second, small plan beside this one: False (default), and every pass without
-        ``clean``, records and runs exactly the operators of a pipeline without the flag."""
+        ``clean``, records and runs exactly the operators of a pipeline without the flag.
+        objective (needs L_): the plan of the denoising objective instead of the sampler's (``ObjectiveLeg``, ``self.objective``;
+        ``objective_pass``).  The front is this constructor's own - wav prep, STFT, compression, the prior, and the label leg's
+        front for the label spectrogram - and behind the prior the plan holds X_init / 11 (range "scale") and ONE recorded
+        eps-net step at a per-utterance ``tsteps`` row (range "step0", ``EpsNetPlan(nsteps=1)``): no x_T, no reverse loop, no
+        ISTFT.  ``spec`` is then the eps-net's prediction, which ``check()`` judges.  The parameterisation follows ``deltamu`` and
+        ``cond`` as trainer/complex_ddpm_trainer.py:726-733 reads them: DiffUNet1(noisy, init, t), Nocon(noisy, t), or
+        DiffUNet1(noisy, feat, t) with feat NOT divided by 11 (:701 is commented out).  Padded batches only (``ragged``:
+        ValueError); no verdict."""
+        objective = bool(objective)
+        if objective and (L_ is None or ragged or verdict):
+            raise ValueError("the objective plan needs the signal front end (pass L_) and is built for padded batches, without the verdict")
         if L_ is not None:
             T = 1 + L_ // 160
         if with_signal is None:
@@ -200,7 +211,7 @@ class SamplerPipeline:
             raise ValueError("prior %r not built (GCRN, DiffUNet, aia_complex_trans_ri, dual_aia_trans_merge_crm)" % prior_name)
         if dtype == "bf16":
             split_bf16 = True
-        self.eps = adopt(nets.EpsNetPlan(ctx, ddpm_sd, B, T, time_cond=True, nsteps=S, plan=self.plan,
+        self.eps = adopt(nets.EpsNetPlan(ctx, ddpm_sd, B, T, time_cond=True, nsteps=1 if objective else S, plan=self.plan,
                                          with_pre=not deltamu, split_bf16=split_bf16,
                                          planes=nplanes,
                                          exclusive=exclusive, frames=self.frames_tab))
@@ -211,15 +222,18 @@ class SamplerPipeline:
         self.xT_plus_init = xT_plus_init = bool(deltamu if xT_plus_init is None else xT_plus_init)
         self.cond_feat = cond_feat = (cond == "feat") and not deltamu
         self.istft = adopt(nets.IstftPlan(ctx, B, T, L_, plan=self.plan, split_bf16=split_bf16, frames=self.frames_tab,
-                                          lens=self.stft.lens if self.ragged else None)) if with_signal else None
+                                          lens=self.stft.lens if self.ragged else None)) if with_signal and not objective else None
 
         self.feat = self.prior.x                     # prior input = compressed spectrogram
         # X_init / 11: the eps-net's conditioning input only in the pirorgrad parameterisation
         self.init = self.eps.x_init if not (deltamu or cond_feat) else ctx.alloc(B, 2, T, F0)
-        self.zero = ctx.alloc(B, 2, T, F0, zero=True) if (deltamu or cond_feat) else None
+        self.zero = ctx.alloc(B, 2, T, F0, zero=True) if (deltamu or cond_feat) and not objective else None
         self.audio = self.eps.x                      # x_t, updated in place
-        self.spec = self.istft.spec if with_signal else ctx.alloc(B, 2, T, F0)
-        self.xT_in = ctx.alloc(B, 2, T, F0)          # injected x_T (kept so a replay starts from it)
+        if objective:
+            self.spec, self.xT_in = self.eps.out, None   # the prediction of the one step; nothing is injected
+        else:
+            self.spec = self.istft.spec if with_signal else ctx.alloc(B, 2, T, F0)
+            self.xT_in = ctx.alloc(B, 2, T, F0)          # injected x_T (kept so a replay starts from it)
         n = B * 2 * T * F0
 
         if self.audited:
@@ -308,10 +322,27 @@ class SamplerPipeline:
                 ew(L.EW_COPY, self.xT_in, out=self.audio)
             self.eps.build_time()
 
-        mark("prologue", prologue)
-        # diffusion-step rows are stored in loop order: row i is step n = S-1-i
-        self.eps.tsteps.copy_(torch.from_numpy(np.ascontiguousarray(Tarr[::-1]))[:, None].expand(S, B))
-        for i in range(S):
+        def objective_tail():
+            def scale():
+                ew(L.EW_DIV, self.prior.out, out=self.init, s0=PRIOR_SCALE_C)        # init_audio /= self.c  (:700)
+                if cond_feat:
+                    ew(L.EW_COPY, self.feat, out=self.eps.x_init)                     # batch_feat as it is (:701 is commented out)
+
+            def one():
+                self.eps.build_time()
+                self.eps.build_step(0, x=self.audio, x_init=None if deltamu else (self.eps.x_init if cond_feat else self.init),
+                                    out=self.eps.out)
+
+            mark("scale", scale)
+            mark("step0", one)                                                       # tsteps row 0: the utterances' own t
+
+        if objective:
+            objective_tail()
+        else:
+            mark("prologue", prologue)
+            # diffusion-step rows are stored in loop order: row i is step n = S-1-i
+            self.eps.tsteps.copy_(torch.from_numpy(np.ascontiguousarray(Tarr[::-1]))[:, None].expand(S, B))
+        for i in range(0 if objective else S):
             nstep = S - 1 - i
 
             def one(i=i, nstep=nstep):
@@ -325,7 +356,7 @@ class SamplerPipeline:
                        s0=float(c1[0]), s1=float(c2[0]), s2=PRIOR_SCALE_C)
 
             mark("step%d" % nstep, one)
-        if with_signal:
+        if self.istft is not None:
             mark("istft", lambda: self.istft.build(spec=self.spec, c=self.stft.c))
         if self.verdict:
             def count():
@@ -338,12 +369,15 @@ class SamplerPipeline:
                 range_launch(L.RANGE_NONFINITE, rows, tab=self.verdict_tab)
 
             mark("verdict", count)                                 # last launch of the plan
-        self.label = None
-        if label:
+        self.label = self.objective = None
+        if label or objective:
             if not with_signal:
                 raise ValueError("the label leg needs the signal front / back end (pass L_)")
             if self.plan is not None:
-                self.label = LabelLeg(self)
+                self.label = LabelLeg(self, back=not objective)
+                if objective:
+                    self.objective = ObjectiveLeg(self, "deltamu" if deltamu else ("plain" if cond_feat else "pirorgrad"), use_sigma,
+                                                  params.noise_schedule)
         if self.plan is not None:
             self.plan.keep(ctx.keep, ctx.bank)
         self._graph_stream = None
@@ -472,6 +506,8 @@ class SamplerPipeline:
     def sample(self, feat, x_T, graph=False):
         """feat, x_T [B,2,T,161] -> (enhanced compressed spectrogram, X_init); the
         spectrogram-level body of generate_wav (:939-998)."""
+        if self.xT_in is None:
+            raise ValueError("an objective plan has no sampler (SamplerPipeline(objective=True): objective_pass)")
         _expect(feat, self.feat, "feat")
         _expect(x_T, self.xT_in, "x_T")
         self.feat.copy_(feat)
@@ -497,6 +533,8 @@ class SamplerPipeline:
         rescaled by c).  The returned pair is what it is without ``clean``."""
         if self.stft is None:
             raise ValueError("pipeline was built without the signal front/back end (pass L_)")
+        if self.xT_in is None:
+            raise ValueError("an objective plan has no sampler (SamplerPipeline(objective=True): objective_pass)")
         _expect(wav, self.stft.wav, "wav")
         _expect(x_T, self.xT_in, "x_T")
         if clean is not None:
@@ -533,6 +571,45 @@ class SamplerPipeline:
         return wav_out, spec
 
 
+    def objective_pass(self, wav, clean, t, noise, lens=None):
+        """One evaluation of the denoising objective (trainer/complex_ddpm_trainer.py:699-733) on a plan recorded with
+        ``objective=True``: wav, clean [B,L] zero-padded pairs, lens their own lengths (as for ``enhance``: the padding takes
+        part); t [B] integer diffusion steps, a host tensor is range-checked (IndexError), a device tensor is used as it is;
+        noise [B,2,T,161].  Front (wav prep, STFT, compression, prior, label spectrogram), X_init / 11 and label / 11, the
+        noising at every utterance's own step, one eps-net step with ``tsteps = t``.  Afterwards, in buffers the next pass
+        overwrites: ``spec`` (the prediction), ``audio`` (noisy), ``init`` (X_init / 11), ``init_spec`` (X_init), ``label.spec``
+        (the label) and ``objective.label`` (label / 11), ``.noise``, ``.target``, ``.maxbuf``, ``.t``.  Returns ``spec``.
+        Nothing is synchronised."""
+        leg = self.objective
+        if leg is None:
+            raise ValueError("objective_pass needs a pipeline recorded with objective=True")
+        _expect(wav, self.stft.wav, "wav")
+        _expect(clean, self.label.clean, "clean")
+        _expect(noise, leg.noise, "noise")
+        t = torch.as_tensor(t)
+        if tuple(t.shape) != (self.B,) or t.dtype.is_floating_point:
+            raise ValueError("t: expected %d integer diffusion steps" % self.B)
+        if not t.is_cuda and (int(t.min()) < 0 or int(t.max()) >= len(leg.noise_schedule)):
+            raise IndexError("diffusion step outside the %d-entry noise schedule" % len(leg.noise_schedule))
+        self.stft.wav.copy_(wav)
+        self.label.clean.copy_(clean)
+        leg.noise.copy_(noise)
+        leg.t.copy_(t)
+        self.eps.tsteps.copy_(leg.t.view(1, self.B))     # the step embedding's row, as floats
+        if lens is None:
+            self.stft.lens.fill_(self.L)
+        else:
+            self.stft.lens.copy_(torch.as_tensor(lens, dtype=torch.int32))
+        stream = self._stream()
+        self.label.prepare(stream)             # behind the copies of wav, clean and lens, ahead of the pass
+        self.run("stft", "scale")
+        self.label.plan.run(stream)
+        leg.run(stream)
+        self.plan.run_range(*self.ranges["step0"], stream)     # not ``run``: the pass is one, its audit table is cleared once
+        self._ranges_run = set(self.ranges)
+        return self.spec
+
+
 class LabelLeg:
     """The label leg of a validation pass (``SamplerPipeline(label=True)``): what the reference's validation loop needs beside
     the enhancement (trainer/complex_ddpm_trainer.py:408-559, utils/dataset.py:45-74, utils/metrics.py:528-566), as direct
@@ -552,7 +629,8 @@ class LabelLeg:
     shows in its fifth decimal.  On a ragged pipeline the leg uses its length tables: the clean rows reflect
     at their own end and the overlap-adds stop at an utterance's own frames and samples in an exact pass."""
 
-    def __init__(self, pipe):
+    def __init__(self, pipe, back=True):
+        """back False: ``prepare`` and the front only - the label spectrogram, which is all the objective plan needs of the leg."""
         from . import ops
 
         ctx, B, T, L_ = pipe.ctx, pipe.B, pipe.T, pipe.L
@@ -562,6 +640,9 @@ class LabelLeg:
         self.clean, self.spec = self.stft.wav, self.stft.feat
         self.stft.build(prep=False)
         self.plan.keep(ctx.keep, ctx.bank)
+        self.descs = self.stft.descs
+        if not back:
+            return
         self.basis, win2 = ops.frame_tables(pipe.device)
         lens = pipe.stft.lens if pipe.ragged else None
         self.back = nets.PlanBase(ctx, L.Plan(pipe.device))
@@ -590,6 +671,44 @@ class LabelLeg:
         for spec, fr in zip((self.spec, pipe.prior.out, pipe.spec), self.frames):
             L.spec_frames(spec.data_ptr(), self.basis.data_ptr(), fr.data_ptr(), pipe.B, pipe.T, F0, stream, device=pipe.device)
         self.back.plan.run(stream)
+
+
+class ObjectiveLeg:
+    """What the objective plan (``SamplerPipeline(objective=True)``) holds beside the shared front: the buffers of the forward
+    noising of trainer/complex_ddpm_trainer.py:699-733 and one small plan.
+
+        scale     (plan) label / 11 (:699) on the label leg's spectrogram -> ``label``; X_init / 11 is the pipeline's own range
+                  "scale", written where the eps-net reads its conditioning input.
+        noising   pdse_objective_noise (csrc/objective.hip; a plain-argument call, not recordable) on ``label``, the pipeline's
+                  ``init``, ``noise`` and the step row ``t`` -> the eps-net's input (``pipe.audio``), ``target``, ``maxbuf``.
+
+    mode: "pirorgrad", "deltamu" or "plain" (``ops.NOISING_MODES``); sigma: the --sigma mask and target."""
+
+    def __init__(self, pipe, mode, sigma, noise_schedule):
+        ctx, B, T = pipe.ctx, pipe.B, pipe.T
+        if len(noise_schedule) > 50:
+            raise ValueError("the objective draws t below len(noise_schedule) = %d, the step embedding has 50 entries" % len(noise_schedule))
+        self.pipe, self.sigma, self.noise_schedule = pipe, bool(sigma), list(noise_schedule)
+        self.mode = mode
+        self.label, self.noise, self.target = ctx.alloc(B, 2, T, F0), ctx.alloc(B, 2, T, F0), ctx.alloc(B, 2, T, F0)
+        self.maxbuf = ctx.alloc(2 * B)
+        self.t = torch.zeros(B, dtype=torch.int32, device=pipe.device)
+        ctx.keep.append(self.t)
+        self.scale = nets.PlanBase(ctx, L.Plan(pipe.device))
+        d = L.EwDesc()
+        d.a, d.out, d.n, d.s0, d.op = pipe.label.spec.data_ptr(), self.label.data_ptr(), self.label.numel(), PRIOR_SCALE_C, L.EW_DIV
+        self.scale.add(d, nets.TAG_EW)
+        self.scale.plan.keep(ctx.keep)
+        self.descs = self.scale.descs
+
+    def run(self, stream):
+        """Behind the pipeline's ranges "stft" .. "scale" and the label leg's front: label / 11, then the noising."""
+        from . import ops
+
+        pipe = self.pipe
+        self.scale.plan.run(stream)
+        ops.noising(self.label, pipe.init, self.t, self.noise, mode=self.mode, sigma=self.sigma, noise_schedule=self.noise_schedule,
+                    out=(pipe.audio, self.target, self.maxbuf))
 
 
 class ConcurrentSampler:

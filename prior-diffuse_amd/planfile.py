@@ -130,6 +130,8 @@ def save_pipeline(path, pipe):
         raise ValueError("the pipeline was built without the signal front / back end (pass L_)")
     if getattr(pipe, "ragged", False):
         raise ValueError("plan files are dense (pdse_enhance has no length arguments): save a pipeline built without ragged=True")
+    if getattr(pipe, "objective", None) is not None:
+        raise ValueError("plan files hold the sampler's plan: an objective plan runs plain-argument calls between its ranges")
     if getattr(pipe, "verdict", False):
         raise ValueError("plan files do not carry the finiteness verdict: save a pipeline built without verdict=True")
     pipe.stft.lens.fill_(pipe.L)

@@ -234,10 +234,10 @@ class ComplexDDPMTrainer(object):
         return _inference_schedule(self.params, fast_sampling)
 
     # ---- batched entry points ----------------------------------------------
-    def _key(self, B, T=None, L_=None, ragged=False, label=False):
+    def _key(self, B, T=None, L_=None, ragged=False, label=False, objective=False):
         """The key of a geometry in the plan caches and in ``_range_fallback`` / ``_audit_clean``."""
         return ((B, T, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling)) + ((True,) if ragged else ())
-                + (("label",) if label else ()))
+                + (("label",) if label else ()) + (("objective",) if objective else ()))
 
     def _split_of(self, key, split):
         """The operand split a plan of the geometry ``key`` is built with, where ``split`` is what it was asked for."""
@@ -258,15 +258,16 @@ class ComplexDDPMTrainer(object):
         replay a plan from its hipGraph, one host call instead of ~770 launches, do so then; a length seen once is not worth
         the capture."""
         key = self._key(**geom)
-        ragged, label = True in key[5:], "label" in key[5:]
+        ragged = True in key[5:]
+        legs = {name: True for name in ("label", "objective") if name in key[5:]}      # the plans with a leg beside the sampler's
         build = partial(self._build, key, self._split_of(key, self.split), exclusive=self.exclusive, audit=self.audit,
-                        ragged=ragged, masked_prior=ragged and self.masked_prior, **({"label": True} if label else {}))
+                        ragged=ragged, masked_prior=ragged and self.masked_prior, **legs)
         pipe, met = self._pipes.take(key, build)
         return pipe, key, met
 
-    def _pipe(self, B, T=None, L_=None, ragged=False, label=False):
+    def _pipe(self, B, T=None, L_=None, ragged=False, label=False, objective=False):
         """The recorded plan of one geometry."""
-        return self._plan(B=B, T=T, L_=L_, ragged=ragged, label=label)[0]
+        return self._plan(B=B, T=T, L_=L_, ragged=ragged, label=label, objective=objective)[0]
 
     def _checked(self, run, **geom):
         """``run(pipe, graph) -> result`` on the plan of a geometry, verified (``SamplerPipeline.check``: synchronises); graph:
@@ -750,6 +751,26 @@ class ComplexDDPMTrainer(object):
             logging.warning("%s: %d of %d samples clipped at the %d-bit range", dst, clipped, keep, 8 * width)
 
     # ---- the validation epoch (:399-580) -------------------------------------
+    @staticmethod
+    def _pairs(noisy_wavs, clean_wavs):
+        """-> (noisy, clean, lens): the utterance pairs of a batch as lists of 1-D fp32 tensors and their lengths; ValueError for
+        a pair of unequal length and for an utterance no longer than the reflect padding."""
+        noisy = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in noisy_wavs]
+        clean = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in clean_wavs]
+        lens = [int(w.numel()) for w in noisy]
+        if len(clean) != len(noisy) or any(c.numel() != n for c, n in zip(clean, lens)):
+            raise ValueError("every noisy utterance needs a clean partner of its own length")
+        if min(lens) < 161:
+            raise ValueError("utterances must be longer than the reflect padding (160 samples)")
+        return noisy, clean, lens
+
+    def _padded(self, wavs, lens):
+        """The utterances zero-padded to the longest, [B, L] on the device (Collate.collate_fn, utils/dataset.py:45-58)."""
+        batch = torch.zeros(len(wavs), max(lens), dtype=torch.float32, device=self.device)
+        for b, w in enumerate(wavs):
+            batch[b, :lens[b]] = w.to(self.device)
+        return batch
+
     def validate_batch(self, noisy_wavs, clean_wavs, x_T=None, exact=False, prior=True, stoi=False):
         """One batch of the validation loop, scored on the device (:408-559).  noisy_wavs, clean_wavs: lists of 1-D
         waveforms, pair by pair of one length.  The pass is ``enhance_batch``'s - every noisy utterance RMS-normalised over its
@@ -765,24 +786,14 @@ class ComplexDDPMTrainer(object):
         float64 numerators and one [B] tensor per measure.  One synchronisation: the pass's own check (``_checked``)."""
         from . import metrics, validation as V
 
-        noisy = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in noisy_wavs]
-        clean = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in clean_wavs]
-        lens = [int(w.numel()) for w in noisy]
-        if len(clean) != len(noisy) or any(c.numel() != n for c, n in zip(clean, lens)):
-            raise ValueError("every noisy utterance needs a clean partner of its own length")
-        if min(lens) < 161:
-            raise ValueError("utterances must be longer than the reflect padding (160 samples)")
+        noisy, clean, lens = self._pairs(noisy_wavs, clean_wavs)
         frames, cut = [V.frame_num(n) for n in lens], [V.trim_len(n) for n in lens]
         if min(cut) < metrics.MIN_LEN:
             raise ValueError("utterances must keep at least %d samples after trimming to frames" % metrics.MIN_LEN)
         B, L_ = len(noisy), max(lens)
         if exact:
             ragged_args(self.prior_name, L_, masked=self.masked_prior)
-        batch = torch.zeros(B, L_, dtype=torch.float32, device=self.device)
-        cbatch = torch.zeros(B, L_, dtype=torch.float32, device=self.device)
-        for b, (w, c) in enumerate(zip(noisy, clean)):
-            batch[b, :lens[b]] = w.to(self.device)
-            cbatch[b, :lens[b]] = c.to(self.device)
+        batch, cbatch = self._padded(noisy, lens), self._padded(clean, lens)
         x_T = self._x_T((B, 2, 1 + L_ // 160, 161), x_T)
 
         def run(pipe, graph):
@@ -816,34 +827,46 @@ class ComplexDDPMTrainer(object):
         ``mean_wss``, ``mean_fwsnrseg`` (``mean_stoi``, ``mean_estoi`` with ``stoi``): means of batch means; with ``prior`` all of it
         again under "init", for X_init - what the diffusion adds over its prior; ``files``: per file its name, frames, loss
         numerators and measures.  PESQ and the composite figures that need it stay out, as in ``metrics``."""
-        from . import validation as V
-
-        pairs = V.pair_names(noisy_dir, clean_dir)
-        if batch_size is None:
-            batch_size = self.config.train.batch_size
-        batches = V.windows(len(pairs), batch_size, order=order, drop_last=drop_last)
+        names, batches, load = self._pair_epoch(noisy_dir, clean_dir, batch_size, order, drop_last)
         if x_T is not None and len(x_T) != len(batches):
             raise ValueError("x_T: expected one tensor per batch (%d), got %d" % (len(batches), len(x_T)))
         ndiscard = len(self.inference_schedule(self.params.fast_sampling)[0]) - 1 if rng_fidelity else 0
         held = []
         with torch.no_grad():
             for k, idx in enumerate(batches):
-                part = [pairs[i] for i in idx]
-                nwav, nlens = wavdev.load([p for p, _ in part], self.device, 16000, formats=self.wav_formats)
-                cwav, clens = wavdev.load([c for _, c in part], self.device, 16000, formats=self.wav_formats)
-                V.check_lengths(part, nlens, clens)
-                shape = (len(idx), 2, 1 + max(int(n) for n in nlens) // 160, 161)
+                noisy, clean = load(idx)
+                shape = (len(idx), 2, 1 + max(int(w.numel()) for w in noisy) // 160, 161)
                 if x_T is None:
                     draw = self._x_T(shape, None)                                  # :448 randn_like(init_audio)
                     for _ in range(ndiscard):
                         torch.randn(*shape, device=self.device, dtype=torch.float32)   # :484 randn_like(audio), scaled by 0
                 else:
                     draw = x_T[k]
-                _, scores = self.validate_batch([nwav[j, :nlens[j]] for j in range(len(idx))],
-                                                [cwav[j, :clens[j]] for j in range(len(idx))], x_T=draw, exact=exact, prior=prior,
-                                                stoi=stoi)
+                _, scores = self.validate_batch(noisy, clean, x_T=draw, exact=exact, prior=prior, stoi=stoi)
                 held.append((idx, scores))
-        return self._collect_validation(held, [os.path.basename(p) for p, _ in pairs], prior, stoi)
+        return self._collect_validation(held, names, prior, stoi)
+
+    def _pair_epoch(self, noisy_dir, clean_dir, batch_size, order, drop_last):
+        """The file loop of an epoch over the (noisy, clean) pairs of two directories, shared by ``validate`` and ``objective``:
+        -> (names, batches, load).  names: the pairs' file names in name order (``validation.pair_names``); batches: the epoch's
+        windows as lists of indices into them (``validation.windows``; batch_size None: ``config.train.batch_size``);
+        load(idx) -> (noisy, clean): the pairs of one batch decoded on the device (``wavdev.load``, the trainer's
+        ``wav_formats``) as lists of 1-D waveforms of their own lengths, a pair of unequal length raising ValueError."""
+        from . import validation as V
+
+        pairs = V.pair_names(noisy_dir, clean_dir)
+        if batch_size is None:
+            batch_size = self.config.train.batch_size
+        batches = V.windows(len(pairs), batch_size, order=order, drop_last=drop_last)
+
+        def load(idx):
+            part = [pairs[i] for i in idx]
+            nwav, nlens = wavdev.load([p for p, _ in part], self.device, 16000, formats=self.wav_formats)
+            cwav, clens = wavdev.load([c for _, c in part], self.device, 16000, formats=self.wav_formats)
+            V.check_lengths(part, nlens, clens)
+            return [nwav[j, :nlens[j]] for j in range(len(idx))], [cwav[j, :clens[j]] for j in range(len(idx))]
+
+        return [os.path.basename(p) for p, _ in pairs], batches, load
 
     def _collect_validation(self, held, names, prior, stoi):
         """The epoch's scores in one copy to the host, then ``validation.aggregate``."""
@@ -868,18 +891,139 @@ class ComplexDDPMTrainer(object):
             batches.append(row)
         return V.aggregate(batches, names, F=161, prior=prior, stoi=stoi)
 
+    # ---- the denoising objective on a held-out set (train_step's figures, :633-760) ---------
+    def objective_batch(self, noisy_wavs, clean_wavs, t=None, noise=None, tensors=False):
+        """The quantity the eps-network is trained on, for one batch of (noisy, clean) pairs, on the device (:699-738): the
+        front of a validation pass - every noisy utterance RMS-normalised over its own samples, zero-padded to the longest,
+        the padding takes part; the label scaled by the noisy utterance's c; the prior - then X_init / 11 and label / 11, the
+        forward noising at a per-utterance diffusion step (``ops.noising``), ONE eps-net step at those steps, and the loss of
+        its prediction against the noise it was given (with ``--sigma``: against the masked noise, ``ops.sigma_loss``).  The
+        parameterisation follows ``params.pirorgrad`` / ``params.deltamu`` as :720-733 reads them.  Both networks run in eval
+        mode, as in validation: a held-out evaluation of the objective, not a replay of a training step
+        (oracle/bn_train_mode_gap.py).  Padded batches only.
+
+        t: [B] integer diffusion steps; None: ``torch.randint(0, len(noise_schedule), [B])``.  noise: [B, 2, T, 161]; None:
+        ``torch.randn`` of that shape.  Both are drawn on the device from the global generator, t first (:707, :711), so a
+        seeded run follows the reference's draws.
+        Returns scores, device tensors but for ``frames`` (host list): ``t`` [B] int32; ``ddpm``: with ``--sigma``
+        {"loss" [1], "per_utt" [B]} (``ops.sigma_loss``), else {"loss" [3] (com_mse, mag_mse, com_mag_mse), "per_utt" [B, 2]}
+        (``ops.spec_losses``) over ``frame_num = len // 160 + 1`` frames; ``dis``: the latter for X_init against the label, both
+        before the division by 11 (:668).  tensors=True: also clones of ``noisy``, ``target``, ``predicted``, ``init`` and
+        ``label`` (the last two divided by 11), for tests and debugging.  One synchronisation: the pass's own check
+        (``_checked``)."""
+        from . import validation as V
+
+        noisy, clean, lens = self._pairs(noisy_wavs, clean_wavs)
+        frames = [V.frame_num(n) for n in lens]
+        B, T = len(noisy), 1 + max(lens) // 160
+        if t is None:
+            t = torch.randint(0, len(self.params.noise_schedule), [B], device=self.device)               # :707
+        if noise is None:
+            noise = torch.randn(B, 2, T, 161, device=self.device, dtype=torch.float32)                    # :711 randn_like(batch_label)
+        return self._objective_run(noisy, clean, lens, frames, t, noise, tensors)
+
+    def _objective_run(self, noisy, clean, lens, frames, t, noise, tensors):
+        """``objective_batch`` behind its draws: the verified pass on the objective plan of the geometry, and the losses."""
+        from . import validation as V
+
+        batch, cbatch = self._padded(noisy, lens), self._padded(clean, lens)
+        noise = noise.to(self.device, torch.float32)
+        sigma = bool(getattr(self.args, "sigma", False))
+
+        def run(pipe, graph):
+            predicted = pipe.objective_pass(batch, cbatch, t, noise, lens=lens)                             # never replayed
+            leg = pipe.objective
+            with torch.cuda.device(self.device):
+                dis = ops.spec_losses(pipe.init_spec, pipe.label.spec, frames)
+                if sigma:
+                    ls = ops.sigma_loss(predicted, leg.target, pipe.init, leg.maxbuf, frames)
+                    ddpm = {"loss": ls["com_mse_sigma"].reshape(1), "per_utt": ls["per_utt"]}
+                else:
+                    ls = ops.spec_losses(predicted, leg.target, frames)
+                    ddpm = {"loss": torch.stack([ls[k] for k in V.LOSSES]), "per_utt": ls["per_utt"]}
+            scores = {"frames": frames, "t": leg.t.clone(), "ddpm": ddpm,
+                      "dis": {"loss": torch.stack([dis[k] for k in V.LOSSES]), "per_utt": dis["per_utt"]}}
+            if tensors:
+                scores.update(noisy=pipe.audio.clone(), target=leg.target.clone(), predicted=predicted.clone(),
+                              init=pipe.init.clone(), label=leg.label.clone())
+            return scores
+
+        return self._checked(run, B=len(noisy), L_=max(lens), objective=True)
+
+    def objective(self, noisy_dir="data/noisy_testset_wav", clean_dir="data/clean_testset_wav", batch_size=None, order="sorted",
+                  drop_last=False, draws=1, t=None, noise=None, lam=None):
+        """One epoch of the denoising objective over the (noisy, clean) pairs of two directories: ``train_step``'s three logged
+        figures (:743-749) on a held-out set, and the eps-net's loss by diffusion step.  Returns the dictionary of
+        ``objective.aggregate``.  The file loop is ``validate``'s (``_pair_epoch``): pairs by name, windows of the sorted names,
+        ``order`` / ``drop_last`` as there.  draws: every batch is evaluated this many times with fresh (t, noise) - one draw per
+        pair gives a noisy per-step curve on a small set.  t / noise: None, or lists with one entry per (batch, draw), batch by
+        batch (nothing is drawn then).  lam: the weight of ddpm_loss in loss_sum; None: ``config.train.lam``, 1.0 where the
+        config has none.  The loss is the one ``config.train.loss`` names (``objective.loss_name``), the --sigma loss for
+        ddpm_loss with ``--sigma``.  The scores stay on the device until the epoch ends and come back in one copy; an
+        evaluation synchronises once, for its pass's own check."""
+        from . import objective as O
+
+        loss = O.loss_name(self.config)
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError("draws must be at least 1, got %d" % draws)
+        names, batches, load = self._pair_epoch(noisy_dir, clean_dir, batch_size, order, drop_last)
+        for given, what in ((t, "t"), (noise, "noise")):
+            if given is not None and len(given) != len(batches) * draws:
+                raise ValueError("%s: expected one entry per (batch, draw) (%d), got %d" % (what, len(batches) * draws, len(given)))
+        held = []
+        with torch.no_grad():
+            for k, idx in enumerate(batches):
+                noisy, clean = load(idx)
+                for j in range(draws):
+                    at = k * draws + j
+                    scores = self.objective_batch(noisy, clean, t=None if t is None else t[at], noise=None if noise is None else noise[at])
+                    held.append((idx, scores))
+        if lam is None:
+            lam = getattr(self.config.train, "lam", 1.0)
+        return self._collect_objective(held, names, loss, lam)
+
+    def _collect_objective(self, held, names, loss, lam):
+        """The epoch's scores in one copy to the host, then ``objective.aggregate``."""
+        from . import objective as O
+
+        sigma = bool(getattr(self.args, "sigma", False))
+        flat = [x.double().flatten() for _, sc in held for x in (sc["t"], sc["ddpm"]["loss"], sc["ddpm"]["per_utt"], sc["dis"]["loss"],
+                                                                  sc["dis"]["per_utt"])]
+        host = torch.cat(flat).cpu().numpy() if flat else None
+        batches, at = [], 0
+
+        def take(n):
+            nonlocal at
+            at += n
+            return host[at - n:at]
+
+        for idx, sc in held:
+            B = len(idx)
+            row = {"names": idx, "frames": sc["frames"], "t": take(B).astype(int)}
+            row["ddpm"] = {"loss": take(1), "per_utt": take(B)} if sigma else {"loss": take(3), "per_utt": take(2 * B).reshape(B, 2)}
+            row["dis"] = {"loss": take(3), "per_utt": take(2 * B).reshape(B, 2)}
+            batches.append(row)
+        return O.aggregate(batches, names, len(self.params.noise_schedule), loss=loss, sigma=sigma, lam=lam,
+                           joint=bool(getattr(self.args, "joint", False)), F=161)
+
     def train_ddpm(self):
         """With ``args.eval``: one validation epoch (``validate`` over ``args.data`` / ``args.clean``, ``--batch`` as the batch
         size where the CLI was given one), logged in one line, and its dictionary returned - the reference exits there
-        (:579-580).  Without it: training, which this package does not implement."""
+        (:579-580).  With ``args.objective`` as well: one epoch of the denoising objective instead (``objective``, ``args.draws``
+        evaluations per batch).  Without ``args.eval``: training, which this package does not implement."""
         if not getattr(self.args, "eval", False):
             raise NotImplementedError("training is outside the sampling path this package implements (SURVEY.md §8)")
-        from . import validation as V
+        from . import objective as O, validation as V
 
         kw = {}
         for arg, name in (("data", "noisy_dir"), ("clean", "clean_dir"), ("eval_batch", "batch_size")):
             if getattr(self.args, arg, None) is not None:
                 kw[name] = getattr(self.args, arg)
+        if getattr(self.args, "objective", False):
+            res = self.objective(draws=getattr(self.args, "draws", 1), **kw)
+            logging.info(O.log_line(res))
+            return res
         res = self.validate(**kw)
         logging.info(V.log_line(res))
         return res
