@@ -216,14 +216,32 @@ typedef struct pdse_ew_desc {
   int32_t op;
 } pdse_ew_desc;
 
-/* sqrt-compression / square-decompression of a [B,2,T,F] spectrogram
- * (trainer/complex_ddpm_trainer.py:931-937 and :1004-1008):  power = 0.5 or 2. */
+/* Compression / decompression of a [B,2,T,F] spectrogram: the magnitude m = |X| goes through f, the phase is kept, cos / sin of
+ * it evaluated as re / m, im / m with (1, 0) at m == 0 (trainer/complex_ddpm_trainer.py:931-937 and :1004-1008 for the square
+ * root; :414-435 and utils/metrics.py:531-551 for the other feat_type values of the configuration files).  Modes, additive
+ * within ABI 9 (the struct is unchanged; any other value is an argument error):
+ *   feat_type  compress (front end, label)        decompress (back end)
+ *   sqrt       PDSE_COMPAND_SQRT    m ** 0.5      PDSE_COMPAND_SQUARE  m ** 2
+ *   normal     PDSE_COMPAND_MAG     m             PDSE_COMPAND_COPY    re, im moved unchanged
+ *   cubic      PDSE_COMPAND_POW03   m ** 0.3      PDSE_COMPAND_POW103  m ** (10 / 3)
+ *   log_1x     PDSE_COMPAND_LOG1X   log(m + 1)    PDSE_COMPAND_EXPM1   exp(m) - 1
+ *   none       no launch                          PDSE_COMPAND_COPY
+ * Everything is fp32, every operation rounded on its own: m + 1 is rounded before the logarithm (below m = 6e-8 the result
+ * is 0) and exp(m) before the subtraction; exp(m) beyond the fp32 range gives a non-finite element, nothing is clamped. */
+#define PDSE_COMPAND_SQRT 0
+#define PDSE_COMPAND_SQUARE 1
+#define PDSE_COMPAND_MAG 2
+#define PDSE_COMPAND_COPY 3
+#define PDSE_COMPAND_POW03 4
+#define PDSE_COMPAND_POW103 5
+#define PDSE_COMPAND_LOG1X 6
+#define PDSE_COMPAND_EXPM1 7
 typedef struct pdse_compand_desc {
   const float* in;
   float* out;
   int64_t plane; /* T*F */
   int32_t B;
-  int32_t mode; /* 0: mag**0.5 (compress), 1: mag**2 (decompress) */
+  int32_t mode; /* PDSE_COMPAND_*: 0 mag**0.5, 1 mag**2, 2 mag, 3 copy, 4 mag**0.3, 5 mag**(10/3), 6 log(mag+1), 7 exp(mag)-1 */
   /* F > 0: the output is written as out[b*out_sb + ri*out_sc + t*out_st + f] instead of the input's own layout (the
    * ISTFT GEMM reads frame-major rows [B][T][2*168] whose 336 entries are its K dimension; the pad entries are never
    * written).  F == 0: out has the layout of in. */
@@ -1191,6 +1209,16 @@ int pdse_spec_frames(const float* spec,     /* device [B][2][T][161] */
                      const double* basis,   /* device [322][320] */
                      float* frames,         /* device [B][320][T] */
                      int32_t B, int32_t T, int32_t F, pdse_stream_t s);
+
+/* pdse_spec_frames for every decompression (additive within ABI 9): mode is the DECOMPRESS mode of pdse_compand_desc -
+ * PDSE_COMPAND_SQUARE (what pdse_spec_frames does, which forwards here), PDSE_COMPAND_COPY, PDSE_COMPAND_POW103 or
+ * PDSE_COMPAND_EXPM1; any other value is an argument error.  The decompression runs in double on the fp32 spectrogram:
+ * m = sqrt(re^2 + im^2), then m (re, im), (re, im), pow(m, 10.0 / 3.0) (re, im) / m or (exp(m) - 1.0) (re, im) / m with (0, 0) at
+ * m == 0; the 322-term sum is the same. */
+int pdse_spec_frames_mode(const float* spec,     /* device [B][2][T][161] */
+                          const double* basis,   /* device [322][320] */
+                          float* frames,         /* device [B][320][T] */
+                          int32_t B, int32_t T, int32_t F, int32_t mode, pdse_stream_t s);
 
 /* Denoising objective (csrc/objective.hip, additive within ABI 9; plain arguments): the forward noising of the reference's training
  * step (trainer/complex_ddpm_trainer.py:699-733) for a whole batch, and the --sigma loss (utils/loss.py:46-56).  Everything is

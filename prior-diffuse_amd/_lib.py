@@ -72,6 +72,23 @@ class CompandDesc(C.Structure):
                 ("out_sb", _i64), ("out_sc", _i64), ("out_st", _i64), ("F", _i32), ("pad_", _i32)]
 
 
+# pdse_compand_desc.mode (include/pdse.h PDSE_COMPAND_*) and the feat_type values of the configuration files: what the front
+# end and the label leg record (None: no launch) and what the back end and the scored waveforms decompress with
+COMPAND_SQRT, COMPAND_SQUARE, COMPAND_MAG, COMPAND_COPY, COMPAND_POW03, COMPAND_POW103, COMPAND_LOG1X, COMPAND_EXPM1 = range(8)
+FEAT_TYPES = ("sqrt", "normal", "cubic", "log_1x", "none")
+COMPRESS_MODE = {"sqrt": COMPAND_SQRT, "normal": COMPAND_MAG, "cubic": COMPAND_POW03, "log_1x": COMPAND_LOG1X, "none": None}
+DECOMPRESS_MODE = {"sqrt": COMPAND_SQUARE, "normal": COMPAND_COPY, "cubic": COMPAND_POW103, "log_1x": COMPAND_EXPM1,
+                   "none": COMPAND_COPY}
+
+
+def feat_type_of(value):
+    """``value`` if it is one of FEAT_TYPES, else ValueError.  The reference treats every string outside its list as "leave the
+    STFT alone"; here only the literal "none" means that, so that a misspelt mode does not pass for one."""
+    if value not in FEAT_TYPES:
+        raise ValueError("feat_type %r: must be one of 'sqrt', 'normal', 'cubic', 'log_1x', 'none'" % (value,))
+    return value
+
+
 class WavprepDesc(C.Structure):
     _fields_ = [("wav", _fp), ("xpad", _fp), ("c", _fp), ("lens", _fp),
                 ("B", _i32), ("L", _i32), ("pad", _i32), ("normalize", _i32), ("reflect_own", _i32), ("pad_", _i32)]
@@ -356,6 +373,7 @@ EXPORTS = [
     "pdse_plan_build_graph", "pdse_plan_launch_graph", "pdse_plan_time_ops", "pdse_plan_time_tag",
     "pdse_plan_destroy", "pdse_plan_load", "pdse_plan_region", "pdse_prior_forward", "pdse_eps_forward", "pdse_enhance",
     "pdse_wav_encode", "pdse_wav_encode_channels", "pdse_pair_prep", "pdse_spec_losses", "pdse_spec_frames",
+    "pdse_spec_frames_mode",
     "pdse_objective_noise", "pdse_sigma_loss",
 ] + [name for _, _, name in OPS]
 
@@ -422,6 +440,8 @@ def load():
     lib.pdse_spec_losses.restype = C.c_int
     lib.pdse_spec_frames.argtypes = [_fp] * 3 + [_i32] * 3 + [C.c_void_p]
     lib.pdse_spec_frames.restype = C.c_int
+    lib.pdse_spec_frames_mode.argtypes = [_fp] * 3 + [_i32] * 4 + [C.c_void_p]
+    lib.pdse_spec_frames_mode.restype = C.c_int
     lib.pdse_objective_noise.argtypes = [_fp] * 9 + [_i32] * 5 + [C.c_void_p]
     lib.pdse_objective_noise.restype = C.c_int
     lib.pdse_sigma_loss.argtypes = [_fp] * 9 + [_i32] * 3 + [C.c_void_p]
@@ -503,6 +523,14 @@ def spec_frames(spec, basis, frames, B, T, F, stream=0, device=None):
     lib = load()
     with _on(device):
         check(lib.pdse_spec_frames(spec, basis, frames, int(B), int(T), int(F), C.c_void_p(stream)), "pdse_spec_frames")
+
+
+def spec_frames_mode(spec, basis, frames, B, T, F, mode, stream=0, device=None):
+    """pdse_spec_frames_mode (include/pdse.h: pdse_spec_frames with the decompress mode of a feat_type, csrc/valid.hip)."""
+    lib = load()
+    with _on(device):
+        check(lib.pdse_spec_frames_mode(spec, basis, frames, int(B), int(T), int(F), int(mode), C.c_void_p(stream)),
+              "pdse_spec_frames_mode")
 
 
 def objective_noise(label, init, noise, t, a_tab, s_tab, noisy, target, maxbuf, B, T, F, mode=0, sigma=0, stream=0, device=None):

@@ -178,6 +178,10 @@ int pdse_spec_losses(const float* esti, const float* label, const int32_t* frame
 int pdse_spec_frames(const float* spec, const double* basis, float* frames, int32_t B, int32_t T, int32_t F, pdse_stream_t s) {
   return pdse_spec_frames_launch(spec, basis, frames, B, T, F, (hipStream_t)s);
 }
+int pdse_spec_frames_mode(const float* spec, const double* basis, float* frames, int32_t B, int32_t T, int32_t F, int32_t mode,
+                          pdse_stream_t s) {
+  return pdse_spec_frames_mode_launch(spec, basis, frames, B, T, F, mode, (hipStream_t)s);
+}
 
 // the denoising objective's forward noising and --sigma loss (csrc/objective.hip): plain arguments, outside the operator table
 int pdse_objective_noise(const float* label, const float* init, const float* noise, const int32_t* t, const float* a_tab,

@@ -1,5 +1,5 @@
 // misc.hip — the HBM-bound and small kernels around the convolution stack:
-// diffusion-step embedding, reverse-step update, sqrt/square companding, waveform
+// diffusion-step embedding, reverse-step update, spectral companding (feat_type), waveform
 // front-end, overlap-add back-end, --sigma mask, LayerNorm.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -151,7 +151,31 @@ int pdse_ew_launch(const pdse_ew_desc* d, hipStream_t s) {
 // ---------------------------------------------------------------------------------------
 // Companding of [B,2,T,F]: phase kept, magnitude raised to 0.5 (front-end, :931-937) or 2
 // (back-end, :1004-1008).  cos/sin(atan2(im,re)) is evaluated as re/|X|, im/|X| (1,0 at 0).
+// The other feat_type values of the configuration files (:414-435, utils/metrics.py:531-551) are further modes of the same
+// kernel: the mode is a template parameter, so modes 0 and 1 keep their code and no pass pays for a powf / logf / expf it
+// does not use.  PDSE_COMPAND_COPY moves both parts unchanged (the back end of 'normal' and 'none': the ISTFT GEMM still
+// needs its frame-major rows).  A magnitude whose exp() overflows gives a non-finite element: the verdict's business.
 // ---------------------------------------------------------------------------------------
+template <int MODE>
+__device__ __forceinline__ float compand_mag(float mag) {
+#pragma clang fp contract(off)
+  if constexpr (MODE == PDSE_COMPAND_SQRT) return sqrtf(mag);
+  if constexpr (MODE == PDSE_COMPAND_SQUARE) return mag * mag;
+  if constexpr (MODE == PDSE_COMPAND_MAG) return mag;
+  if constexpr (MODE == PDSE_COMPAND_POW03) return powf(mag, 0.3f);
+  if constexpr (MODE == PDSE_COMPAND_POW103) return powf(mag, (float)(10.0 / 3.0));
+  if constexpr (MODE == PDSE_COMPAND_LOG1X) {
+    const float m1 = mag + 1.f;      // the sum rounded to fp32 first, as torch.log(norm + 1) rounds it
+    return logf(m1);
+  }
+  if constexpr (MODE == PDSE_COMPAND_EXPM1) {
+    const float e = expf(mag);
+    return e - 1.f;
+  }
+  return mag;
+}
+
+template <int MODE>
 __global__ __launch_bounds__(256) void compand_kernel(const pdse_compand_desc d) {
   const int64_t total = (int64_t)d.B * d.plane;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -160,33 +184,52 @@ __global__ __launch_bounds__(256) void compand_kernel(const pdse_compand_desc d)
     const int64_t b = i / d.plane, q = i - b * d.plane;
     const int64_t ire = (2 * b) * d.plane + q, iim = ire + d.plane;
     const float re = d.in[ire], im = d.in[iim];
-    const float rr = re * re, ii = im * im;
-    const float mag = sqrtf(rr + ii);
-    float cr = 1.f, sr = 0.f;
-    if (mag > 0.f) {
-      cr = re / mag;
-      sr = im / mag;
+    float o_re, o_im;
+    if constexpr (MODE == PDSE_COMPAND_COPY) {
+      o_re = re;
+      o_im = im;
+    } else {
+      const float rr = re * re, ii = im * im;
+      const float mag = sqrtf(rr + ii);
+      float cr = 1.f, sr = 0.f;
+      if (mag > 0.f) {
+        cr = re / mag;
+        sr = im / mag;
+      }
+      const float m2 = compand_mag<MODE>(mag);
+      o_re = m2 * cr;
+      o_im = m2 * sr;
     }
-    const float m2 = d.mode == 0 ? sqrtf(mag) : mag * mag;
     if (d.F > 0) {
       const int64_t t = q / d.F, f = q - t * d.F;
       float* o = d.out + b * d.out_sb + t * d.out_st + f;
-      o[0] = m2 * cr;
-      o[d.out_sc] = m2 * sr;
+      o[0] = o_re;
+      o[d.out_sc] = o_im;
     } else {
-      d.out[ire] = m2 * cr;
-      d.out[iim] = m2 * sr;
+      d.out[ire] = o_re;
+      d.out[iim] = o_im;
     }
   }
 }
 
 int pdse_compand_launch(const pdse_compand_desc* d, hipStream_t s) {
   REQ(d && d->in && d->out && d->B > 0 && d->plane > 0, "compand: bad descriptor");
-  REQ(d->mode == 0 || d->mode == 1, "compand: mode must be 0 or 1");
+  REQ(d->mode >= PDSE_COMPAND_SQRT && d->mode <= PDSE_COMPAND_EXPM1,
+      "compand: mode must be 0 (mag**0.5), 1 (mag**2), 2 (mag), 3 (copy), 4 (mag**0.3), 5 (mag**(10/3)), 6 (log(mag+1)) or 7 (exp(mag)-1)");
   REQ(d->F >= 0 && (d->F == 0 || d->plane % d->F == 0), "compand: plane must be a multiple of F");
   int64_t blocks = ((int64_t)d->B * d->plane + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(compand_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *d);
+  const dim3 grid((unsigned)blocks), block(256);
+  switch (d->mode) {
+    case PDSE_COMPAND_SQRT: hipLaunchKernelGGL(compand_kernel<PDSE_COMPAND_SQRT>, grid, block, 0, s, *d); break;
+    case PDSE_COMPAND_SQUARE: hipLaunchKernelGGL(compand_kernel<PDSE_COMPAND_SQUARE>, grid, block, 0, s, *d); break;
+    case PDSE_COMPAND_MAG: hipLaunchKernelGGL(compand_kernel<PDSE_COMPAND_MAG>, grid, block, 0, s, *d); break;
+    case PDSE_COMPAND_COPY: hipLaunchKernelGGL(compand_kernel<PDSE_COMPAND_COPY>, grid, block, 0, s, *d); break;
+    case PDSE_COMPAND_POW03: hipLaunchKernelGGL(compand_kernel<PDSE_COMPAND_POW03>, grid, block, 0, s, *d); break;
+    case PDSE_COMPAND_POW103: hipLaunchKernelGGL(compand_kernel<PDSE_COMPAND_POW103>, grid, block, 0, s, *d); break;
+    case PDSE_COMPAND_LOG1X: hipLaunchKernelGGL(compand_kernel<PDSE_COMPAND_LOG1X>, grid, block, 0, s, *d); break;
+    default: hipLaunchKernelGGL(compand_kernel<PDSE_COMPAND_EXPM1>, grid, block, 0, s, *d); break;
+  }
   return pdse_check_launch("compand");
 }
 

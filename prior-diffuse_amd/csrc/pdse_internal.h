@@ -88,6 +88,8 @@ int pdse_pair_prep_launch(const float* noisy, const float* clean, const int32_t*
 int pdse_spec_losses_launch(const float* esti, const float* label, const int32_t* frames_host, const int32_t* frames, double* partial,
                             double* per_utt, float* loss, int32_t B, int32_t T, int32_t F, hipStream_t s);
 int pdse_spec_frames_launch(const float* spec, const double* basis, float* frames, int32_t B, int32_t T, int32_t F, hipStream_t s);
+int pdse_spec_frames_mode_launch(const float* spec, const double* basis, float* frames, int32_t B, int32_t T, int32_t F, int32_t mode,
+                                 hipStream_t s);
 // csrc/objective.hip: the forward noising and the --sigma loss of the denoising objective behind pdse_objective_noise / pdse_sigma_loss (plain arguments too)
 int pdse_objective_noise_launch(const float* label, const float* init, const float* noise, const int32_t* t, const float* a_tab,
                                 const float* s_tab, float* noisy, float* target, float* maxbuf, int32_t B, int32_t T, int32_t F,

@@ -212,6 +212,27 @@ int pdse_spec_losses_launch(const float* esti, const float* label, const int32_t
 #define VF_N 320
 #define VF_ROWS 4
 
+// MODE: the decompress mode of pdse_compand_desc (the other feat_type values, utils/metrics.py:534-551), a template parameter:
+// the sqrt case keeps its code.  COPY takes the spectrogram as it is; POW103 and EXPM1 scale (re, im) by f(m) / m in double.
+template <int MODE>
+__device__ __forceinline__ void spec_decompress(const double re, const double im, double& vr, double& vi) {
+  if constexpr (MODE == PDSE_COMPAND_COPY) {
+    vr = re;
+    vi = im;
+  } else {
+    const double mag = sqrt(re * re + im * im);
+    if constexpr (MODE == PDSE_COMPAND_SQUARE) {
+      vr = mag * re;   // |X|^2 cos(phase) = |X| re
+      vi = mag * im;
+    } else {
+      const double g = MODE == PDSE_COMPAND_POW103 ? pow(mag, 10.0 / 3.0) : exp(mag) - 1.0;
+      vr = mag > 0.0 ? g * (re / mag) : 0.0;     // f(0) = 0 for both
+      vi = mag > 0.0 ? g * (im / mag) : 0.0;
+    }
+  }
+}
+
+template <int MODE>
 __global__ __launch_bounds__(VF_N) void spec_frames_kernel(const float* __restrict__ spec, const double* __restrict__ basis,
                                                            float* __restrict__ frames, const int T) {
   __shared__ double dec[VF_ROWS][2 * VF_F];
@@ -224,9 +245,7 @@ __global__ __launch_bounds__(VF_N) void spec_frames_kernel(const float* __restri
     double vr = 0.0, vi = 0.0;
     if (t < T) {
       const double re = (double)re_p[(int64_t)t * VF_F + f], im = (double)im_p[(int64_t)t * VF_F + f];
-      const double mag = sqrt(re * re + im * im);
-      vr = mag * re;   // |X|^2 cos(phase) = |X| re
-      vi = mag * im;
+      spec_decompress<MODE>(re, im, vr, vi);
     }
     dec[row][f] = vr;
     dec[row][VF_F + f] = vi;
@@ -245,10 +264,23 @@ __global__ __launch_bounds__(VF_N) void spec_frames_kernel(const float* __restri
     if (t0 + j < T) frames[((int64_t)b * VF_N + r) * T + t0 + j] = (float)acc[j];
 }
 
-int pdse_spec_frames_launch(const float* spec, const double* basis, float* frames, int32_t B, int32_t T, int32_t F, hipStream_t s) {
+int pdse_spec_frames_mode_launch(const float* spec, const double* basis, float* frames, int32_t B, int32_t T, int32_t F, int32_t mode,
+                                 hipStream_t s) {
   REQ(spec && basis && frames, "spec_frames: null pointer");
   REQ(B > 0 && B <= 65535 && T > 0, "spec_frames: bad sizes (0 < B <= 65535, T > 0)");
   REQ(F == VF_F, "spec_frames: F must be 161 (n_fft 320)");
-  hipLaunchKernelGGL(spec_frames_kernel, dim3((T + VF_ROWS - 1) / VF_ROWS, B), dim3(VF_N), 0, s, spec, basis, frames, T);
+  REQ(mode == PDSE_COMPAND_SQUARE || mode == PDSE_COMPAND_COPY || mode == PDSE_COMPAND_POW103 || mode == PDSE_COMPAND_EXPM1,
+      "spec_frames: mode must be a decompress mode: 1 (mag**2), 3 (copy), 5 (mag**(10/3)) or 7 (exp(mag)-1)");
+  const dim3 grid((T + VF_ROWS - 1) / VF_ROWS, B), block(VF_N);
+  switch (mode) {
+    case PDSE_COMPAND_SQUARE: hipLaunchKernelGGL(spec_frames_kernel<PDSE_COMPAND_SQUARE>, grid, block, 0, s, spec, basis, frames, T); break;
+    case PDSE_COMPAND_COPY: hipLaunchKernelGGL(spec_frames_kernel<PDSE_COMPAND_COPY>, grid, block, 0, s, spec, basis, frames, T); break;
+    case PDSE_COMPAND_POW103: hipLaunchKernelGGL(spec_frames_kernel<PDSE_COMPAND_POW103>, grid, block, 0, s, spec, basis, frames, T); break;
+    default: hipLaunchKernelGGL(spec_frames_kernel<PDSE_COMPAND_EXPM1>, grid, block, 0, s, spec, basis, frames, T); break;
+  }
   return pdse_check_launch("spec_frames");
+}
+
+int pdse_spec_frames_launch(const float* spec, const double* basis, float* frames, int32_t B, int32_t T, int32_t F, hipStream_t s) {
+  return pdse_spec_frames_mode_launch(spec, basis, frames, B, T, F, PDSE_COMPAND_SQUARE, s);
 }

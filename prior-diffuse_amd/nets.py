@@ -1350,14 +1350,22 @@ class GcrnPlan(PlanBase):
 # ==========================================================================
 # signal front / back end
 # ==========================================================================
+def feat_ns(feat_type):
+    """The part of a front / back end's ``ns`` that names its compression: empty for "sqrt", whose key is the one it always had."""
+    return () if feat_type == "sqrt" else (feat_type,)
+
+
 class StftPlan(PlanBase):
     """wav [B,L] -> c [B], compressed spectrogram [B,2,T,161]
-    (trainer/complex_ddpm_trainer.py:921-937)."""
+    (trainer/complex_ddpm_trainer.py:921-937; the compressions beside the square root: :414-435)."""
 
-    def __init__(self, ctx, B, L_, plan=None, normalize=True, split_bf16=False, reflect_own=False):
+    def __init__(self, ctx, B, L_, plan=None, normalize=True, split_bf16=False, reflect_own=False, feat_type="sqrt"):
         """split_bf16: the framing GEMM on the bf16 matrix cores with exact three-way operand splits (csrc/gconv4.hip).
-        reflect_own: exact ragged batches - the right-hand reflect padding sits at every utterance's own end (``lens``)."""
-        super().__init__(ctx, plan, ns=("stft", bool(split_bf16)))
+        reflect_own: exact ragged batches - the right-hand reflect padding sits at every utterance's own end (``lens``).
+        feat_type: the compression of the magnitude behind the framing GEMM, one of ``L.FEAT_TYPES`` (``L.COMPRESS_MODE``);
+        "none" records no compand launch: the raw STFT."""
+        self.feat_type = L.feat_type_of(feat_type)
+        super().__init__(ctx, plan, ns=("stft", bool(split_bf16)) + feat_ns(feat_type))
         self.split_bf16 = bool(split_bf16)
         if L_ <= 160:
             raise ValueError(f"utterance of {L_} samples: the centred STFT reflects 160 samples on each side (torch.stft "
@@ -1391,20 +1399,25 @@ class StftPlan(PlanBase):
                    sf_in=160, W=lambda: dict(wk0=P.stft_kmat(320)), Cout=2 * F0, out=feat, label="stft",
                    out_strides=(2 * T * F0, T * F0, 1, 0, F0), out_cr=F0, B=B, Tout=1, Fout=T, tag=TAG_SIGNAL,
                    s3g=self.split_bf16)
-        c = L.CompandDesc()
-        c.in_, c.out, c.plane, c.B, c.mode = feat.data_ptr(), feat.data_ptr(), T * F0, B, 0
-        self.add(c, TAG_SIGNAL)
+        mode = L.COMPRESS_MODE[self.feat_type]
+        if mode is not None:
+            c = L.CompandDesc()
+            c.in_, c.out, c.plane, c.B, c.mode = feat.data_ptr(), feat.data_ptr(), T * F0, B, mode
+            self.add(c, TAG_SIGNAL)
         return feat
 
 
 class IstftPlan(PlanBase):
     """compressed spectrogram [B,2,T,161] -> wav [B,L] * c
-    (trainer/complex_ddpm_trainer.py:1004-1016)."""
+    (trainer/complex_ddpm_trainer.py:1004-1016; the decompressions beside the square: utils/metrics.py:534-551)."""
 
-    def __init__(self, ctx, B, T, L_, plan=None, split_bf16=False, frames=None, lens=None):
+    def __init__(self, ctx, B, T, L_, plan=None, split_bf16=False, frames=None, lens=None, feat_type="sqrt"):
         """frames, lens: device int32 [B] owned by the caller (exact ragged batches): the overlap-add takes an utterance's own
-        frames only and writes zeros behind its own samples."""
-        super().__init__(ctx, plan, ns=("istft", bool(split_bf16)))
+        frames only and writes zeros behind its own samples.
+        feat_type: the decompression in front of the GEMM, one of ``L.FEAT_TYPES`` (``L.DECOMPRESS_MODE``); "normal" and "none"
+        record the copy mode: nothing is decompressed, but the GEMM reads the frame-major rows the launch writes."""
+        self.feat_type = L.feat_type_of(feat_type)
+        super().__init__(ctx, plan, ns=("istft", bool(split_bf16)) + feat_ns(feat_type))
         self.frames_tab, self.lens_tab = frames, lens
         self.split_bf16 = bool(split_bf16)
         self.B, self.T, self.L = B, T, L_
@@ -1419,7 +1432,7 @@ class IstftPlan(PlanBase):
         B, T = self.B, self.T
         spec = self.spec if spec is None else spec
         cd = L.CompandDesc()
-        cd.in_, cd.out, cd.plane, cd.B, cd.mode = spec.data_ptr(), self.dec.data_ptr(), T * F0, B, 1
+        cd.in_, cd.out, cd.plane, cd.B, cd.mode = spec.data_ptr(), self.dec.data_ptr(), T * F0, B, L.DECOMPRESS_MODE[self.feat_type]
         K = 2 * P.ISTFT_ROW
         cd.out_sb, cd.out_sc, cd.out_st, cd.F = T * K, P.ISTFT_ROW, K, F0
         self.add(cd, TAG_SIGNAL)

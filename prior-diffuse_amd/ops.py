@@ -403,14 +403,44 @@ def spec_losses(esti, label, frame_list):
     return {"com_mse": loss[0], "mag_mse": loss[1], "com_mag_mse": loss[2], "per_utt": per_utt}
 
 
-_LABEL_PLANS = OrderedDict()     # (device, B, L, reflect_own) -> (context, plan, front end) of label_spec; a few geometries
+def _compand(spec, mode, what):
+    if spec.device.type != "cuda":
+        raise L.PdseError("%s runs on the GPU only (no CPU fallback)" % what)
+    if spec.dim() != 4 or spec.shape[1] != 2 or spec.dtype != torch.float32 or spec.numel() == 0:
+        raise ValueError("spec: an fp32 [B,2,T,F] tensor")
+    spec = spec.contiguous()
+    out = torch.empty_like(spec)
+    d = L.CompandDesc()
+    d.in_, d.out, d.plane, d.B, d.mode = spec.data_ptr(), out.data_ptr(), spec.shape[2] * spec.shape[3], spec.shape[0], mode
+    L.launch(d, torch.cuda.current_stream(spec.device).cuda_stream, device=spec.device)
+    return out
 
 
-def label_spec(noisy, clean, lens=None, reflect_own=False):
+def compress(spec, feat_type="sqrt"):
+    """The front end's compression of a complex spectrogram, fp32 [B,2,T,161] -> a new tensor of that shape: the magnitude m = |X|
+    through ``feat_type`` with the phase kept (trainer/complex_ddpm_trainer.py:414-435) - "sqrt" m ** 0.5, "normal" m (re-stacked
+    through the phase), "cubic" m ** 0.3, "log_1x" log(m + 1), "none" the spectrogram as it is; any other string: ValueError.
+    cos / sin of the phase are re / m, im / m with (1, 0) at m == 0.  One launch of the compand operator (csrc/misc.hip,
+    include/pdse.h: pdse_compand_desc), the copy mode for "none".  GPU only, no host synchronisation."""
+    mode = L.COMPRESS_MODE[L.feat_type_of(feat_type)]
+    return _compand(spec, L.COMPAND_COPY if mode is None else mode, "compress")
+
+
+def decompress(spec, feat_type="sqrt"):
+    """The back end's decompression, the inverse of ``compress`` (utils/metrics.py:531-551): "sqrt" m ** 2, "cubic" m ** (10 / 3),
+    "log_1x" exp(m) - 1 (beyond the fp32 range: non-finite, nothing is clamped), "normal" and "none" the spectrogram as it is.
+    fp32 [B,2,T,161] -> a new tensor of that shape.  GPU only, no host synchronisation."""
+    return _compand(spec, L.DECOMPRESS_MODE[L.feat_type_of(feat_type)], "decompress")
+
+
+_LABEL_PLANS = OrderedDict()     # (device, B, L, reflect_own, feat_type) -> (context, plan, front end) of label_spec; a few geometries
+
+
+def label_spec(noisy, clean, lens=None, reflect_own=False, feat_type="sqrt"):
     """The label of a validation batch, on the device: noisy, clean fp32 [B,L] (zero-padded utterance pairs), lens the
     utterances' own lengths (host integers; None: every utterance spans L) -> (label [B,2,T,161], c [B]).  Collate.collate_fn
     (utils/dataset.py:45-74) scales the clean utterance by the NOISY utterance's c and takes the STFT of the padded batch; the
-    validation loop sqrt-compresses it (trainer/complex_ddpm_trainer.py:414-435).  Here: pdse_pair_prep (csrc/valid.hip), then
+    validation loop compresses it as ``feat_type`` says (trainer/complex_ddpm_trainer.py:414-435; ``compress``).  Here: pdse_pair_prep (csrc/valid.hip), then
     the framing GEMM and the compression of the sampling path's front end on the clean rows.  c is this package's
     sqrt(sum x^2 / len), the divisor (the reference multiplies by its reciprocal).  reflect_own: reflect at every utterance's
     own end, the convention of exact ragged batches.  No host synchronisation; a (B, L) records its small plan once."""
@@ -420,13 +450,13 @@ def label_spec(noisy, clean, lens=None, reflect_own=False):
         raise ValueError("noisy, clean: fp32 tensors of one [B,L] shape")
     B, L_ = noisy.shape
     dev = noisy.device
-    key = (str(dev), B, L_, bool(reflect_own))
+    key = _label_key(dev, B, L_, reflect_own, feat_type)
     hit = _LABEL_PLANS.get(key)
     if hit is None:
         while len(_LABEL_PLANS) >= 3:
             _LABEL_PLANS.popitem(last=False)
         ctx = nets.Ctx(dev)
-        st = nets.StftPlan(ctx, B, L_, reflect_own=reflect_own)
+        st = nets.StftPlan(ctx, B, L_, reflect_own=reflect_own, feat_type=feat_type)
         st.build(prep=False)
         st.finish()
         hit = _LABEL_PLANS[key] = (ctx, st, ctx.alloc(B, L_ + 320))
@@ -448,6 +478,11 @@ def label_spec(noisy, clean, lens=None, reflect_own=False):
     return st.feat.clone(), st.c.clone()
 
 
+def _label_key(dev, B, L_, reflect_own, feat_type):
+    """The key of a label_spec plan in _LABEL_PLANS: two compressions never share a recorded plan."""
+    return (str(dev), B, L_, bool(reflect_own), L.feat_type_of(feat_type))
+
+
 _FRAME_TABLES = {}      # device -> (basis [322, 320] float64, win2 [320] fp32) of spec_to_wav and the label leg
 
 
@@ -467,12 +502,14 @@ def frame_tables(device):
     return _FRAME_TABLES[key]
 
 
-def spec_to_wav(spec):
+def spec_to_wav(spec, feat_type="sqrt"):
     """Compressed spectrogram fp32 [B,2,T,161] -> waveforms [B, (T - 1) * 160] in the normalised domain, as the quality measures
     compare them (utils/metrics.py:531-561: magnitude squared with the phase kept, torch.istft): pdse_spec_frames - decompression
     and windowed inverse DFT in double, frames rounded to fp32 once (csrc/valid.hip) - then the path's overlap-add operator without
-    the rescale by c.  The waveforms of a validation pass (``SamplerPipeline(label=True)``) are made the same way.  No host
+    the rescale by c.  feat_type: the decompression, as in ``decompress`` (utils/metrics.py:534-551; pdse_spec_frames_mode for a
+    value other than "sqrt").  The waveforms of a validation pass (``SamplerPipeline(label=True)``) are made the same way.  No host
     synchronisation."""
+    mode = L.DECOMPRESS_MODE[L.feat_type_of(feat_type)]
     if spec.device.type != "cuda":
         raise L.PdseError("spec_to_wav runs on the GPU only (no CPU fallback)")
     if spec.dim() != 4 or spec.shape[1] != 2 or spec.shape[3] != nets.F0 or spec.dtype != torch.float32 or spec.shape[2] < 2:
@@ -484,7 +521,10 @@ def spec_to_wav(spec):
     frames = torch.empty(B, 320, T, dtype=torch.float32, device=dev)
     wav = torch.empty(B, L_, dtype=torch.float32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    L.spec_frames(spec.data_ptr(), basis.data_ptr(), frames.data_ptr(), B, T, nets.F0, stream, device=dev)
+    if mode == L.COMPAND_SQUARE:
+        L.spec_frames(spec.data_ptr(), basis.data_ptr(), frames.data_ptr(), B, T, nets.F0, stream, device=dev)
+    else:
+        L.spec_frames_mode(spec.data_ptr(), basis.data_ptr(), frames.data_ptr(), B, T, nets.F0, mode, stream, device=dev)
     o = L.OlaDesc()
     o.frames, o.win2, o.c, o.out = frames.data_ptr(), win2.data_ptr(), 0, wav.data_ptr()
     o.B, o.T, o.L, o.n_fft, o.hop = B, T, L_, 320, 160

@@ -62,7 +62,7 @@ class SamplerPipeline:
     def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, T=None, L_=None, fast_sampling=True,
                  use_sigma=False, params=default_params, with_signal=None, deltamu=False, cond="init", bank=None,
                  split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False, ragged=False,
-                 verdict=False, masked_prior=False, label=False, objective=False):
+                 verdict=False, masked_prior=False, label=False, objective=False, feat_type="sqrt"):
         """deltamu: the alternative parameterisation of utils/params.py:36 — ddpm_sd is a ``Nocon`` state_dict,
         x_T = noise + X_init/11 (:947-948), eps = Nocon(x, t) (:970-971), no final ``+ X_init`` (:995).
         cond (deltamu False): what conditions DiffUNet1 — "init": X_init/11 (pirorgrad, :967-969, + X_init at the end,
@@ -135,8 +135,17 @@ class SamplerPipeline:
         ISTFT.  ``spec`` is then the eps-net's prediction, which ``check()`` judges.  The parameterisation follows ``deltamu`` and
         ``cond`` as trainer/complex_ddpm_trainer.py:726-733 reads them: DiffUNet1(noisy, init, t), Nocon(noisy, t), or
         DiffUNet1(noisy, feat, t) with feat NOT divided by 11 (:701 is commented out).  Padded batches only (``ragged``:
-        ValueError); no verdict."""
+        ValueError); no verdict.
+        feat_type: the spectral compression around the networks, the ``feat_type`` of the reference's configuration files -
+        "sqrt" (default), "normal", "cubic", "log_1x" or "none" (include/pdse.h: pdse_compand_desc; any other string:
+        ValueError).  The front end and the label leg compress with it, the back end and the label leg's scored waveforms
+        decompress with it; the prior, the eps-net, X_init / 11, the sigma mask, the losses and the objective's noising work in
+        the compressed domain whatever it is, so nothing else changes.  "sqrt" records, launch for launch and field for field,
+        the plan it always recorded.  The fp16 window of the f16x2 split was audited on sqrt-compressed activations only:
+        "normal" and "none" feed the networks magnitudes one to two orders above those, and a pass that leaves the window shows
+        in the verdict / ``check()`` as before."""
         objective = bool(objective)
+        self.feat_type = L.feat_type_of(feat_type)
         if objective and (L_ is None or ragged or verdict):
             raise ValueError("the objective plan needs the signal front end (pass L_) and is built for padded batches, without the verdict")
         if L_ is not None:
@@ -190,7 +199,8 @@ class SamplerPipeline:
             self.frames_tab = torch.full((B,), T, dtype=torch.int32, device=self.device)
             self.valid_tab = torch.full((2 * B,), T * F0, dtype=torch.int32, device=self.device)
             ctx.keep += [self.frames_tab, self.valid_tab]
-        self.stft = adopt(nets.StftPlan(ctx, B, L_, plan=self.plan, split_bf16=split_bf16, reflect_own=self.ragged)) if with_signal else None
+        self.stft = adopt(nets.StftPlan(ctx, B, L_, plan=self.plan, split_bf16=split_bf16, reflect_own=self.ragged,
+                                        feat_type=self.feat_type)) if with_signal else None
         # operand planes of the matrix-core kernels (csrc/planes.h): 1 = plain bf16 (the bf16 mode), 2 = f16x2, 3 = bf16x3
         nplanes = 1 if dtype == "bf16" else (2 if split == "f16x2" else 3)
         # the priors' GEMM-shaped convolutions (csrc/gconv4.hip: korder 4 / 5 / 3) and DB-AIAT's dense blocks (np); None: their fp32 kernels
@@ -222,7 +232,8 @@ class SamplerPipeline:
         self.xT_plus_init = xT_plus_init = bool(deltamu if xT_plus_init is None else xT_plus_init)
         self.cond_feat = cond_feat = (cond == "feat") and not deltamu
         self.istft = adopt(nets.IstftPlan(ctx, B, T, L_, plan=self.plan, split_bf16=split_bf16, frames=self.frames_tab,
-                                          lens=self.stft.lens if self.ragged else None)) if with_signal and not objective else None
+                                          lens=self.stft.lens if self.ragged else None,
+                                          feat_type=self.feat_type)) if with_signal and not objective else None
 
         self.feat = self.prior.x                     # prior input = compressed spectrogram
         # X_init / 11: the eps-net's conditioning input only in the pirorgrad parameterisation
@@ -618,8 +629,8 @@ class LabelLeg:
         prepare   pdse_pair_prep (csrc/valid.hip; a plain-argument call, not recordable): the noisy rows' c, both rows / c,
                   reflect-padded.  The noisy outputs go where the pipeline's own wavprep launch writes the same bits (its
                   ``stft.xpad``, ``stft.c``); the clean rows into this leg's STFT input.
-        front     (plan) STFT GEMM + sqrt-compression of the clean rows -> ``spec`` (the label).
-        frames    pdse_spec_frames (csrc/valid.hip, plain arguments) on the label, on the prior's output and on the final
+        front     (plan) STFT GEMM + compression (the pipeline's ``feat_type``) of the clean rows -> ``spec`` (the label).
+        frames    pdse_spec_frames (pdse_spec_frames_mode for a feat_type other than "sqrt"; csrc/valid.hip, plain arguments) on the label, on the prior's output and on the final
                   spectrogram: decompression and windowed inverse DFT in double, frames rounded to fp32 once.
         back      (plan) the overlap-add operator on the three frame tensors, without the rescale by c -> ``wav`` (label),
                   ``init_wav``, ``est_wav``.
@@ -636,7 +647,8 @@ class LabelLeg:
         ctx, B, T, L_ = pipe.ctx, pipe.B, pipe.T, pipe.L
         self.pipe = pipe
         self.plan = L.Plan(pipe.device)
-        self.stft = nets.StftPlan(ctx, B, L_, plan=self.plan, split_bf16=pipe.stft.split_bf16, reflect_own=pipe.ragged)
+        self.stft = nets.StftPlan(ctx, B, L_, plan=self.plan, split_bf16=pipe.stft.split_bf16, reflect_own=pipe.ragged,
+                                  feat_type=pipe.feat_type)
         self.clean, self.spec = self.stft.wav, self.stft.feat
         self.stft.build(prep=False)
         self.plan.keep(ctx.keep, ctx.bank)
@@ -668,8 +680,13 @@ class LabelLeg:
     def run(self, stream):
         pipe = self.pipe
         self.plan.run(stream)
+        mode = L.DECOMPRESS_MODE[pipe.feat_type]
         for spec, fr in zip((self.spec, pipe.prior.out, pipe.spec), self.frames):
-            L.spec_frames(spec.data_ptr(), self.basis.data_ptr(), fr.data_ptr(), pipe.B, pipe.T, F0, stream, device=pipe.device)
+            if mode == L.COMPAND_SQUARE:
+                L.spec_frames(spec.data_ptr(), self.basis.data_ptr(), fr.data_ptr(), pipe.B, pipe.T, F0, stream, device=pipe.device)
+            else:
+                L.spec_frames_mode(spec.data_ptr(), self.basis.data_ptr(), fr.data_ptr(), pipe.B, pipe.T, F0, mode, stream,
+                                   device=pipe.device)
         self.back.plan.run(stream)
 
 

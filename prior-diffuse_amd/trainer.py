@@ -81,7 +81,11 @@ class ComplexDDPMTrainer(object):
     def __init__(self, args, config, device=None, prior_state_dict=None, ddpm_state_dict=None, params=None, exclusive=None,
                  dtype=None, split=None, audit=None, masked_prior=None, wav_formats=None, wav_out=None, channels=None):
         """args: .retrain .joint .draw .sigma .checkpoint .generated_wav
-        config: .model.name, .train.{fft_num, win_size, win_shift, feat_type}
+        config: .model.name, .train.{fft_num, win_size, win_shift, feat_type}.  feat_type: the spectral compression the
+        checkpoint was trained with - "sqrt", "normal", "cubic", "log_1x" or "none" (``SamplerPipeline(feat_type=...)``; any other
+        string: ValueError).  Every entry point honours it without an argument of its own: the front end and the label leg
+        compress with it, the back end and the scored waveforms decompress with it, everything between them works in the
+        compressed domain whatever it is.
         Weights come from ``<args.checkpoint>/best_checkpoint.pth`` under the reference's
         rules (:91-97) or from the two state_dict arguments (synthetic runs).
         exclusive: this trainer is the only work on its GPU (the reference's situation: one process, one batch at a
@@ -179,8 +183,10 @@ class ComplexDDPMTrainer(object):
         self.xT_plus_init = bool(self.params.deltamu)
         self.cond = "init" if (self.pirorgrad or self.deltamu) else "feat"
         tr = self.config.train
-        if (tr.fft_num, tr.win_size, tr.win_shift) != (320, 320, 160) or tr.feat_type != "sqrt":
-            raise NotImplementedError("STFT 320/320/160 with feat_type 'sqrt' is baked into every model of the path")
+        if (tr.fft_num, tr.win_size, tr.win_shift) != (320, 320, 160):
+            raise NotImplementedError("STFT 320/320/160 is baked into every model of the path")
+        # the spectral compression around the networks (:414-435, utils/metrics.py:534-551): one of L.FEAT_TYPES, else ValueError
+        self.feat_type = L.feat_type_of(tr.feat_type)
         if device is None:
             rank = int(os.environ.get("LOCAL_RANK", "0"))
             device = "cuda:%d" % rank
@@ -237,7 +243,8 @@ class ComplexDDPMTrainer(object):
     def _key(self, B, T=None, L_=None, ragged=False, label=False, objective=False):
         """The key of a geometry in the plan caches and in ``_range_fallback`` / ``_audit_clean``."""
         return ((B, T, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling)) + ((True,) if ragged else ())
-                + (("label",) if label else ()) + (("objective",) if objective else ()))
+                + (("label",) if label else ()) + (("objective",) if objective else ())
+                + ((self.feat_type,) if self.feat_type != "sqrt" else ()))       # a trainer has one; the key names it all the same
 
     def _split_of(self, key, split):
         """The operand split a plan of the geometry ``key`` is built with, where ``split`` is what it was asked for."""
@@ -249,7 +256,8 @@ class ComplexDDPMTrainer(object):
         return SamplerPipeline(
             self.device, self.prior_name, self.prior_sd, self.ddpm_sd, key[0], T=key[1], L_=key[2],
             fast_sampling=self.params.fast_sampling, use_sigma=key[3], params=self.params, deltamu=self.deltamu,
-            cond=self.cond, bank=self.bank, xT_plus_init=self.xT_plus_init, dtype=self.dtype, split=split, **kw)
+            cond=self.cond, bank=self.bank, xT_plus_init=self.xT_plus_init, dtype=self.dtype, split=split,
+            feat_type=self.feat_type, **kw)
 
     def _plan(self, **geom):
         """-> (plan, key, met_before) of one geometry (``_key``'s arguments).  ``generate_wav`` meets a new utterance length
@@ -546,6 +554,10 @@ class ComplexDDPMTrainer(object):
     def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True, batch=1, inflight=1):
         """Per-file B=1 enhancement of ``data_path/*.wav`` into ``args.generated_wav``
         (:903-1018).  Returns the list of written paths instead of calling exit().
+
+        feat_type: the reference's own generate_wav defines its compressed magnitude for "sqrt" only and stops with a NameError
+        for every other value; for those this method follows the statements of the validation loop (:414-435 to compress,
+        utils/metrics.py:534-551 to decompress), as every other entry point does.
 
         One loop (``_file_loop``) serves the three modes: the sorted paths are read, every readable file's x_T is drawn in path
         order at its own shape and followed at once by its ``rng_fidelity`` discards, the files are enhanced, and the results
