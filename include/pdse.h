@@ -1263,6 +1263,32 @@ int pdse_sigma_loss(const float* predicted,       /* device [B][2][T][F] */
                     float* loss,                  /* device [1] */
                     int32_t B, int32_t T, int32_t F, pdse_stream_t s);
 
+/* Posterior ensembles (csrc/ensemble.hip, additive within ABI 9; plain arguments): the statistics of K reverse trajectories of the
+ * same B utterances.  members is member-major, [K][B][2][T][F] fp32: member k of utterance b is row k B + b, so every member is an
+ * ordinary [B][2][T][F] tensor.  Everything is validated before the launch and without a device: null pointers, 1 <= K <=
+ * PDSE_ENSEMBLE_MAX, 1 <= B <= 65535, T >= 1, F >= 1, 0 <= frames_host[b] <= T (frames_host is the host copy of frames, read by the
+ * call itself; a batch without a frame is allowed: its sums are zeros).
+ * Per element e of [B][2][T][F]: the K fp32 values are added in double in member order k = 0 .. K-1 and divided by K in double - the
+ * double mean; mean[e] is that, rounded to fp32 once.  Per bin (b, t, f): d_k = x_k - the double mean over re and im, in double, and
+ *   spread[b][t][f] = (float) sqrt(sum_k |d_k|^2 / (K - 1)),  the sample standard deviation of the complex bin; 0 for K = 1.
+ * Every element of mean and spread is written, padding frames included.  Over the frames t < frames[b] of utterance b only:
+ *   per_utt[b][0] = sum_bins sum_k |d_k|^2,   per_utt[b][1] = sum_bins |double mean|^2,   per_member[k][b] = sum_bins |d_k|^2.
+ * The sums are double and added in a fixed order, as the masked losses above add theirs: thread, shuffle tree, the waves of a
+ * workgroup in index order, PDSE_ENSEMBLE_BLOCKS partials per utterance, one thread per sum over the partials in index order.  No
+ * atomics: two calls give the same bits.  partial: scratch of B * PDSE_ENSEMBLE_BLOCKS * (K + 2) doubles.  Each member element is
+ * read once: K n reads against 1.5 n writes. */
+#define PDSE_ENSEMBLE_MAX 16
+#define PDSE_ENSEMBLE_BLOCKS 32
+int pdse_ensemble_stats(const float* members,         /* device [K][B][2][T][F] */
+                        float* mean,                  /* device [B][2][T][F] */
+                        float* spread,                /* device [B][T][F] */
+                        const int32_t* frames_host,   /* host [B] */
+                        const int32_t* frames,        /* device [B] */
+                        double* partial,              /* device [B][PDSE_ENSEMBLE_BLOCKS][K + 2] */
+                        double* per_utt,              /* device [B][2] */
+                        double* per_member,           /* device [K][B] */
+                        int32_t K, int32_t B, int32_t T, int32_t F, pdse_stream_t s);
+
 /* plans: a recorded operator sequence replayed by one call (and capturable in a hipGraph) */
 typedef struct pdse_plan pdse_plan;
 int pdse_plan_create(pdse_plan** out);

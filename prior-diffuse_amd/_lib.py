@@ -21,6 +21,8 @@ EW_DIV, EW_UPDATE, EW_UPDATE_FINAL, EW_COPY, EW_ADD_MUL = 0, 1, 2, 3, 4
 MASKLOSS_BLOCKS = 32
 SPECLOSS_BLOCKS = 32      # PDSE_SPECLOSS_BLOCKS: workgroups per utterance of pdse_spec_losses (partial [B][32][2] doubles)
 
+ENSEMBLE_BLOCKS = 32      # PDSE_ENSEMBLE_BLOCKS: workgroups per utterance of pdse_ensemble_stats (partial [B][32][K + 2] doubles)
+ENSEMBLE_MAX = 16         # PDSE_ENSEMBLE_MAX: members of a posterior ensemble (a thread of pdse_ensemble_stats holds K values in registers)
 _fp = C.c_void_p  # device pointers travel as integers
 _i32, _i64, _f32 = C.c_int32, C.c_int64, C.c_float
 
@@ -87,6 +89,14 @@ def feat_type_of(value):
     if value not in FEAT_TYPES:
         raise ValueError("feat_type %r: must be one of 'sqrt', 'normal', 'cubic', 'log_1x', 'none'" % (value,))
     return value
+
+
+def members_arg(members):
+    """``members`` of the ensemble entry points as an int in 1 .. ENSEMBLE_MAX; anything else: ValueError.  Host only."""
+    if isinstance(members, bool) or not isinstance(members, int) or not 1 <= members <= ENSEMBLE_MAX:
+        raise ValueError("members must be an integer in 1 .. %d (pdse_ensemble_stats holds a bin's members in registers), got %r"
+                         % (ENSEMBLE_MAX, members))
+    return members
 
 
 class WavprepDesc(C.Structure):
@@ -374,7 +384,7 @@ EXPORTS = [
     "pdse_plan_destroy", "pdse_plan_load", "pdse_plan_region", "pdse_prior_forward", "pdse_eps_forward", "pdse_enhance",
     "pdse_wav_encode", "pdse_wav_encode_channels", "pdse_pair_prep", "pdse_spec_losses", "pdse_spec_frames",
     "pdse_spec_frames_mode",
-    "pdse_objective_noise", "pdse_sigma_loss",
+    "pdse_objective_noise", "pdse_sigma_loss", "pdse_ensemble_stats",
 ] + [name for _, _, name in OPS]
 
 
@@ -446,6 +456,8 @@ def load():
     lib.pdse_objective_noise.restype = C.c_int
     lib.pdse_sigma_loss.argtypes = [_fp] * 9 + [_i32] * 3 + [C.c_void_p]
     lib.pdse_sigma_loss.restype = C.c_int
+    lib.pdse_ensemble_stats.argtypes = [_fp] * 8 + [_i32] * 4 + [C.c_void_p]
+    lib.pdse_ensemble_stats.restype = C.c_int
     if lib.pdse_abi_version() != ABI_VERSION:
         raise PdseError("libpdse.so ABI %d != binding ABI %d" % (lib.pdse_abi_version(), ABI_VERSION))
     for kind, typ in DESC_TYPES.items():
@@ -547,6 +559,14 @@ def sigma_loss(predicted, target, init, maxbuf, frames_host, frames, partial, pe
     with _on(device):
         check(lib.pdse_sigma_loss(predicted, target, init, maxbuf, frames_host, frames, partial, per_utt, loss, int(B), int(T), int(F),
                                   C.c_void_p(stream)), "pdse_sigma_loss")
+
+
+def ensemble_stats(members, mean, spread, frames_host, frames, partial, per_utt, per_member, K, B, T, F, stream=0, device=None):
+    """pdse_ensemble_stats (include/pdse.h: mean, spread and sums of a member-major ensemble, csrc/ensemble.hip): pointers as integers."""
+    lib = load()
+    with _on(device):
+        check(lib.pdse_ensemble_stats(members, mean, spread, frames_host, frames, partial, per_utt, per_member, int(K), int(B), int(T),
+                                      int(F), C.c_void_p(stream)), "pdse_ensemble_stats")
 
 
 class Plan:

@@ -196,6 +196,13 @@ int pdse_sigma_loss(const float* predicted, const float* target, const float* in
   return pdse_sigma_loss_launch(predicted, target, init, maxbuf, frames_host, frames, partial, per_utt, loss, B, T, F, (hipStream_t)s);
 }
 
+// the statistics of a posterior ensemble (csrc/ensemble.hip): plain arguments, outside the operator table
+int pdse_ensemble_stats(const float* members, float* mean, float* spread, const int32_t* frames_host, const int32_t* frames,
+                        double* partial, double* per_utt, double* per_member, int32_t K, int32_t B, int32_t T, int32_t F,
+                        pdse_stream_t s) {
+  return pdse_ensemble_stats_launch(members, mean, spread, frames_host, frames, partial, per_utt, per_member, K, B, T, F, (hipStream_t)s);
+}
+
 int pdse_plan_create(pdse_plan** out) {
   if (!out) {
     pdse_set_error("plan_create: null out");

@@ -97,5 +97,9 @@ int pdse_objective_noise_launch(const float* label, const float* init, const flo
 int pdse_sigma_loss_launch(const float* predicted, const float* target, const float* init, const float* maxbuf,
                            const int32_t* frames_host, const int32_t* frames, double* partial, double* per_utt, float* loss, int32_t B,
                            int32_t T, int32_t F, hipStream_t s);
+// csrc/ensemble.hip: the statistics of a posterior ensemble behind pdse_ensemble_stats (plain arguments too)
+int pdse_ensemble_stats_launch(const float* members, float* mean, float* spread, const int32_t* frames_host, const int32_t* frames,
+                               double* partial, double* per_utt, double* per_member, int32_t K, int32_t B, int32_t T, int32_t F,
+                               hipStream_t s);
 int pdse_range_validate(const pdse_range_desc* d);               /* reads the row table back and checks it (direct launches, plan_add) */
 #endif

@@ -9,6 +9,8 @@
 ``<assets>/log/<doc>/eval.json``; with ``--generate`` the generation runs, as the reference tests ``generate`` first (:97).
 ``--eval --objective`` runs one epoch of the denoising objective instead (``ComplexDDPMTrainer.objective``: the eps-net's loss
 on the held-out pairs, by diffusion step) and writes ``<assets>/log/<doc>/objective.json``.
+``--members K`` makes either a posterior ensemble: ``--generate`` writes every file from the mean of K reverse trajectories and
+``<assets>/log/<doc>/ensemble.json``, ``--eval`` scores the mean and adds the members' losses to ``eval.json``.
 """
 import argparse
 import logging
@@ -80,6 +82,12 @@ def parse_args_and_config(argv=None):
     p.add_argument("--draws", type=int, default=1,
                    help="(not a flag of the reference) --eval --objective: evaluate every batch this many times, each with a fresh "
                         "diffusion step per utterance and fresh noise; default 1")
+    p.add_argument("--members", type=int, default=1,
+                   help="(not a flag of the reference) a posterior ensemble: this many (2 .. 16) reverse trajectories per utterance behind "
+                        "one pass of the front end and the prior.  --generate: every file is written from the ensemble mean and "
+                        "ensemble.json holds its relative spread and medoid member; --eval: the mean is scored and eval.json gains "
+                        "the members' losses and the spread; not with --batch (--generate), --inflight, --per-channel, --audit-range "
+                        "or --objective; default 1: one trajectory")
     args = p.parse_args(argv)
     if args.objective and not args.eval:
         p.error("--objective evaluates a held-out set: it needs --eval")
@@ -88,6 +96,15 @@ def parse_args_and_config(argv=None):
     import sys
 
     given = sys.argv[1:] if argv is None else list(argv)
+    if not 1 <= args.members <= 16:
+        p.error("--members must be 1 .. 16")
+    if args.members > 1:
+        if args.objective:
+            p.error("--objective --members: the objective plan runs one eps-net step, not a sampler to draw members from")
+        for on, flag in ((args.generate and args.batch > 1, "--batch"), (args.inflight > 1, "--inflight"), (args.per_channel, "--per-channel"),
+                         (args.audit_range, "--audit-range")):
+            if on:
+                p.error("--members with %s: ensembles are built for one file per pass, verified by its own check" % flag)
     # --eval: --batch is the validation batch size where it was given; else config.train.batch_size
     args.eval_batch = args.batch if any(a == "--batch" or a.startswith("--batch=") for a in given) else None
     args.log = os.path.join(args.assets, "log", args.doc)
@@ -117,7 +134,7 @@ def main(argv=None):
         raise NotImplementedError("only ComplexDDPMTrainer's sampling path is built")
     trainer = ComplexDDPMTrainer(args, config)
     if args.generate:
-        return trainer.generate_wav(load_pre_train=True, data_path=args.data, batch=args.batch, inflight=args.inflight)
+        return trainer.generate_wav(load_pre_train=True, data_path=args.data, batch=args.batch, inflight=args.inflight, members=args.members)
     res = trainer.train_ddpm()          # --eval: one validation epoch, or with --objective one of the denoising objective (raises NotImplementedError otherwise: training)
     import json
 

@@ -403,6 +403,61 @@ def spec_losses(esti, label, frame_list):
     return {"com_mse": loss[0], "mag_mse": loss[1], "com_mag_mse": loss[2], "per_utt": per_utt}
 
 
+def ensemble_stats(members, K, frames, out=None):
+    """The statistics of a posterior ensemble in one call of csrc/ensemble.hip (include/pdse.h: pdse_ensemble_stats).  members: the
+    K members of B utterances, member-major - a contiguous fp32 [K*B,2,T,F] (row k B + b is member k of utterance b) or
+    [K,B,2,T,F] tensor; frames: every utterance's own frames, host integers in [0, T].  Returns a dict of device tensors:
+
+        mean        fp32 [B,2,T,F]   the members added in double in member order, divided by K, rounded once
+        spread      fp32 [B,T,F]     sqrt(sum_k |x_k - mean|^2 / (K - 1)) per complex bin, from the double mean; zeros for K = 1
+        per_utt     float64 [B,2]    over an utterance's own frames: sum_bins sum_k |x_k - mean|^2, and sum_bins |mean|^2
+        per_member  float64 [K,B]    over an utterance's own frames: sum_bins |x_k - mean|^2
+
+    ``mean`` and ``spread`` cover every frame, the sums an utterance's own.  The sums are added in a fixed order: two calls give the
+    same bits.  out: (mean, spread) to write into - contiguous fp32 tensors of those shapes on the members' device.  No host
+    synchronisation."""
+    import numpy as np
+
+    K = L.members_arg(K)
+    if members.device.type != "cuda":
+        raise L.PdseError("ensemble_stats runs on the GPU only (no CPU fallback)")
+    if members.dim() == 5:
+        if members.shape[0] != K:
+            raise ValueError("members: expected [K,B,2,T,F] with K = %d, got %s" % (K, tuple(members.shape)))
+        members = members.reshape((-1,) + tuple(members.shape[2:])) if members.is_contiguous() else members
+    if members.dim() != 4 or members.shape[1] != 2 or members.dtype != torch.float32 or not members.is_contiguous() or members.shape[0] % K \
+            or members.numel() == 0:
+        raise ValueError("members: a contiguous fp32 [K*B,2,T,F] or [K,B,2,T,F] tensor")
+    B, T, F_ = members.shape[0] // K, members.shape[2], members.shape[3]
+    dev = members.device
+    frames_h = np.ascontiguousarray(np.asarray(list(frames), dtype=np.int64).reshape(-1))
+    if frames_h.size != B or frames_h.min() < 0 or frames_h.max() > T:
+        raise ValueError("frames: one frame count in [0, T] per utterance")
+    frames_h = frames_h.astype(np.int32)
+    if out is None:
+        mean, spread = torch.empty(B, 2, T, F_, dtype=torch.float32, device=dev), torch.empty(B, T, F_, dtype=torch.float32, device=dev)
+    else:
+        mean, spread = out
+        for t, shape in ((mean, (B, 2, T, F_)), (spread, (B, T, F_))):
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError("out: contiguous fp32 tensors [B,2,T,F] and [B,T,F] on the members' device")
+    frames_d = torch.from_numpy(frames_h).to(dev)
+    partial = torch.empty(B * L.ENSEMBLE_BLOCKS * (K + 2), dtype=torch.float64, device=dev)
+    per_utt = torch.empty(B, 2, dtype=torch.float64, device=dev)
+    per_member = torch.empty(K, B, dtype=torch.float64, device=dev)
+    L.ensemble_stats(members.data_ptr(), mean.data_ptr(), spread.data_ptr(), frames_h.ctypes.data, frames_d.data_ptr(), partial.data_ptr(),
+                     per_utt.data_ptr(), per_member.data_ptr(), K, B, T, F_, torch.cuda.current_stream(dev).cuda_stream, device=dev)
+    return {"mean": mean, "spread": spread, "per_utt": per_utt, "per_member": per_member}
+
+
+def relative_spread(per_utt, K):
+    """``sqrt(per_utt[b][0] / (K - 1) / per_utt[b][1])`` of ``ensemble_stats``' sums: the ensemble's standard deviation over the
+    norm of its mean, per utterance, float64 [B] (K = 1: zeros)."""
+    if K == 1:
+        return torch.zeros_like(per_utt[:, 0])
+    return torch.sqrt(per_utt[:, 0] / (K - 1) / per_utt[:, 1])
+
+
 def _compand(spec, mode, what):
     if spec.device.type != "cuda":
         raise L.PdseError("%s runs on the GPU only (no CPU fallback)" % what)

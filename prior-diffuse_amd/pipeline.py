@@ -62,7 +62,7 @@ class SamplerPipeline:
     def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, T=None, L_=None, fast_sampling=True,
                  use_sigma=False, params=default_params, with_signal=None, deltamu=False, cond="init", bank=None,
                  split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False, ragged=False,
-                 verdict=False, masked_prior=False, label=False, objective=False, feat_type="sqrt"):
+                 verdict=False, masked_prior=False, label=False, objective=False, feat_type="sqrt", members=1):
         """deltamu: the alternative parameterisation of utils/params.py:36 — ddpm_sd is a ``Nocon`` state_dict,
         x_T = noise + X_init/11 (:947-948), eps = Nocon(x, t) (:970-971), no final ``+ X_init`` (:995).
         cond (deltamu False): what conditions DiffUNet1 — "init": X_init/11 (pirorgrad, :967-969, + X_init at the end,
@@ -143,8 +143,25 @@ class SamplerPipeline:
         the compressed domain whatever it is, so nothing else changes.  "sqrt" records, launch for launch and field for field,
         the plan it always recorded.  The fp16 window of the f16x2 split was audited on sqrt-compressed activations only:
         "normal" and "none" feed the networks magnitudes one to two orders above those, and a pass that leaves the window shows
-        in the verdict / ``check()`` as before."""
+        in the verdict / ``check()`` as before.
+        members: K = 1 .. 16 reverse trajectories per utterance behind ONE pass of the front end and the prior - a posterior
+        ensemble (any other value: ValueError).  Wav prep, STFT, compression and the prior are recorded at B, the
+        eps-net and the reverse loop at K B (``EpsNetPlan(B=K*B)``), member-major: row k B + b is member k of utterance b, so a
+        member's block of B rows is an ordinary [B,2,T,161] tensor.  The prologue broadcasts X_init / 11 (and with
+        ``cond="feat"`` the feature) to the K B conditioning rows with K launches of the same division; ``xT_in`` is
+        [K B,2,T,161]; the last step writes ``members_spec`` [K B,2,T,161]; ``spec`` stays [B,2,T,161] and holds what the ISTFT
+        inverts - the ensemble mean, written by ``pdse_ensemble_stats`` (csrc/ensemble.hip; a plain-argument call between the
+        ranges "step0" and "istft", so ``graph=True`` is a ValueError), which also leaves ``ensemble``: ``spread`` [B,T,161],
+        ``per_utt`` [B,2] and ``per_member`` [K,B] (``ops.ensemble_stats``).  With ``label``, all five ``feat_type`` values,
+        ``use_sigma``, the three conditioning branches and every arithmetic; with ``ragged``, ``verdict`` or ``objective``:
+        ValueError, and plan files do not carry it.  1 (default): the plan is launch for launch and field for field today's."""
         objective = bool(objective)
+        self.members = K = L.members_arg(members)
+        if K > 1:
+            for flag, name in ((ragged, "ragged"), (verdict, "verdict"), (objective, "objective")):
+                if flag:
+                    raise ValueError("members=%d with %s=True: ensembles are built for padded sampler passes verified by check() "
+                                     "(exact ragged batches, the in-flight verdict and the objective plan run one trajectory)" % (K, name))
         self.feat_type = L.feat_type_of(feat_type)
         if objective and (L_ is None or ragged or verdict):
             raise ValueError("the objective plan needs the signal front end (pass L_) and is built for padded batches, without the verdict")
@@ -221,7 +238,8 @@ class SamplerPipeline:
             raise ValueError("prior %r not built (GCRN, DiffUNet, aia_complex_trans_ri, dual_aia_trans_merge_crm)" % prior_name)
         if dtype == "bf16":
             split_bf16 = True
-        self.eps = adopt(nets.EpsNetPlan(ctx, ddpm_sd, B, T, time_cond=True, nsteps=1 if objective else S, plan=self.plan,
+        KB = K * B       # rows of the reverse loop: member-major, row k B + b
+        self.eps = adopt(nets.EpsNetPlan(ctx, ddpm_sd, KB, T, time_cond=True, nsteps=1 if objective else S, plan=self.plan,
                                          with_pre=not deltamu, split_bf16=split_bf16,
                                          planes=nplanes,
                                          exclusive=exclusive, frames=self.frames_tab))
@@ -237,14 +255,17 @@ class SamplerPipeline:
 
         self.feat = self.prior.x                     # prior input = compressed spectrogram
         # X_init / 11: the eps-net's conditioning input only in the pirorgrad parameterisation
-        self.init = self.eps.x_init if not (deltamu or cond_feat) else ctx.alloc(B, 2, T, F0)
-        self.zero = ctx.alloc(B, 2, T, F0, zero=True) if (deltamu or cond_feat) and not objective else None
+        self.init = self.eps.x_init if not (deltamu or cond_feat) else ctx.alloc(KB, 2, T, F0)
+        self.zero = ctx.alloc(KB, 2, T, F0, zero=True) if (deltamu or cond_feat) and not objective else None
         self.audio = self.eps.x                      # x_t, updated in place
         if objective:
             self.spec, self.xT_in = self.eps.out, None   # the prediction of the one step; nothing is injected
         else:
             self.spec = self.istft.spec if with_signal else ctx.alloc(B, 2, T, F0)
-            self.xT_in = ctx.alloc(B, 2, T, F0)          # injected x_T (kept so a replay starts from it)
+            self.xT_in = ctx.alloc(KB, 2, T, F0)         # injected x_T (kept so a replay starts from it)
+        # what the last step writes: ``spec`` itself, or the K members the ensemble kernel reduces into it
+        self.members_spec = ctx.alloc(KB, 2, T, F0) if K > 1 else self.spec
+        self.ensemble = None                             # the statistics of the last ensemble pass (ops.ensemble_stats)
         n = B * 2 * T * F0
 
         if self.audited:
@@ -308,16 +329,19 @@ class SamplerPipeline:
         else:
             mark("prior", lambda: self.prior.build_step(0, x=self.feat, out=self.prior.out))
 
-        def ew(op, a, b=None, c=None, out=None, s0=0.0, s1=0.0, s2=0.0):
+        def ew(op, a, b=None, c=None, out=None, s0=0.0, s1=0.0, s2=0.0, rows=K, member=0):
+            """rows: member blocks the launch covers (K: all K B rows); member: the block of ``out`` a one-block launch writes."""
             d = L.EwDesc()
-            d.a, d.b, d.c, d.out = a.data_ptr(), nets.Ctx.ptr(b), nets.Ctx.ptr(c), out.data_ptr()
-            d.n, d.s0, d.s1, d.s2, d.op = n, s0, s1, s2, op
+            d.a, d.b, d.c, d.out = a.data_ptr(), nets.Ctx.ptr(b), nets.Ctx.ptr(c), out.data_ptr() + 4 * n * member
+            d.n, d.s0, d.s1, d.s2, d.op = n * rows, s0, s1, s2, op
             self.eps.add(d, nets.TAG_EW)
 
         def prologue():
-            ew(L.EW_DIV, self.prior.out, out=self.init, s0=PRIOR_SCALE_C)
+            for k in range(K):                    # the prior ran at B: its output / 11 into every member's conditioning rows
+                ew(L.EW_DIV, self.prior.out, out=self.init, s0=PRIOR_SCALE_C, rows=1, member=k)
             if cond_feat:
-                ew(L.EW_DIV, self.feat, out=self.eps.x_init, s0=PRIOR_SCALE_C)        # batch_feat /= c  (:943)
+                for k in range(K):
+                    ew(L.EW_DIV, self.feat, out=self.eps.x_init, s0=PRIOR_SCALE_C, rows=1, member=k)   # batch_feat /= c  (:943)
             src = self.xT_in
             if xT_plus_init:
                 ew(L.EW_ADD_MUL, self.xT_in, b=self.init, out=self.audio, s0=1.0)     # randn_like(init) + init  (:947-948)
@@ -325,8 +349,8 @@ class SamplerPipeline:
             if use_sigma:                                                             # audio * sqrt(mask(init))  (:951-956)
                 d = L.SigmaDesc()
                 d.init, d.a, d.out = self.init.data_ptr(), src.data_ptr(), self.audio.data_ptr()
-                d.maxbuf = ctx.alloc(B * 2).data_ptr()
-                d.plane, d.nplanes = T * F0, B * 2
+                d.maxbuf = ctx.alloc(KB * 2).data_ptr()
+                d.plane, d.nplanes = T * F0, KB * 2
                 d.valid = nets.Ctx.ptr(self.valid_tab)
                 self.eps.add(d, nets.TAG_EW)
             elif not xT_plus_init:
@@ -352,7 +376,7 @@ class SamplerPipeline:
         else:
             mark("prologue", prologue)
             # diffusion-step rows are stored in loop order: row i is step n = S-1-i
-            self.eps.tsteps.copy_(torch.from_numpy(np.ascontiguousarray(Tarr[::-1]))[:, None].expand(S, B))
+            self.eps.tsteps.copy_(torch.from_numpy(np.ascontiguousarray(Tarr[::-1]))[:, None].expand(S, KB))
         for i in range(0 if objective else S):
             nstep = S - 1 - i
 
@@ -363,7 +387,7 @@ class SamplerPipeline:
                     ew(L.EW_UPDATE, self.audio, b=self.eps.out, out=self.audio, s0=float(c1[nstep]), s1=float(c2[nstep]))
                 else:
                     ew(L.EW_UPDATE_FINAL, self.audio, b=self.eps.out, c=self.zero if self.zero is not None else self.init,
-                       out=self.spec,
+                       out=self.members_spec,
                        s0=float(c1[0]), s1=float(c2[0]), s2=PRIOR_SCALE_C)
 
             mark("step%d" % nstep, one)
@@ -399,6 +423,8 @@ class SamplerPipeline:
 
     def run(self, first=None, last=None, graph=False):
         """Run ranges first..last (names from ``self.ranges``), whole plan by default."""
+        if graph:
+            self._members_xT(None, True)          # an ensemble plan: ValueError
         if self.plan is None:
             raise L.PdseError("SamplerPipeline built on a CPU context cannot run: there is no CPU fallback")
         if graph:
@@ -519,15 +545,45 @@ class SamplerPipeline:
         spectrogram-level body of generate_wav (:939-998)."""
         if self.xT_in is None:
             raise ValueError("an objective plan has no sampler (SamplerPipeline(objective=True): objective_pass)")
+        x_T = SamplerPipeline._members_xT(self, x_T, graph)    # not a bound call: the argument checks run on any object with the fields
         _expect(feat, self.feat, "feat")
         _expect(x_T, self.xT_in, "x_T")
         self.feat.copy_(feat)
         self.xT_in.copy_(x_T)
-        if graph and self.stft is None:
+        if self.members > 1:
+            self._run_members("prior", None, back=False)
+        elif graph and self.stft is None:
             self.run(graph=True)
         else:
             self.run("prior", "step0")
         return self.spec.clone(), self.prior.out.clone()
+
+    def _members_xT(self, x_T, graph):
+        """The x_T of a pass as the plan holds it: an ensemble's [K,B,2,T,161] as [K B,2,T,161] (member-major either way);
+        ``graph=True`` on an ensemble plan: ValueError."""
+        K = getattr(self, "members", 1)
+        if graph and K > 1:
+            raise ValueError("graph=True with members=%d: the ensemble kernel is a plain-argument launch between the plan's ranges, "
+                             "not part of the plan or of its hipGraph" % K)
+        if x_T is not None and x_T.dim() == 5 and x_T.shape[0] == K:      # K = 1 too: [1,B,2,T,161] is one member
+            x_T = x_T.reshape((-1,) + tuple(x_T.shape[2:]))
+        return x_T
+
+    def _run_members(self, first, frames, back=True):
+        """An ensemble pass (``members`` > 1): the ranges ``first`` .. "step0", whose last launch leaves the K members in
+        ``members_spec``; ``pdse_ensemble_stats`` on them - the mean into ``spec``, the rest into ``ensemble`` (frames: every
+        utterance's own frames for the masked sums, None: all T); then, with ``back``, the range "istft" on the mean."""
+        from . import ops
+
+        self.run(first, "step0")
+        with torch.cuda.device(self.device):
+            if self.ensemble is None:
+                self._spread = torch.empty(self.B, self.T, F0, dtype=torch.float32, device=self.device)
+            self.ensemble = ops.ensemble_stats(self.members_spec, self.members, [self.T] * self.B if frames is None else frames,
+                                               out=(self.spec, self._spread))
+        if back and self.istft is not None:
+            self.plan.run_range(*self.ranges["istft"], self._stream())   # not ``run``: the pass is one, its audit table is cleared once
+            self._ranges_run = set(self.ranges)
 
     def enhance(self, wav, x_T, graph=False, lens=None, exact=False, clean=None):
         """wav [B,L], x_T [B,2,T,161] -> (enhanced wav [B,L], spectrogram [B,2,T,161]).
@@ -541,11 +597,15 @@ class SamplerPipeline:
         label spectrogram), ``spec`` (the final one, as ever), ``init_spec`` (the prior's output at the label's scale, what the
         reference's loop holds after ``init_audio *= self.c``) and the waveforms ``label.wav``, ``label.init_wav`` and
         ``label.est_wav`` - label, X_init and the final spectrogram decompressed and inverted, in the normalised domain (not
-        rescaled by c).  The returned pair is what it is without ``clean``."""
+        rescaled by c).  The returned pair is what it is without ``clean``.
+        Pipelines built with ``members=K`` > 1: x_T is [K,B,2,T,161] or [K B,2,T,161], member-major; the returned pair is the
+        ensemble mean's - ``spec`` and the waveform the back end makes of it - and the pass leaves ``members_spec`` and
+        ``ensemble`` (its masked sums over ``1 + lens[b] // 160`` frames); ``graph=True``: ValueError."""
         if self.stft is None:
             raise ValueError("pipeline was built without the signal front/back end (pass L_)")
         if self.xT_in is None:
             raise ValueError("an objective plan has no sampler (SamplerPipeline(objective=True): objective_pass)")
+        x_T = SamplerPipeline._members_xT(self, x_T, graph)    # not a bound call: the argument checks run on any object with the fields
         _expect(wav, self.stft.wav, "wav")
         _expect(x_T, self.xT_in, "x_T")
         if clean is not None:
@@ -572,7 +632,10 @@ class SamplerPipeline:
         if clean is not None:
             self.label.clean.copy_(clean)
             self.label.prepare(self._stream())     # behind the copies of wav, clean and lens, ahead of the pass
-        self.run(graph=graph)
+        if self.members > 1:      # the masked sums over every utterance's own frames, 1 + len // 160
+            self._run_members(None, None if lens is None else [1 + int(n) // 160 for n in lens])
+        else:
+            self.run(graph=graph)
         if clean is not None:
             self.label.run(self._stream())
         wav_out, spec = self.istft.wav.clone(), self.spec.clone()

@@ -134,6 +134,9 @@ def save_pipeline(path, pipe):
         raise ValueError("plan files hold the sampler's plan: an objective plan runs plain-argument calls between its ranges")
     if getattr(pipe, "verdict", False):
         raise ValueError("plan files do not carry the finiteness verdict: save a pipeline built without verdict=True")
+    if getattr(pipe, "members", 1) > 1:
+        raise ValueError("plan files hold one trajectory per utterance: a pipeline built with members=%d runs planfile.save_pipeline's "
+                         "plan around a plain-argument call (pdse_ensemble_stats)" % pipe.members)
     pipe.stft.lens.fill_(pipe.L)
     named = {"wav": pipe.stft.wav, "x_T": pipe.xT_in, "wav_out": pipe.istft.wav, "spec": pipe.spec}
     if getattr(pipe, "audited", False):

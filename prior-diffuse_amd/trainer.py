@@ -240,10 +240,11 @@ class ComplexDDPMTrainer(object):
         return _inference_schedule(self.params, fast_sampling)
 
     # ---- batched entry points ----------------------------------------------
-    def _key(self, B, T=None, L_=None, ragged=False, label=False, objective=False):
+    def _key(self, B, T=None, L_=None, ragged=False, label=False, objective=False, members=1):
         """The key of a geometry in the plan caches and in ``_range_fallback`` / ``_audit_clean``."""
         return ((B, T, L_, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling)) + ((True,) if ragged else ())
                 + (("label",) if label else ()) + (("objective",) if objective else ())
+                + ((("members", members),) if members != 1 else ())              # plans are cached per K; K = 1: the key it always had
                 + ((self.feat_type,) if self.feat_type != "sqrt" else ()))       # a trainer has one; the key names it all the same
 
     def _split_of(self, key, split):
@@ -268,14 +269,15 @@ class ComplexDDPMTrainer(object):
         key = self._key(**geom)
         ragged = True in key[5:]
         legs = {name: True for name in ("label", "objective") if name in key[5:]}      # the plans with a leg beside the sampler's
+        legs.update(m for m in key[5:] if isinstance(m, tuple))                       # ("members", K): an ensemble plan
         build = partial(self._build, key, self._split_of(key, self.split), exclusive=self.exclusive, audit=self.audit,
                         ragged=ragged, masked_prior=ragged and self.masked_prior, **legs)
         pipe, met = self._pipes.take(key, build)
         return pipe, key, met
 
-    def _pipe(self, B, T=None, L_=None, ragged=False, label=False, objective=False):
+    def _pipe(self, B, T=None, L_=None, ragged=False, label=False, objective=False, members=1):
         """The recorded plan of one geometry."""
-        return self._plan(B=B, T=T, L_=L_, ragged=ragged, label=label, objective=objective)[0]
+        return self._plan(B=B, T=T, L_=L_, ragged=ragged, label=label, objective=objective, members=members)[0]
 
     def _checked(self, run, **geom):
         """``run(pipe, graph) -> result`` on the plan of a geometry, verified (``SamplerPipeline.check``: synchronises); graph:
@@ -441,36 +443,74 @@ class ComplexDDPMTrainer(object):
             slot.pipes.pop((job.key, job.pipe.split), None)
         return self._checked(lambda pipe, graph: pipe.enhance(job.wav, job.x_T, graph=graph), B=job.wav.shape[0], L_=job.wav.shape[1])
 
-    def _x_T(self, shape, x_T):
+    def _x_T(self, shape, x_T, members=1):
+        """The x_T of a pass of ``shape`` [B,2,T,161].  members K > 1: [K B,2,T,161], member-major - drawn as K consecutive draws
+        of ``shape`` (what K one-member passes draw), or a given [K,B,2,T,161] / [K B,2,T,161] tensor."""
         if x_T is None:                                            # :947-950 randn_like(init)
-            return torch.randn(*shape, device=self.device, dtype=torch.float32)
-        return x_T.to(self.device)
+            draws = [torch.randn(*shape, device=self.device, dtype=torch.float32) for _ in range(members)]
+            return draws[0] if members == 1 else torch.cat(draws)
+        x_T = x_T.to(self.device)
+        if x_T.dim() == 5 and x_T.shape[0] == members:                   # members = 1 too: [1,B,2,T,161] is one member
+            x_T = x_T.reshape((-1,) + tuple(x_T.shape[2:]))
+        return x_T
 
-    def sample(self, feat, x_T=None, verify=True):
-        """feat [B,2,T,161] compressed spectrogram -> enhanced compressed spectrogram.  verify: see ``enhance``."""
+    def sample(self, feat, x_T=None, verify=True, members=1):
+        """feat [B,2,T,161] compressed spectrogram -> enhanced compressed spectrogram.  verify, members: see ``enhance``."""
+        members = L.members_arg(members)
         feat = feat.to(self.device)
         B, _, T, _ = feat.shape
-        x_T = self._x_T(feat.shape, x_T)
+        x_T = self._x_T(feat.shape, x_T, members)
         if not verify:
-            return self._pipe(B, T=T).sample(feat, x_T)[0]
-        return self._checked(lambda pipe, graph: pipe.sample(feat, x_T)[0], B=B, T=T)     # never replayed
+            return self._pipe(B, T=T, members=members).sample(feat, x_T)[0]
+        return self._checked(lambda pipe, graph: pipe.sample(feat, x_T)[0], B=B, T=T, members=members)     # never replayed
 
-    def enhance(self, wav, x_T=None, verify=True):
+    def enhance(self, wav, x_T=None, verify=True, members=1):
         """wav [B,L] (any scale; RMS-normalised internally like :922-923) -> enhanced [B,L].
         verify (default): the pass is checked before its result is handed out (one synchronisation: persistent launches that
         gave up, and - f16x2 operands - an activation outside the fp16 window, in which case the geometry is repeated on the
-        three-plane bf16 split, see ``_checked``); False: asynchronous, the caller answers for ``SamplerPipeline.check()``."""
+        three-plane bf16 split, see ``_checked``); False: asynchronous, the caller answers for ``SamplerPipeline.check()``.
+        members: K = 1 .. 16 reverse trajectories per utterance behind one pass of the front end and the prior
+        (``SamplerPipeline(members=K)``); the result is the ensemble mean - taken in the compressed domain, then decompressed
+        and inverted by the back end as ever.  x_T: [K,B,2,T,161] or [K B,2,T,161], member-major; None: K consecutive draws of
+        [B,2,T,161], what K one-member calls draw.  Never replayed from a hipGraph.  1 (default): today's pass.
+        ``enhance_members`` returns the members, the spread map and the sums as well."""
+        members = L.members_arg(members)
         wav = wav.to(self.device, torch.float32)
         B, L_ = wav.shape
         T = 1 + L_ // 160
-        x_T = self._x_T((B, 2, T, 161), x_T)
-        run = lambda pipe, graph: pipe.enhance(wav, x_T, graph=graph)[0]   # noqa: E731  (a geometry that comes back is replayed: ``_plan``)
+        x_T = self._x_T((B, 2, T, 161), x_T, members)
+        # a geometry that comes back is replayed (``_plan``); an ensemble pass never is
+        run = lambda pipe, graph: pipe.enhance(wav, x_T, graph=graph and members == 1)[0]   # noqa: E731
         if not verify:
-            pipe, _, met = self._plan(B=B, L_=L_)
+            pipe, _, met = self._plan(B=B, L_=L_, members=members)
             return run(pipe, met)
-        return self._checked(run, B=B, L_=L_)
+        return self._checked(run, B=B, L_=L_, members=members)
 
-    def enhance_batch(self, wavs, x_T=None, trim_to_frames=False, exact=False):
+    def enhance_members(self, wav, x_T=None, members=2):
+        """``enhance(wav, x_T, members=K)`` with everything the ensemble pass leaves, as a dictionary of tensors on the device:
+        ``wav`` [B,L] and ``spec`` [B,2,T,161] (the ensemble mean and its waveform, what ``enhance`` returns), ``members_spec``
+        [K B,2,T,161] (row k B + b: member k of utterance b), ``spread`` [B,T,161] (the sample standard deviation of every complex
+        bin), ``per_utt`` [B,2] and ``per_member`` [K,B] (float64 sums, ``ops.ensemble_stats``) and ``relative_spread`` [B] =
+        sqrt(per_utt[b][0] / (K - 1) / per_utt[b][1]), the ensemble's standard deviation over the norm of its mean (zeros for
+        K = 1).  Verified like ``enhance``.  members 1 is allowed: one member, zero spread."""
+        members = L.members_arg(members)
+        wav = wav.to(self.device, torch.float32)
+        B, L_ = wav.shape
+        x_T = self._x_T((B, 2, 1 + L_ // 160, 161), x_T, members)
+
+        def run(pipe, graph):
+            out, spec = pipe.enhance(wav, x_T)                                                  # never replayed
+            if members == 1:
+                with torch.cuda.device(self.device):
+                    ens = ops.ensemble_stats(spec, 1, [pipe.T] * B)
+            else:
+                ens = pipe.ensemble
+            return dict(wav=out, spec=spec, members_spec=pipe.members_spec.clone(), spread=ens["spread"].clone(), per_utt=ens["per_utt"],
+                        per_member=ens["per_member"], relative_spread=ops.relative_spread(ens["per_utt"], members))
+
+        return self._checked(run, B=B, L_=L_, members=members)
+
+    def enhance_batch(self, wavs, x_T=None, trim_to_frames=False, exact=False, members=1):
         """Ragged batch.  Returns a list of 1-D tensors (rescaled by c), each of its utterance's own length.
         exact False (default), the validation loop's convention: every utterance is RMS-normalised
         over its own samples, zero-padded to the longest (utils/dataset.py:45-58), enhanced in one batch
@@ -481,19 +521,25 @@ class ComplexDDPMTrainer(object):
         the maximum over its own frames (``SamplerPipeline(ragged=True)``; priors GCRN and DiffUNet, ValueError for the
         DB-AIAT priors, which attend over all frames of the batch - unless the trainer was built with ``masked_prior=True``).  x_T: one padded [B, 2, T, 161] tensor, or a list of
         per-utterance [2, T_b, 161] (or [1, 2, T_b, 161]) tensors, T_b = 1 + len_b // 160; None: one draw per utterance at its
-        own shape, in list order - the draws of the B = 1 calls."""
+        own shape, in list order - the draws of the B = 1 calls.
+        members: K > 1 returns the ensemble mean of K trajectories of the padded batch (``enhance``; x_T [K,B,2,T,161] or
+        [K B,2,T,161]); with exact=True: ValueError (an exact ragged plan runs one trajectory)."""
+        members = L.members_arg(members)
         wavs = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in wavs]
         lens = [int(w.numel()) for w in wavs]
         if min(lens) < 161:
             raise ValueError("utterances must be longer than the reflect padding (160 samples)")
+        if exact and members > 1:
+            raise ValueError("enhance_batch(exact=True, members=%d): an exact ragged plan runs one trajectory per utterance; ensembles "
+                             "take the padded pass (exact=False)" % members)
         if exact:
             out = self._enhance_ragged(wavs, x_T, max(lens))
             return [o[:(n // 160) * 160].clone() if trim_to_frames else o for o, n in zip(out, lens)]
         batch = torch.nn.utils.rnn.pad_sequence(wavs, batch_first=True).to(self.device)
         B, L_ = batch.shape
         T = 1 + L_ // 160
-        x_T = self._x_T((B, 2, T, 161), x_T)
-        out = self._checked(lambda pipe, graph: pipe.enhance(batch, x_T, lens=lens)[0], B=B, L_=L_)    # never replayed
+        x_T = self._x_T((B, 2, T, 161), x_T, members)
+        out = self._checked(lambda pipe, graph: pipe.enhance(batch, x_T, lens=lens)[0], B=B, L_=L_, members=members)    # never replayed
         cut = [(n // 160) * 160 if trim_to_frames else n for n in lens]
         return [out[i, :cut[i]].clone() for i in range(B)]
 
@@ -551,7 +597,7 @@ class ComplexDDPMTrainer(object):
         return enhanced, scores
 
     # ---- A2..A7: the reference's entry point --------------------------------
-    def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True, batch=1, inflight=1):
+    def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True, batch=1, inflight=1, members=1):
         """Per-file B=1 enhancement of ``data_path/*.wav`` into ``args.generated_wav``
         (:903-1018).  Returns the list of written paths instead of calling exit().
 
@@ -582,23 +628,58 @@ class ComplexDDPMTrainer(object):
         ``enhance_stream(inflight=N)``: they are read, decoded, drawn and skipped as in the default mode, file by file as the
         stream asks for them, and the same files are written under the same names; every file is verified by its plan's
         own verdict instead of a synchronisation per file.  The bits are those of an ``exclusive=False`` trainer (see
-        ``enhance_stream``).  With ``batch`` > 1: ValueError (streams of ragged windows are not built)."""
+        ``enhance_stream``).  With ``batch`` > 1: ValueError (streams of ragged windows are not built).
+
+        members (default 1): K = 2 .. 16 writes every file from the mean of a K-member posterior ensemble (``enhance_members``:
+        one pass of the front end and the prior, K reverse trajectories).  Member k's x_T is the file's k-th draw, each followed by
+        its own ``rng_fidelity`` discards: a seeded run draws for a file what K consecutive one-member runs of it would draw.
+        ``<args.log>/ensemble.json`` (``args.log``: ``<assets>/log/<doc>``; beside the written files where the arguments have
+        none) then holds, per file, ``relative_spread`` and ``medoid``, the index of the member nearest the mean (the argmin of
+        ``per_member``).  One file per pass: with ``batch`` > 1, ``inflight`` > 1, ``channels="each"`` or an ``audit=True``
+        trainer: ValueError."""
         inflight = _inflight_arg(inflight)
+        members = L.members_arg(members)
         if inflight > 1 and int(batch) > 1:
             raise ValueError("generate_wav: inflight > 1 runs one file per pass (batch=1); streams of ragged windows are not built")
+        if members > 1:
+            for on, what in ((int(batch) > 1, "batch > 1 (exact ragged batches run one trajectory per file)"),
+                             (inflight > 1, "inflight > 1 (the in-flight plans are verified by the verdict, which an ensemble plan lacks)"),
+                             (self.channels == "each", "channels='each' (a file's channels share an exact ragged pass)"),
+                             (self.audit, "audit=True (the range audit reads one trajectory's report)")):
+                if on:
+                    raise ValueError("generate_wav(members=%d) with %s: ensembles are built for one file per pass" % (members, what))
         if load_pre_train and getattr(self.args, "retrain", False):
             self._load_checkpoint()
         os.makedirs(self.args.generated_wav, exist_ok=True)
         if int(batch) > 1:
             return self._generate_wav_batched(data_path, rng_fidelity, int(batch))
         one_by_one = lambda n: [(k, k + 1) for k in range(n)]   # noqa: E731  (a file is read when its turn comes)
+        if members > 1:
+            report = {}
+            written = self._file_loop(data_path, rng_fidelity, one_by_one, partial(self._enhance_ensembles, members=members, report=report),
+                                      members=members)
+            import json
+
+            log = getattr(self.args, "log", None) or self.args.generated_wav
+            os.makedirs(log, exist_ok=True)
+            with open(os.path.join(log, "ensemble.json"), "w") as f:
+                json.dump({"members": members, "files": report}, f, indent=1)
+            return written
         return self._file_loop(data_path, rng_fidelity, one_by_one, partial(self._enhance_files, inflight=inflight))
+
+    def _enhance_ensembles(self, windows, members, report):
+        """``_file_loop``'s files one per pass as K-member ensembles: the file from the mean, its figures into ``report``."""
+        for path, wav, x_T in chain.from_iterable(windows):
+            res = self.enhance_members(wav[None], x_T=x_T, members=members)
+            report[os.path.basename(path)] = {"relative_spread": float(res["relative_spread"][0]),
+                                              "medoid": int(torch.argmin(res["per_member"][:, 0]))}
+            yield path, res["wav"][0]
 
     def _generate_wav_batched(self, data_path, rng_fidelity, batch):
         ragged_args(self.prior_name, 161, masked=self.masked_prior)
         return self._file_loop(data_path, rng_fidelity, partial(raggedplan.windows, batch=batch), partial(self._enhance_windows, batch=batch))
 
-    def _file_loop(self, data_path, rng_fidelity, windows, enhance):
+    def _file_loop(self, data_path, rng_fidelity, windows, enhance, members=1):
         """The file loop of ``generate_wav``.  windows(n) -> [(lo, hi)]: the slices of the sorted paths that are read at once.
         enhance: a generator function; it is handed an iterator of windows, each an iterator of the window's readable files as
         ``(path, wav [len], x_T)``, and yields ``(path, enhanced [len])`` in path order (``channels="each"``, a file of C > 1
@@ -611,11 +692,12 @@ class ComplexDDPMTrainer(object):
             for path, wav in self._load_window(window):
                 shape = (1, 2, 1 + wav.shape[-1] // 160, 161)
                 x_T = []
-                for _ in range(1 if wav.dim() == 1 else wav.shape[0]):        # channels="each": a draw per channel, in channel order
+                # channels="each": a draw per channel, in channel order; members=K (mono rows only): a draw per member, in member order
+                for _ in range(members if wav.dim() == 1 else wav.shape[0]):
                     x_T.append(self._x_T(shape, None))                        # :947-950 randn_like(init): the file's draw, kept for a repeat
                     for _ in range(ndiscard):
                         torch.randn(*shape, device=self.device, dtype=torch.float32)     # :986 randn_like, scaled by 0
-                yield path, wav, x_T[0] if wav.dim() == 1 else torch.cat(x_T)
+                yield path, wav, x_T[0] if wav.dim() == 1 and members == 1 else torch.cat(x_T)
 
         written = []
         with torch.no_grad():
@@ -783,7 +865,7 @@ class ComplexDDPMTrainer(object):
             batch[b, :lens[b]] = w.to(self.device)
         return batch
 
-    def validate_batch(self, noisy_wavs, clean_wavs, x_T=None, exact=False, prior=True, stoi=False):
+    def validate_batch(self, noisy_wavs, clean_wavs, x_T=None, exact=False, prior=True, stoi=False, members=1):
         """One batch of the validation loop, scored on the device (:408-559).  noisy_wavs, clean_wavs: lists of 1-D
         waveforms, pair by pair of one length.  The pass is ``enhance_batch``'s - every noisy utterance RMS-normalised over its
         own samples, zero-padded to the longest, the padding takes part (exact=True: the exact ragged pass, every utterance as
@@ -795,9 +877,19 @@ class ComplexDDPMTrainer(object):
         (``metrics.quality(..., stoi=stoi)``).
         Returns (enhanced, scores): enhanced is ``enhance_batch(..., trim_to_frames=True)``'s list; scores holds ``frames``
         (host list) and, under "x" and "init", device tensors: ``loss`` [3] (com_mse, mag_mse, com_mag_mse), ``per_utt`` [B, 2]
-        float64 numerators and one [B] tensor per measure.  One synchronisation: the pass's own check (``_checked``)."""
+        float64 numerators and one [B] tensor per measure.  One synchronisation: the pass's own check (``_checked``).
+        members: K > 1 runs a K-member ensemble of the padded batch (``enhance``; x_T [K, B, 2, T, 161] or [K B, 2, T, 161], None:
+        K consecutive draws).  "x" then scores the ensemble mean - its spectrogram, and the waveforms the label leg makes of
+        it - "init" is what it is for one member, and scores holds "ensemble": ``members``; ``loss_by_member`` [K], the com_mse of
+        every member's own [B, 2, T, 161] block against the label (``ops.spec_losses``), with ``per_utt_by_member`` [K, B, 2], its
+        numerators; ``loss_member_mean`` and ``loss_member_std`` (over the K members; the sample standard deviation) and
+        ``relative_spread`` [B] (``enhance_members``).  With exact=True: ValueError."""
         from . import metrics, validation as V
 
+        members = L.members_arg(members)
+        if exact and members > 1:
+            raise ValueError("validate_batch(exact=True, members=%d): an exact ragged plan runs one trajectory per utterance; ensembles "
+                             "take the padded pass (exact=False)" % members)
         noisy, clean, lens = self._pairs(noisy_wavs, clean_wavs)
         frames, cut = [V.frame_num(n) for n in lens], [V.trim_len(n) for n in lens]
         if min(cut) < metrics.MIN_LEN:
@@ -806,7 +898,7 @@ class ComplexDDPMTrainer(object):
         if exact:
             ragged_args(self.prior_name, L_, masked=self.masked_prior)
         batch, cbatch = self._padded(noisy, lens), self._padded(clean, lens)
-        x_T = self._x_T((B, 2, 1 + L_ // 160, 161), x_T)
+        x_T = self._x_T((B, 2, 1 + L_ // 160, 161), x_T, members)
 
         def run(pipe, graph):
             out, spec = pipe.enhance(batch, x_T, lens=lens, exact=exact, clean=cbatch)           # never replayed
@@ -816,12 +908,18 @@ class ComplexDDPMTrainer(object):
                     ls = ops.spec_losses(sp, leg.spec, frames)
                     q = metrics.quality(leg.wav, wav, lens=cut, stoi=stoi)
                     scores[name] = dict(q, loss=torch.stack([ls[k] for k in V.LOSSES]), per_utt=ls["per_utt"])
+                if members > 1:
+                    by = [ops.spec_losses(pipe.members_spec[k * B:(k + 1) * B], leg.spec, frames) for k in range(members)]
+                    loss = torch.stack([r["com_mse"] for r in by])
+                    scores["ensemble"] = {"members": members, "loss_by_member": loss, "per_utt_by_member": torch.stack([r["per_utt"] for r in by]),
+                                          "loss_member_mean": loss.double().mean(), "loss_member_std": loss.double().std(),
+                                          "relative_spread": ops.relative_spread(pipe.ensemble["per_utt"], members)}
             return [out[i, :cut[i]].clone() for i in range(B)], scores
 
-        return self._checked(run, B=B, L_=L_, ragged=bool(exact), label=True)
+        return self._checked(run, B=B, L_=L_, ragged=bool(exact), label=True, members=members)
 
     def validate(self, noisy_dir="data/noisy_testset_wav", clean_dir="data/clean_testset_wav", batch_size=None, order="sorted",
-                 drop_last=False, exact=False, prior=True, stoi=False, rng_fidelity=True, x_T=None):
+                 drop_last=False, exact=False, prior=True, stoi=False, rng_fidelity=True, x_T=None, members=1):
         """One validation epoch over the (noisy, clean) pairs of two directories: what ``train_ddpm`` runs after an epoch of
         training, and all it runs under ``--eval`` (:387, :399-580).  Returns the dictionary of ``validation.aggregate``.
 
@@ -838,7 +936,17 @@ class ComplexDDPMTrainer(object):
         numerators over summed denominators; the same pair under ``mag_mse`` and ``com_mag_mse``; ``mean_ssnr``, ``mean_llr``,
         ``mean_wss``, ``mean_fwsnrseg`` (``mean_stoi``, ``mean_estoi`` with ``stoi``): means of batch means; with ``prior`` all of it
         again under "init", for X_init - what the diffusion adds over its prior; ``files``: per file its name, frames, loss
-        numerators and measures.  PESQ and the composite figures that need it stay out, as in ``metrics``."""
+        numerators and measures.  PESQ and the composite figures that need it stay out, as in ``metrics``.
+        members: K > 1 scores a K-member ensemble per batch (``validate_batch``): "x" is the ensemble mean's, "init" unchanged, and
+        the dictionary gains "ensemble": ``members``, ``loss_by_member`` (K com_mse values, each the mean of the batches' as
+        ``loss`` is), ``loss_member_mean`` and ``loss_member_std`` over those K (the sample standard deviation) and
+        ``relative_spread``, the mean over files.  A batch's draws are member by member: member k's x_T, then with ``rng_fidelity``
+        its discards - what K consecutive one-member passes of the batch draw.  x_T: per batch [K, B, 2, T, 161] or
+        [K B, 2, T, 161].  With exact=True: ValueError."""
+        members = L.members_arg(members)
+        if exact and members > 1:
+            raise ValueError("validate(exact=True, members=%d): an exact ragged plan runs one trajectory per utterance; ensembles take "
+                             "the padded pass (exact=False)" % members)
         names, batches, load = self._pair_epoch(noisy_dir, clean_dir, batch_size, order, drop_last)
         if x_T is not None and len(x_T) != len(batches):
             raise ValueError("x_T: expected one tensor per batch (%d), got %d" % (len(batches), len(x_T)))
@@ -849,14 +957,30 @@ class ComplexDDPMTrainer(object):
                 noisy, clean = load(idx)
                 shape = (len(idx), 2, 1 + max(int(w.numel()) for w in noisy) // 160, 161)
                 if x_T is None:
-                    draw = self._x_T(shape, None)                                  # :448 randn_like(init_audio)
-                    for _ in range(ndiscard):
-                        torch.randn(*shape, device=self.device, dtype=torch.float32)   # :484 randn_like(audio), scaled by 0
+                    draws = []
+                    for _ in range(members):
+                        draws.append(self._x_T(shape, None))                       # :448 randn_like(init_audio)
+                        for _ in range(ndiscard):
+                            torch.randn(*shape, device=self.device, dtype=torch.float32)   # :484 randn_like(audio), scaled by 0
+                    draw = draws[0] if members == 1 else torch.cat(draws)
                 else:
                     draw = x_T[k]
-                _, scores = self.validate_batch(noisy, clean, x_T=draw, exact=exact, prior=prior, stoi=stoi)
+                _, scores = self.validate_batch(noisy, clean, x_T=draw, exact=exact, prior=prior, stoi=stoi, members=members)
                 held.append((idx, scores))
-        return self._collect_validation(held, names, prior, stoi)
+        res = self._collect_validation(held, names, prior, stoi)
+        if members > 1:
+            import numpy as np
+
+            flat = torch.cat([torch.cat([sc["ensemble"]["loss_by_member"].double(), sc["ensemble"]["relative_spread"]]) for _, sc in held])
+            host, by, spread, at = flat.cpu().numpy(), [], [], 0
+            for idx, _ in held:
+                by.append(host[at:at + members])
+                spread += list(host[at + members:at + members + len(idx)])
+                at += members + len(idx)
+            loss = np.mean(by, axis=0)                                              # per member: the mean of the batches' com_mse
+            res["ensemble"] = {"members": members, "loss_by_member": [float(v) for v in loss], "loss_member_mean": float(loss.mean()),
+                               "loss_member_std": float(loss.std(ddof=1)), "relative_spread": float(np.mean(spread))}
+        return res
 
     def _pair_epoch(self, noisy_dir, clean_dir, batch_size, order, drop_last):
         """The file loop of an epoch over the (noisy, clean) pairs of two directories, shared by ``validate`` and ``objective``:
@@ -1036,7 +1160,7 @@ class ComplexDDPMTrainer(object):
             res = self.objective(draws=getattr(self.args, "draws", 1), **kw)
             logging.info(O.log_line(res))
             return res
-        res = self.validate(**kw)
+        res = self.validate(members=int(getattr(self.args, "members", 1) or 1), **kw)
         logging.info(V.log_line(res))
         return res
 
