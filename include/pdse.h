@@ -401,6 +401,14 @@ typedef struct pdse_glstm_desc {
   int32_t tc;
   int32_t lag;
   int32_t pad_;
+  /* Carried state (additive within ABI 9; the descriptor grew by two pointers, see the note on tc): the recurrence of a long
+     recording cut into consecutive calls.  state_in NULL: h and c of both layers start from zeros - the launch is, bit for bit,
+     the one without the fields.  state_in set: frame 0 of layer 1 / layer 2 reads h[-1] and c[-1] from it instead.  state_out
+     set: frame T - 1 of either layer also stores its h and c there.  Both are [4][G][H][Bp] floats - h1, c1, h2, c2, h in the
+     layout of one hT slot, c in that of cst - and must not overlap each other or the scratch: a call that consumes the state
+     another call left gives what one call over both calls' frames gives, bit for bit (three-stage and chunked form alike). */
+  const float* state_in;
+  float* state_out;
 } pdse_glstm_desc;
 
 /* The same grouped LSTM (both layers + LayerNorm 1, gcrn.py:22-35) as ONE persistent launch for small batches
@@ -1288,6 +1296,22 @@ int pdse_ensemble_stats(const float* members,         /* device [K][B][2][T][F] 
                         double* per_utt,              /* device [B][2] */
                         double* per_member,           /* device [K][B] */
                         int32_t K, int32_t B, int32_t T, int32_t F, pdse_stream_t s);
+
+/* Windowed passes over recordings of any length (csrc/window.hip, additive within ABI 9; plain arguments): frames of a whole-file
+ * [B][C][T][F] fp32 tensor into and out of a fixed-length window tensor [B][C][W][F] - the fp32 layout in which both networks read
+ * their inputs and write their outputs, so a window needs no conversion launch.  Everything is validated before the launch and
+ * without a device.  Both are pure copies along contiguous rows of F floats: a bit pattern arrives unchanged.
+ * pdse_window_gather: win[b][c][w][:] = whole[b][c][a + w][:] for 0 <= a + w < T and zeros for the other w (a window may hang over
+ * either end of the file: the causal prior runs its last window that way); a + W > 0 and a < T.
+ * pdse_window_scatter: whole[b][c][t][:] = win[b][c][t - a][:] for keep_lo <= t < keep_hi only, with
+ * max(a, 0) <= keep_lo <= keep_hi <= min(a + W, T); every other element of whole is left as it is. */
+int pdse_window_gather(const float* whole,            /* device [B][C][T][F] */
+                       float* win,                    /* device [B][C][W][F] */
+                       int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t a, pdse_stream_t s);
+int pdse_window_scatter(const float* win,             /* device [B][C][W][F] */
+                        float* whole,                 /* device [B][C][T][F] */
+                        int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t a, int32_t keep_lo, int32_t keep_hi,
+                        pdse_stream_t s);
 
 /* plans: a recorded operator sequence replayed by one call (and capturable in a hipGraph) */
 typedef struct pdse_plan pdse_plan;

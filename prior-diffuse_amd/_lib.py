@@ -132,7 +132,7 @@ class GlstmDesc(C.Structure):
                 ("hT1", _fp), ("cst1", _fp), ("hT2", _fp), ("cst2", _fp), ("gx2", _fp), ("part", _fp), ("y", _fp),
                 ("y_sb", _i64), ("y_st", _i64), ("y_su", _i64), ("y_sg", _i64),
                 ("B", _i32), ("Bp", _i32), ("T", _i32), ("H", _i32), ("G", _i32), ("eps", _f32), ("slices", _i32), ("tc", _i32), ("lag", _i32),
-                ("pad_", _i32)]
+                ("pad_", _i32), ("state_in", _fp), ("state_out", _fp)]
 
 
 class GlstmpDesc(C.Structure):
@@ -384,7 +384,7 @@ EXPORTS = [
     "pdse_plan_destroy", "pdse_plan_load", "pdse_plan_region", "pdse_prior_forward", "pdse_eps_forward", "pdse_enhance",
     "pdse_wav_encode", "pdse_wav_encode_channels", "pdse_pair_prep", "pdse_spec_losses", "pdse_spec_frames",
     "pdse_spec_frames_mode",
-    "pdse_objective_noise", "pdse_sigma_loss", "pdse_ensemble_stats",
+    "pdse_objective_noise", "pdse_sigma_loss", "pdse_ensemble_stats", "pdse_window_gather", "pdse_window_scatter",
 ] + [name for _, _, name in OPS]
 
 
@@ -458,6 +458,10 @@ def load():
     lib.pdse_sigma_loss.restype = C.c_int
     lib.pdse_ensemble_stats.argtypes = [_fp] * 8 + [_i32] * 4 + [C.c_void_p]
     lib.pdse_ensemble_stats.restype = C.c_int
+    lib.pdse_window_gather.argtypes = [_fp] * 2 + [_i32] * 6 + [C.c_void_p]
+    lib.pdse_window_gather.restype = C.c_int
+    lib.pdse_window_scatter.argtypes = [_fp] * 2 + [_i32] * 8 + [C.c_void_p]
+    lib.pdse_window_scatter.restype = C.c_int
     if lib.pdse_abi_version() != ABI_VERSION:
         raise PdseError("libpdse.so ABI %d != binding ABI %d" % (lib.pdse_abi_version(), ABI_VERSION))
     for kind, typ in DESC_TYPES.items():
@@ -567,6 +571,21 @@ def ensemble_stats(members, mean, spread, frames_host, frames, partial, per_utt,
     with _on(device):
         check(lib.pdse_ensemble_stats(members, mean, spread, frames_host, frames, partial, per_utt, per_member, int(K), int(B), int(T),
                                       int(F), C.c_void_p(stream)), "pdse_ensemble_stats")
+
+
+def window_gather(whole, win, B, C_, T, F, W, a, stream=0, device=None):
+    """pdse_window_gather (include/pdse.h: frames [a, a + W) of a whole-file tensor into a window, csrc/window.hip): pointers as integers."""
+    lib = load()
+    with _on(device):
+        check(lib.pdse_window_gather(whole, win, int(B), int(C_), int(T), int(F), int(W), int(a), C.c_void_p(stream)), "pdse_window_gather")
+
+
+def window_scatter(win, whole, B, C_, T, F, W, a, keep_lo, keep_hi, stream=0, device=None):
+    """pdse_window_scatter (include/pdse.h: a window's kept frames back to their whole-file position, csrc/window.hip)."""
+    lib = load()
+    with _on(device):
+        check(lib.pdse_window_scatter(win, whole, int(B), int(C_), int(T), int(F), int(W), int(a), int(keep_lo), int(keep_hi),
+                                      C.c_void_p(stream)), "pdse_window_scatter")
 
 
 class Plan:

@@ -203,6 +203,17 @@ int pdse_ensemble_stats(const float* members, float* mean, float* spread, const 
   return pdse_ensemble_stats_launch(members, mean, spread, frames_host, frames, partial, per_utt, per_member, K, B, T, F, (hipStream_t)s);
 }
 
+// gather / scatter of the windowed passes (csrc/window.hip): plain arguments, outside the operator table
+int pdse_window_gather(const float* whole, float* win, int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t a,
+                       pdse_stream_t s) {
+  return pdse_window_gather_launch(whole, win, B, C, T, F, W, a, (hipStream_t)s);
+}
+
+int pdse_window_scatter(const float* win, float* whole, int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t a,
+                        int32_t keep_lo, int32_t keep_hi, pdse_stream_t s) {
+  return pdse_window_scatter_launch(win, whole, B, C, T, F, W, a, keep_lo, keep_hi, (hipStream_t)s);
+}
+
 int pdse_plan_create(pdse_plan** out) {
   if (!out) {
     pdse_set_error("plan_create: null out");

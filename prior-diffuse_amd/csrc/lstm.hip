@@ -147,7 +147,10 @@ __device__ long long* g_trace_l = nullptr;   // PDSE_GLSTM_TRACE=1 (diagnostic):
 // alone - so it leaves the per-step launch: grid z carries stages A and C only (C at frame s - lag, lag = tc + 1), and
 // glstm_proj_kernel below evaluates stage B for a chunk of tc frames from ONE fetch of its weight slice.  hT1, part and gx2
 // are rings of R = 2 tc frames (pdse.h).  Stages A and C are the same code in the same order as in the three-stage form.
-template <int NS, bool CH>
+// ST: the launch carries state (pdse_glstm_desc.state_in / state_out, [4][G][H][Bp]: h1, c1, h2, c2) - frame 0 of a layer reads
+// h[-1] and c[-1] from state_in where it is set, frame T - 1 also stores its h and c to state_out where it is set.  A template
+// parameter: the instantiations without it are, instruction for instruction, the kernels as they were.
+template <int NS, bool CH, bool ST>
 __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d, const int s, const int stage_mask) {
   extern __shared__ __attribute__((aligned(16))) float lds_[];
   float (*red)[32 * NS][33] = reinterpret_cast<float (*)[32 * NS][33]>(lds_);                    // [8 waves][rows][items + 1]
@@ -186,6 +189,7 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
     hsrc0 = hsrc1 = d.hT1 + ((size_t)r1 * G + g) * hsz;
     kq0 = 0, kq1 = 32;
     skip = t == 0;
+    if (ST && t == 0 && d.state_in) hsrc0 = hsrc1 = d.state_in + (size_t)g * hsz, skip = false;
   } else if (!CH && stage == 1) {                          // W'_ih2 y1[t]: features of chunk g = units 256g..256g+255 of BOTH groups
     Aw = d.wih2;
     const float* base = d.hT1 + (size_t)((t + 1) & 1) * G * hsz;   // h1[t] was written to parity (t & 1) ^ 1
@@ -196,6 +200,7 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
     hsrc0 = hsrc1 = d.hT2 + ((size_t)par * G + g) * hsz;
     kq0 = 0, kq1 = 32;
     skip = t == 0;
+    if (ST && t == 0 && d.state_in) hsrc0 = hsrc1 = d.state_in + (size_t)(2 * G + g) * hsz, skip = false;
   }
   const float4* A4 = reinterpret_cast<const float4*>(Aw) + ((size_t)(g * (H / 8) + slice) * (H / 8)) * 64 + lane;
 
@@ -260,10 +265,12 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
       const int lq = threadIdx.x / (64 * NS), lb = (threadIdx.x / (2 * NS)) & 31, lu = (threadIdx.x & (2 * NS - 1)) * 4;
       gx4 = *reinterpret_cast<const float4*>(d.gx1 + (((size_t)g * d.T + t) * Bp + bt * 32 + lb) * (4 * H) + (size_t)lq * H + slice * 8 + lu);
       if (t > 0) c_old = d.cst1[ci];
+      else if (ST && d.state_in) c_old = d.state_in[(size_t)G * hsz + ci];
     } else if (stage == 2) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) pre[q] = d.gx2[(((size_t)r1 * G + g) * (4 * H) + (size_t)q * H + hu) * Bp + b];
       if (t > 0) c_old = d.cst2[ci];
+      else if (ST && d.state_in) c_old = d.state_in[(size_t)3 * G * hsz + ci];
     }
   }
   float k0e = 0.f;                                   // stage B: the k of the fold, for the epilogue's item
@@ -351,10 +358,18 @@ __global__ __launch_bounds__(512) void glstm_wave_kernel(const pdse_glstm_desc d
       d.cst1[ci] = c;
       d.hT1[((size_t)w1 * G + g) * hsz + hidx(hu, b, Bp)] = hv;
       stat[uu][bb][0] = hv;                         // stat[] is unused in stages 0 / 2: staging for the partial sums
+      if (ST && d.state_out && t == d.T - 1) {
+        d.state_out[(size_t)g * hsz + hidx(hu, b, Bp)] = hv;
+        d.state_out[(size_t)G * hsz + ci] = c;
+      }
     } else {
       d.cst2[ci] = c;
       d.hT2[((size_t)(par ^ 1) * G + g) * hsz + hidx(hu, b, Bp)] = hv;
       if (b < d.B) d.y[(int64_t)b * d.y_sb + (int64_t)t * d.y_st + (int64_t)hu * d.y_su + (int64_t)g * d.y_sg] = hv;
+      if (ST && d.state_out && t == d.T - 1) {
+        d.state_out[(size_t)(2 * G + g) * hsz + hidx(hu, b, Bp)] = hv;
+        d.state_out[(size_t)3 * G * hsz + ci] = c;
+      }
     }
   }
   LSTAMP(5);
@@ -520,8 +535,10 @@ static int glstm_chunk_launch(const pdse_glstm_desc* d, hipStream_t s, const int
   const dim3 grid(d->H / 8 / NS, d->G, 2 * nbt), block(512);
   const size_t lds = (size_t)(8 * 32 * NS * 33 + 16 * 32 * 2 + 4 * 32 * 8 * NS) * sizeof(float);
   const size_t plds = (size_t)2 * PROJ_BUF * sizeof(float);
-  static unsigned long long attr_wave = 0, attr_proj = 0;
-  if (NS == 2 && pdse_lds_attr((const void*)glstm_wave_kernel<2, true>, &attr_wave, "glstm lds attribute")) return 1;
+  static unsigned long long attr_wave = 0, attr_wave_st = 0, attr_proj = 0;
+  const bool st_ = d->state_in || d->state_out;
+  if (NS == 2 && !st_ && pdse_lds_attr((const void*)glstm_wave_kernel<2, true, false>, &attr_wave, "glstm lds attribute")) return 1;
+  if (NS == 2 && st_ && pdse_lds_attr((const void*)glstm_wave_kernel<2, true, true>, &attr_wave_st, "glstm lds attribute")) return 1;
   if (pdse_lds_attr((const void*)glstm_proj_kernel, &attr_proj, "glstm projection lds attribute")) return 1;
   for (int st = 0; st < T + TC + 1; ++st) {
     if (st > 0 && st <= T && (st % TC == 0 || st == T) && (mask & 2)) {   // frames (st - 1) / TC * TC .. st - 1 are complete
@@ -530,8 +547,11 @@ static int glstm_chunk_launch(const pdse_glstm_desc* d, hipStream_t s, const int
       hipLaunchKernelGGL(glstm_proj_kernel, dim3(d->H / 8, d->G, nbt * FS), block, plds, s, *d, t0, nf, FS);
     }
     if (st >= T && st < d->lag) continue;                                  // T < lag: steps with neither stage
-    if (NS == 2) hipLaunchKernelGGL((glstm_wave_kernel<2, true>), grid, block, lds, s, *d, st, mask);
-    else hipLaunchKernelGGL((glstm_wave_kernel<1, true>), grid, block, lds, s, *d, st, mask);
+    if (st_) {
+      if (NS == 2) hipLaunchKernelGGL((glstm_wave_kernel<2, true, true>), grid, block, lds, s, *d, st, mask);
+      else hipLaunchKernelGGL((glstm_wave_kernel<1, true, true>), grid, block, lds, s, *d, st, mask);
+    } else if (NS == 2) hipLaunchKernelGGL((glstm_wave_kernel<2, true, false>), grid, block, lds, s, *d, st, mask);
+    else hipLaunchKernelGGL((glstm_wave_kernel<1, true, false>), grid, block, lds, s, *d, st, mask);
   }
   return pdse_check_launch("glstm");
 }
@@ -554,6 +574,10 @@ int pdse_glstm_launch(const pdse_glstm_desc* d, hipStream_t s) {
     pdse_set_error("glstm: bad sizes (H == 512, G == 2 as in gcrn.py:9-16, Bp % 32 == 0, Bp >= B)");
     return 1;
   }
+  if (d->state_in && d->state_in == d->state_out) {
+    pdse_set_error("glstm: state_in and state_out must not be the same buffer (frame 0 of layer 2 reads the one after frame T - 1 of layer 1 wrote the other)");
+    return 1;
+  }
   if (d->slices < 0 || d->slices > 2) {
     pdse_set_error("glstm: slices is 0 / 1 (one slice of 8 units per workgroup) or 2");
     return 1;
@@ -564,8 +588,10 @@ int pdse_glstm_launch(const pdse_glstm_desc* d, hipStream_t s) {
   const int NS = d->slices == 2 ? 2 : 1;
   const dim3 grid(d->H / 8 / NS, d->G, 3 * (d->Bp / 32)), block(512);
   const size_t lds = (size_t)(8 * 32 * NS * 33 + 16 * 32 * 2 + 4 * 32 * 8 * NS) * sizeof(float);
-  static unsigned long long attr_mask = 0;
-  if (NS == 2 && pdse_lds_attr((const void*)glstm_wave_kernel<2, false>, &attr_mask, "glstm lds attribute")) return 1;
+  static unsigned long long attr_mask = 0, attr_mask_st = 0;
+  const bool st_ = d->state_in || d->state_out;
+  if (NS == 2 && !st_ && pdse_lds_attr((const void*)glstm_wave_kernel<2, false, false>, &attr_mask, "glstm lds attribute")) return 1;
+  if (NS == 2 && st_ && pdse_lds_attr((const void*)glstm_wave_kernel<2, false, true>, &attr_mask_st, "glstm lds attribute")) return 1;
   static const bool tracing = PDSE_DIAG_ENV("PDSE_GLSTM_TRACE") != nullptr;
   static long long* tbuf = nullptr;
   const size_t nw = (size_t)grid.x * grid.y * grid.z * 8;
@@ -577,8 +603,11 @@ int pdse_glstm_launch(const pdse_glstm_desc* d, hipStream_t s) {
     (void)hipMemsetAsync(tbuf, 0, nw * 64, s);
   }
   for (int st = 0; st < d->T + 2; ++st) {
-    if (NS == 2) hipLaunchKernelGGL((glstm_wave_kernel<2, false>), grid, block, lds, s, *d, st, mask);
-    else hipLaunchKernelGGL((glstm_wave_kernel<1, false>), grid, block, lds, s, *d, st, mask);
+    if (st_) {
+      if (NS == 2) hipLaunchKernelGGL((glstm_wave_kernel<2, false, true>), grid, block, lds, s, *d, st, mask);
+      else hipLaunchKernelGGL((glstm_wave_kernel<1, false, true>), grid, block, lds, s, *d, st, mask);
+    } else if (NS == 2) hipLaunchKernelGGL((glstm_wave_kernel<2, false, false>), grid, block, lds, s, *d, st, mask);
+    else hipLaunchKernelGGL((glstm_wave_kernel<1, false, false>), grid, block, lds, s, *d, st, mask);
   }
   if (tracing) {   // diagnostic: stamps of wavefront step T/2 - start spread (100 MHz clock) and shader clocks since the wave started
     (void)hipStreamSynchronize(s);

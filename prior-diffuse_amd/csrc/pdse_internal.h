@@ -101,5 +101,10 @@ int pdse_sigma_loss_launch(const float* predicted, const float* target, const fl
 int pdse_ensemble_stats_launch(const float* members, float* mean, float* spread, const int32_t* frames_host, const int32_t* frames,
                                double* partial, double* per_utt, double* per_member, int32_t K, int32_t B, int32_t T, int32_t F,
                                hipStream_t s);
+// csrc/window.hip: gather / scatter of the windowed passes behind pdse_window_gather / pdse_window_scatter (plain arguments too)
+int pdse_window_gather_launch(const float* whole, float* win, int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t a,
+                              hipStream_t s);
+int pdse_window_scatter_launch(const float* win, float* whole, int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t a,
+                               int32_t keep_lo, int32_t keep_hi, hipStream_t s);
 int pdse_range_validate(const pdse_range_desc* d);               /* reads the row table back and checks it (direct launches, plan_add) */
 #endif

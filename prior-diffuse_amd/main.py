@@ -20,6 +20,8 @@ import numpy as np
 import torch
 import yaml
 
+from . import longplan
+
 
 def dict2namespace(config):  # main.py:9-17
     ns = argparse.Namespace()
@@ -88,7 +90,24 @@ def parse_args_and_config(argv=None):
                         "ensemble.json holds its relative spread and medoid member; --eval: the mean is scored and eval.json gains "
                         "the members' losses and the spread; not with --batch (--generate), --inflight, --per-channel, --audit-range "
                         "or --objective; default 1: one trajectory")
+    p.add_argument("--window", type=int, nargs="?", const=longplan.DEFAULT_WINDOW, default=None, metavar="FRAMES",
+                   help="(not a flag of the reference) --generate: recordings of any length - a file of more than FRAMES frames (10 ms "
+                        "each) runs both networks in windows of FRAMES frames through one plan that every file reuses, with the result "
+                        "of the whole-file pass (priors GCRN and DiffUNet); a multiple of 32, above the eps-net's receptive field of "
+                        "388 + 378 frames; given without a value: %d (20.5 s; 1.6 frames computed per frame kept); not with --batch, "
+                        "--inflight, --per-channel, --members, --audit-range, --eval or --objective; default: one plan per length"
+                        % longplan.DEFAULT_WINDOW)
     args = p.parse_args(argv)
+    if args.window is not None:
+        try:
+            longplan.window_arg(args.window)
+        except ValueError as e:
+            p.error("--window: %s" % e)
+        for on, flag in ((not args.generate, "--eval" if args.eval else "anything but --generate"), (args.batch > 1, "--batch"),
+                         (args.inflight > 1, "--inflight"), (args.per_channel, "--per-channel"), (args.members > 1, "--members"),
+                         (args.audit_range, "--audit-range"), (args.objective, "--objective")):
+            if on:
+                p.error("--window with %s: windowed passes enhance one file, one trajectory at a time" % flag)
     if args.objective and not args.eval:
         p.error("--objective evaluates a held-out set: it needs --eval")
     if args.draws < 1:
@@ -134,7 +153,8 @@ def main(argv=None):
         raise NotImplementedError("only ComplexDDPMTrainer's sampling path is built")
     trainer = ComplexDDPMTrainer(args, config)
     if args.generate:
-        return trainer.generate_wav(load_pre_train=True, data_path=args.data, batch=args.batch, inflight=args.inflight, members=args.members)
+        return trainer.generate_wav(load_pre_train=True, data_path=args.data, batch=args.batch, inflight=args.inflight, members=args.members,
+                                    window=args.window)
     res = trainer.train_ddpm()          # --eval: one validation epoch, or with --objective one of the denoising objective (raises NotImplementedError otherwise: training)
     import json
 

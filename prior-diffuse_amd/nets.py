@@ -229,6 +229,14 @@ class PlanBase:
         if self.plan is not None:
             self.plan.keep(self.ctx.keep, self.ctx.bank)
 
+    # ---- windowed passes (longplan.py) --------------------------
+    carries_state = False   # the network's reach into the past is a recurrent state that one window can hand to the next
+
+    def receptive_field(self):
+        """(H_left, H_right): the frames before and after frame t that output frame t of this network depends on, when that is
+        finite; None when the network looks at all frames (attention, a bidirectional recurrence) and cannot run in windows."""
+        return None
+
     # ---- descriptor helpers -------------------------------------------------
     def src(self, t, C_, sb, sc, st, sf, off=0, act=L.ACT_NONE, blk=0):
         return L.Src(Ctx.ptr(t, off), sb, sc, st, sf, C_, act, blk, 0)
@@ -369,6 +377,7 @@ class EpsNetPlan(PlanBase):
     # in 0.69 of the three-plane form's time, parity margins equal or better)
     planes = 2
     TCM_F16 = True          # with planes 2 the TCM stack runs its two-plane form too (False: it keeps the three-plane split)
+    TCM_STACKS, TCM_DILATIONS = 3, (1, 2, 4, 8, 16, 32)   # model/diff3.py:260-277: 3 x residual(d = 1 .. 32)
     NSLOT = 20  # 15 stages + en1 real-row bias + 4 composed encoder-stage-1 biases (l/r x frame >= 1 / frame 0)
 
     def __init__(self, ctx, sd, B, T, time_cond=True, nsteps=1, plan=None, table=None, with_pre=None, split_bf16=None,
@@ -459,6 +468,37 @@ class EpsNetPlan(PlanBase):
     def w(self, k):
         return P._np(self.sd[k])
 
+    def _tcm_names(self):
+        """(state_dict prefix, dilation) of every TCM residual block, in the order they run."""
+        return [("TCMs.%d.residual%d" % (i, j + 1), dil) for i in range(self.TCM_STACKS) for j, dil in enumerate(self.TCM_DILATIONS)]
+
+    def time_stages(self):
+        """Every stage of the network that reaches across frames, in the order they run, as (name, frames back, frames ahead) -
+        read from the layer table this builder records and from the kernel shapes in the state_dict:
+          encoder stage k    Conv2d (kt, kf) behind one pad frame on top (diff3.py:144-166): kt - 1 frames back
+          TCM block (p, d)   Conv1d(kernel K, dilation d, padding (K - 1) / 2 * d) in both branches: (K - 1) / 2 * d either way
+          decoder stage k    ConvTranspose2d (kt, kf) and Chomp_T(kt - 1) (diff3.py:298-304): kt - 1 frames back; the two decoders
+                             run side by side on the same input, so a stage counts once (the larger of the two)
+        The 1x1 convolutions, the folded BatchNorms, PReLU and the gates are per frame."""
+        st = []
+        for k in range(1, 6):
+            kt = max(self.w("en.conv%d.%s.weight" % (k, br)).shape[2] for br in ("l", "r"))
+            st.append(("en%d" % k, kt - 1, 0))
+        for p, dil in self._tcm_names():
+            K = max(self.w("%s.%s.2.weight" % (p, br)).shape[2] for br in ("mainbranch", "maskbranch"))
+            if K % 2 != 1:
+                raise ValueError("TCM block %s: an even kernel has no symmetric padding" % p)
+            st.append((p, (K - 1) // 2 * dil, (K - 1) // 2 * dil))
+        for k in (5, 4, 3, 2, 1):
+            kt = max(self.w("%s.de%d.0.%s.weight" % (de, k, br)).shape[2] for de in ("de_real", "de_imag") for br in ("l", "r"))
+            st.append(("de%d" % k, kt - 1, 0))
+        return st
+
+    def receptive_field(self):
+        """(H_left, H_right) in frames: the stages run one behind the other, so their reaches add (``time_stages``)."""
+        st = self.time_stages()
+        return sum(s_[1] for s_ in st), sum(s_[2] for s_ in st)
+
     def _stage_fold(self):
         """Per stage k: (W1 [32,Cin], b1 [32], Wtp [Cin,512], btp [Cin])."""
         st = []
@@ -521,6 +561,7 @@ class EpsNetPlan(PlanBase):
         d.wfT, d.bf = self.t_wfT.data_ptr(), self.t_bf.data_ptr()
         d.out, d.temb = self.tbias.data_ptr(), self.temb.data_ptr()
         d.B, d.NF, d.max_steps = self.nsteps * self.B, self.NSLOT * 32, 50
+        self.time_index = len(self.descs)      # where the launch sits in the plan (a windowed pass runs it alone)
         self.add(d, TAG_EW)
 
     # ---- blocks -----------------------------------------------------------
@@ -999,7 +1040,7 @@ class EpsNetPlan(PlanBase):
             src_x, src_i = self.src(o, 64, *nchw(64, T, Fin)), None
         # TCMs over [B,256,T]
         cur, nxt = self.en[4], self.tcm_a
-        names = [("TCMs.%d.residual%d" % (i, j + 1), dil) for i in range(3) for j, dil in enumerate((1, 2, 4, 8, 16, 32))]
+        names = self._tcm_names()
         if self.force_generic or not self.fused_tcm:
             for p, dil in names:
                 self._residual(p, dil, cur, nxt)
@@ -1095,15 +1136,29 @@ class GcrnPlan(PlanBase):
     PERSIST_MAX_B = 4       # measured (tools/time_glstm.py --persist): 3.9 / 6.0 / 9.0 / 21.8 us per step at B = 1 / 2 / 4 / 8 against 11.4-12.0 for the wavefront
     ENC_C = [2, 16, 32, 64, 128, 256]
     ENC_F = [161, 80, 39, 19, 9, 4]
+    carries_state = True    # every convolution has a time kernel of 1 (gcrn.py: kernel_size (1, 3)); the grouped LSTM is causal
 
-    def __init__(self, ctx, sd, B, T, plan=None, split_bf16=None, exclusive=False, planes=None):
+    def receptive_field(self):
+        """(0, 0): no frame of the input but t itself reaches output frame t except through the LSTM's state (``carries_state``)."""
+        return 0, 0
+
+    def __init__(self, ctx, sd, B, T, plan=None, split_bf16=None, exclusive=False, planes=None, carry_state=False):
         """planes 3 / 2: the fp32-equivalent operand splits of the GEMM-shaped convolutions (bf16x3: korder 3; f16x2: korder 5, the
         default); planes 1: the opt-in bf16 mode - the gated (transposed) convolutions and the LSTM input projection multiply plain
         bf16 operands (csrc/gconv4.hip, korder 4); tensors, LSTM and the last stage stay fp32.
         exclusive: nothing else runs on the GPU beside this plan (one batch in flight) - the condition under which the
         persistent LSTM may be used (its 256 workgroups wait for each other and must all be resident).  Off by default: a
         plan built with it takes another LSTM kernel at B <= PERSIST_MAX_B than at larger B, so an utterance's result is
-        within 1e-5 of, not bit-identical to, the same utterance in a larger batch or shard."""
+        within 1e-5 of, not bit-identical to, the same utterance in a larger batch or shard.
+        carry_state: the plan of one window of a long recording: the grouped LSTM takes the wavefront form, whatever
+        ``exclusive`` says, and is recorded with ``state_in`` / ``state_out`` (pdse_glstm_desc: h and c of both layers and groups) -
+        a run starts from what ``state_in`` holds (zeros: the start of a recording) and leaves its last frame's state in
+        ``state_out``; the caller copies one into the other between windows.  False (default): the fields stay NULL."""
+        self.carry_state = bool(carry_state)
+        if self.carry_state:
+            exclusive = False
+            if not self.fused_glstm or self.force_generic:
+                raise ValueError("carry_state needs the wavefront form of the grouped LSTM (csrc/lstm.hip: glstm_wave_kernel)")
         if split_bf16 is not None:
             self.split_bf16 = bool(split_bf16)
         if planes is not None:
@@ -1142,6 +1197,8 @@ class GcrnPlan(PlanBase):
         elif self.fused_glstm and not self.force_generic:
             self.hT2, self.cst2 = a(2, 2, 512, Bp, zero=True), a(2, 512, Bp, zero=True)
             self.gx2, self.part = a(R, 2, 2048, Bp, zero=True), a(R, 2, 64, Bp, 2, zero=True)
+            if self.carry_state:     # [4][G][H][Bp]: h1, c1, h2, c2
+                self.state_in, self.state_out = a(4, 2, 512, Bp, zero=True), a(4, 2, 512, Bp, zero=True)
         else:
             self.yn = a(B, 1024, T)
         self.glstm = a(B, 256, T, 4)
@@ -1221,6 +1278,8 @@ class GcrnPlan(PlanBase):
         d.slices = 2 if self.exclusive else 1     # a plan that owns the GPU: two slices per workgroup share one fetch of the state (bit-identical)
         if self.chunk:                             # same packed operands: the chunk projection walks K in stage B's order
             d.tc, d.lag = self.CHUNK_TC, self.CHUNK_TC + 1
+        if self.carry_state:
+            d.state_in, d.state_out = self.state_in.data_ptr(), self.state_out.data_ptr()
         self.add(d, TAG_LSTM)
 
     def _glstm_persistent(self, proj1):

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import nets, packing, rangeaudit
+from . import longplan, nets, packing, rangeaudit
 from .params import PRIOR_SCALE_C, params as default_params
 from .schedule import inference_schedule, step_coefficients
 
@@ -62,7 +62,8 @@ class SamplerPipeline:
     def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, T=None, L_=None, fast_sampling=True,
                  use_sigma=False, params=default_params, with_signal=None, deltamu=False, cond="init", bank=None,
                  split_bf16=None, xT_plus_init=None, dtype="f32", exclusive=False, split=None, audit=False, ragged=False,
-                 verdict=False, masked_prior=False, label=False, objective=False, feat_type="sqrt", members=1):
+                 verdict=False, masked_prior=False, label=False, objective=False, feat_type="sqrt", members=1, window=None,
+                 carry_state=False):
         """deltamu: the alternative parameterisation of utils/params.py:36 — ddpm_sd is a ``Nocon`` state_dict,
         x_T = noise + X_init/11 (:947-948), eps = Nocon(x, t) (:970-971), no final ``+ X_init`` (:995).
         cond (deltamu False): what conditions DiffUNet1 — "init": X_init/11 (pirorgrad, :967-969, + X_init at the end,
@@ -154,8 +155,34 @@ class SamplerPipeline:
         ranges "step0" and "istft", so ``graph=True`` is a ValueError), which also leaves ``ensemble``: ``spread`` [B,T,161],
         ``per_utt`` [B,2] and ``per_member`` [K,B] (``ops.ensemble_stats``).  With ``label``, all five ``feat_type`` values,
         ``use_sigma``, the three conditioning branches and every arithmetic; with ``ragged``, ``verdict`` or ``objective``:
-        ValueError, and plan files do not carry it.  1 (default): the plan is launch for launch and field for field today's."""
+        ValueError, and plan files do not carry it.  1 (default): the plan is launch for launch and field for field today's.
+        window: W frames (a multiple of ``longplan.FRAME_TILE``; needs L_): recordings of any length through ONE plan of W frames
+        (DESIGN.md 4.13).  With T = 1 + L_ // 160 <= W the pipeline is the whole-file one, launch for launch.  With T > W it
+        records no whole-file network plan at all: ``self.long`` is a ``LongSampler`` and ``enhance`` runs its windowed pass, whose
+        results are the whole-file plan's (built with ``exclusive=False``).  Priors GCRN (its LSTM state carried from window to
+        window) and DiffUNet (halos); the DB-AIAT priors attend over all frames: ValueError.  With ``ragged``, ``members`` > 1,
+        ``verdict``, ``label``, ``objective`` or ``audit``: ValueError; plan files do not carry it.  None (default): off.
+        carry_state: this pipeline is the window plan of a ``LongSampler`` - a GCRN prior is recorded with the LSTM's state
+        fields (``nets.GcrnPlan(carry_state=True)``).  False (default): launch for launch today's."""
         objective = bool(objective)
+        self.window = longplan.window_arg(window)
+        self.long = None
+        if self.window is not None:
+            if L_ is None:
+                raise ValueError("window= needs the signal front / back end (pass L_)")
+            longplan.window_conflicts(ragged=ragged, members=members, verdict=verdict, label=label, objective=objective)
+            if audit:
+                raise ValueError("window= with audit=True: the range audit reads one recorded plan's table")
+            LongSampler.prior_check(prior_name)
+            if 1 + L_ // 160 > self.window:
+                self.long = LongSampler(device, prior_name, prior_sd, ddpm_sd, B, self.window, fast_sampling=fast_sampling,
+                                        use_sigma=use_sigma, params=params, deltamu=deltamu, cond=cond, bank=bank, split_bf16=split_bf16,
+                                        xT_plus_init=xT_plus_init, dtype=dtype, split=split, feat_type=feat_type)
+                self.B, self.T, self.L, self.device, self.members = B, 1 + L_ // 160, L_, torch.device(device), 1
+                self.bank, self.split, self.dtype, self.plan = self.long.bank, self.long.win.split, dtype, None
+                self.audit = self.audited = self.verdict = False
+                self.label = self.objective = self.stft = None
+                return
         self.members = K = L.members_arg(members)
         if K > 1:
             for flag, name in ((ragged, "ragged"), (verdict, "verdict"), (objective, "objective")):
@@ -224,7 +251,7 @@ class SamplerPipeline:
         pplanes = nplanes if (split_bf16 or dtype == "bf16") else None
         if prior_name == "GCRN":
             self.prior = adopt(nets.GcrnPlan(ctx, prior_sd, B, T, plan=self.plan, split_bf16=split_bf16 or dtype == "bf16", exclusive=exclusive,
-                                             planes=pplanes))
+                                             planes=pplanes, carry_state=carry_state))
         elif prior_name == "DiffUNet":
             self.prior = adopt(nets.EpsNetPlan(ctx, prior_sd, B, T, time_cond=False, plan=self.plan, split_bf16=split_bf16, exclusive=exclusive,
                                                frames=self.frames_tab))
@@ -421,8 +448,15 @@ class SamplerPipeline:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def _whole_file_only(self, what):
+        """A pipeline built with ``window=W`` for more than W frames holds a ``LongSampler`` and no whole-file plan."""
+        if getattr(self, "long", None) is not None:
+            raise ValueError("%s on a pipeline built with window=%d for %d frames: it records no whole-file plan - enhance() and "
+                             "check() run the windowed pass (self.long)" % (what, self.window, self.T))
+
     def run(self, first=None, last=None, graph=False):
         """Run ranges first..last (names from ``self.ranges``), whole plan by default."""
+        self._whole_file_only("run")
         if graph:
             self._members_xT(None, True)          # an ensemble plan: ValueError
         if self.plan is None:
@@ -464,6 +498,7 @@ class SamplerPipeline:
         The report is that of the last ``run()`` call: every call starts from a cleared table, and only the rows of the marked
         ranges that call executed are reported (a pipeline stepped range by range reports the last range; rows of ranges that
         did not run would be all-zero and read as clean)."""
+        self._whole_file_only("range_report")
         if not self.audit:
             raise ValueError("the pipeline was built without the range audit (SamplerPipeline(audit=True))")
         if not self.audited:
@@ -516,6 +551,8 @@ class SamplerPipeline:
         result is not finite: an activation left the top of the fp16 window (``PdseRangeError``; an audited pipeline names the
         tensor).  audit=True (pipelines built with ``audit=True``): also reads the range report and raises ``PdseRangeError``
         naming the first tensor, and its marked range, that lay wholly below the window - the case that leaves no other trace."""
+        if getattr(self, "long", None) is not None:
+            return self.long.check()
         for net, field, what in ((self.prior, "status", "persistent LSTM gave up at step %d"), (self.eps, "tcm_status", "TCM stack launch gave up at block %d"),
                                  (self.prior, "tcm_status", "TCM stack launch of the prior gave up at block %d")):
             st = getattr(net, field, None)
@@ -543,6 +580,7 @@ class SamplerPipeline:
     def sample(self, feat, x_T, graph=False):
         """feat, x_T [B,2,T,161] -> (enhanced compressed spectrogram, X_init); the
         spectrogram-level body of generate_wav (:939-998)."""
+        SamplerPipeline._whole_file_only(self, "sample")
         if self.xT_in is None:
             raise ValueError("an objective plan has no sampler (SamplerPipeline(objective=True): objective_pass)")
         x_T = SamplerPipeline._members_xT(self, x_T, graph)    # not a bound call: the argument checks run on any object with the fields
@@ -600,7 +638,12 @@ class SamplerPipeline:
         rescaled by c).  The returned pair is what it is without ``clean``.
         Pipelines built with ``members=K`` > 1: x_T is [K,B,2,T,161] or [K B,2,T,161], member-major; the returned pair is the
         ensemble mean's - ``spec`` and the waveform the back end makes of it - and the pass leaves ``members_spec`` and
-        ``ensemble`` (its masked sums over ``1 + lens[b] // 160`` frames); ``graph=True``: ValueError."""
+        ``ensemble`` (its masked sums over ``1 + lens[b] // 160`` frames); ``graph=True``: ValueError.
+        Pipelines built with ``window=W`` for more than W frames: the windowed pass (``LongSampler.enhance``); ``graph``, ``lens``,
+        ``exact`` and ``clean`` are then refused."""
+        if getattr(self, "long", None) is not None:     # (the argument checks below run on any object with the fields)
+            longplan.window_conflicts(graph=graph, ragged=exact or lens is not None, label=clean is not None)
+            return self.long.enhance(wav, x_T)
         if self.stft is None:
             raise ValueError("pipeline was built without the signal front/back end (pass L_)")
         if self.xT_in is None:
@@ -943,3 +986,170 @@ class PipelinedSampler:
         for e in self.done:
             if e is not None:
                 cur.wait_event(e)
+
+
+class LongSampler:
+    """Recordings of any length through ONE window plan (``SamplerPipeline(window=W)``, ``ComplexDDPMTrainer(window=W)``).
+
+    What grows with the frame count T and is small stays whole-file, in buffers re-made when the length changes: the waveforms, the
+    [B,2,T,161] spectrograms (feature, X_init, X_init / 11, x_T, two copies of x_t, the result) and the front / back end with its
+    frame GEMMs, recorded per length exactly as ``SamplerPipeline`` records them.  The two networks exist once, as ``win``: a
+    ``SamplerPipeline`` of W frames without the signal ends, ``exclusive=False``, whose activation set serves every window, every
+    step and every file.  One pass:
+
+        front      wav prep, STFT, compression                          whole-file plan, as ever
+        prior      GCRN: consecutive windows (``longplan.carried``), the LSTM's h and c handed from each to the next
+                   (pdse_glstm_desc.state_in / state_out; zeros at the start of the file)
+                   DiffUNet: windows with halos (``longplan.windows`` at the prior's receptive field)
+        prologue   X_init / 11, x_T (+ X_init / 11), the --sigma mask   whole-file launches of the operators the one-plan pass
+                   records: the mask's per-utterance maximum is taken over the whole file, once
+        steps      step-major: for n = S-1 .. 0, for every window (``longplan.windows`` at the eps-net's receptive field):
+                   gather x_n and the condition, one eps-net step and the update on the window, scatter of the kept frames of
+                   x_{n-1} into the second whole-file buffer; then the buffers swap.  The field is two-sided, so a window needs
+                   x_n of frames a later window owns: no window may run ahead of the others.
+        back       decompression, inverse frames, overlap-add            whole-file plan, as ever
+
+    pdse_window_gather / pdse_window_scatter (csrc/window.hip) move the frames.  The priors that attend over all frames have no
+    receptive field (``prior_check``: ValueError)."""
+
+    @staticmethod
+    def prior_check(prior_name):
+        if prior_name not in ("GCRN", "DiffUNet"):
+            raise ValueError("window=: prior %r attends and runs a bidirectional GRU over all T frames, it has no finite receptive "
+                             "field and no state to carry (supported priors: GCRN, DiffUNet)" % prior_name)
+
+    def __init__(self, device, prior_name, prior_sd, ddpm_sd, B, window, fast_sampling=True, use_sigma=False, params=default_params,
+                 deltamu=False, cond="init", bank=None, split_bf16=None, xT_plus_init=None, dtype="f32", split=None, feat_type="sqrt"):
+        self.prior_check(prior_name)
+        self.W = W = longplan.window_arg(window)
+        if W is None:
+            raise ValueError("LongSampler needs a window length")
+        self.device = torch.device(device)
+        self.B, self.prior_name, self.use_sigma, self.feat_type = B, prior_name, bool(use_sigma), L.feat_type_of(feat_type)
+        self.win = win = SamplerPipeline(device, prior_name, prior_sd, ddpm_sd, B, T=W, with_signal=False, fast_sampling=fast_sampling,
+                                         use_sigma=False, params=params, deltamu=deltamu, cond=cond, bank=bank, split_bf16=split_bf16,
+                                         xT_plus_init=xT_plus_init, dtype=dtype, exclusive=False, split=split, carry_state=True)
+        self.bank = win.bank
+        sb = bool(fast_sampling) if split_bf16 is None else split_bf16      # as SamplerPipeline hands it to its front and back end
+        self._split_front, self._split_back = sb, True if dtype == "bf16" else sb
+        self.eps_field = win.eps.receptive_field()
+        self.prior_field = win.prior.receptive_field()
+        self.carried = bool(win.prior.carries_state)
+        longplan.windows(W + 1, W, *self.eps_field)                          # ValueError: W does not exceed the field
+        if not self.carried:
+            longplan.windows(W + 1, W, *self.prior_field)
+        self.nsteps = win.nsteps
+        self._time = win.eps.time_index                                       # the launch of the steps' folded time biases
+        self.L = self.T = None
+        self.spec = None
+
+    # ------------------------------------------------------------------
+    def _whole(self, L_):
+        """The whole-file side for recordings of L_ samples: buffers and the front / back end, re-made when the length changes."""
+        if self.L == L_:
+            return
+        win, B = self.win, self.B
+        T = 1 + L_ // 160
+        ctx = nets.Ctx(self.device, self.bank)
+        self.stft = nets.StftPlan(ctx, B, L_, split_bf16=self._split_front, feat_type=self.feat_type)
+        self.istft = nets.IstftPlan(ctx, B, T, L_, split_bf16=self._split_back, feat_type=self.feat_type)
+        a = ctx.alloc
+        self.feat, self.xinit, self.init, self.xT_in = a(B, 2, T, F0), a(B, 2, T, F0), a(B, 2, T, F0), a(B, 2, T, F0)
+        self.x = [a(B, 2, T, F0), a(B, 2, T, F0)]
+        self.featc = a(B, 2, T, F0) if win.cond_feat else None
+        self.spec = self.istft.spec
+        self.stft.build(feat=self.feat)
+        self.istft.build(spec=self.spec, c=self.stft.c)
+        # the prologue of the one-plan pass (SamplerPipeline.__init__: prologue) on the whole-file tensors
+        pro = self.pro = nets.PlanBase(ctx)
+        n = B * 2 * T * F0
+
+        def ew(op, a_, b=None, out=None, s0=0.0):
+            d = L.EwDesc()
+            d.a, d.b, d.c, d.out = a_.data_ptr(), nets.Ctx.ptr(b), 0, out.data_ptr()
+            d.n, d.s0, d.s1, d.s2, d.op = n, s0, 0.0, 0.0, op
+            pro.add(d, nets.TAG_EW)
+
+        ew(L.EW_DIV, self.xinit, out=self.init, s0=PRIOR_SCALE_C)
+        if win.cond_feat:
+            ew(L.EW_DIV, self.feat, out=self.featc, s0=PRIOR_SCALE_C)
+        src = self.xT_in
+        if win.xT_plus_init:
+            ew(L.EW_ADD_MUL, self.xT_in, b=self.init, out=self.x[0], s0=1.0)
+            src = self.x[0]
+        if self.use_sigma:
+            d = L.SigmaDesc()
+            d.init, d.a, d.out = self.init.data_ptr(), src.data_ptr(), self.x[0].data_ptr()
+            d.maxbuf = ctx.alloc(B * 2).data_ptr()
+            d.plane, d.nplanes, d.valid = T * F0, B * 2, 0
+            pro.add(d, nets.TAG_EW)
+        elif not win.xT_plus_init:
+            ew(L.EW_COPY, self.xT_in, out=self.x[0])
+        for pb in (self.stft, self.istft, pro):
+            pb.finish()
+        self.ctx, self.L, self.T = ctx, L_, T
+        self.eps_windows = longplan.windows(T, self.W, *self.eps_field)
+        self.prior_windows = longplan.carried(T, self.W) if self.carried else longplan.windows(T, self.W, *self.prior_field)
+
+    def activation_bytes(self):
+        """(window plan, whole-file side) bytes of per-plan device memory - weights excluded; the second grows with T."""
+        size = lambda ctx: sum(t.numel() * t.element_size() for t in ctx.keep if torch.is_tensor(t))   # noqa: E731
+        return size(self.win.ctx), size(self.ctx) if self.L is not None else 0
+
+    def _gather(self, whole, winbuf, a, stream):
+        L.window_gather(whole.data_ptr(), winbuf.data_ptr(), self.B, 2, self.T, F0, self.W, a, stream, device=self.device)
+
+    def _scatter(self, winbuf, whole, a, lo, hi, stream):
+        L.window_scatter(winbuf.data_ptr(), whole.data_ptr(), self.B, 2, self.T, F0, self.W, a, lo, hi, stream, device=self.device)
+
+    def enhance(self, wav, x_T):
+        """wav [B,L], x_T [B,2,T,161] with T = 1 + L // 160 > W -> (enhanced wav [B,L], spectrogram [B,2,T,161]): what a
+        whole-file ``SamplerPipeline(exclusive=False)`` of that length returns.  Nothing is synchronised."""
+        win = self.win
+        if wav.dim() != 2 or wav.shape[0] != self.B:
+            raise ValueError("wav: expected [%d, L], got %s" % (self.B, tuple(wav.shape)))
+        L_ = int(wav.shape[1])
+        if 1 + L_ // 160 <= self.W:
+            raise ValueError("a recording of %d frames fits the window of %d: it takes the whole-file plan" % (1 + L_ // 160, self.W))
+        self._whole(L_)
+        _expect(wav, self.stft.wav, "wav")
+        _expect(x_T, self.xT_in, "x_T")
+        self.stft.wav.copy_(wav)
+        self.xT_in.copy_(x_T)
+        self.stft.lens.fill_(L_)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.stft.plan.run(stream)
+        # ---- prior
+        prior = win.prior
+        if self.carried:
+            prior.state_in.zero_()
+        for a, lo, hi in self.prior_windows:
+            self._gather(self.feat, win.feat, a, stream)
+            win.plan.run_range(*win.ranges["prior"], stream)
+            self._scatter(prior.out, self.xinit, a, lo, hi, stream)
+            if self.carried:
+                prior.state_in.copy_(prior.state_out)
+        # ---- prologue on the whole file, and the steps' time biases
+        self.pro.plan.run(stream)
+        win.plan.run_range(self._time, self._time + 1, stream)
+        cond = None if win.deltamu else (self.featc if win.cond_feat else self.init)
+        # the last step adds X_init / 11 back where the window plan does (win.zero None): it is the gathered condition
+        cur, nxt = self.x
+        for nstep in range(self.nsteps - 1, -1, -1):
+            rng = win.ranges["step%d" % nstep]
+            dst = nxt if nstep else self.spec
+            for a, lo, hi in self.eps_windows:
+                self._gather(cur, win.audio, a, stream)
+                if cond is not None:
+                    self._gather(cond, win.eps.x_init, a, stream)
+                win.plan.run_range(*rng, stream)
+                self._scatter(win.audio if nstep else win.members_spec, dst, a, lo, hi, stream)
+            cur, nxt = nxt, cur
+        self.istft.plan.run(stream)
+        return self.istft.wav.clone(), self.spec.clone()
+
+    def check(self):
+        """Synchronises; raises ``PdseRangeError`` if an f16x2 pass left a non-finite spectrogram (``SamplerPipeline.check``).
+        (``SamplerPipeline.windowed`` is the older name of "has an fp16 range to leave" and has nothing to do with frame windows.)"""
+        if self.win.windowed and not bool(torch.isfinite(self.spec).all()):
+            raise SamplerPipeline.nonfinite_error()

@@ -126,6 +126,9 @@ def save_pipeline(path, pipe):
     x_T [B,2,T,161], wav_out [B,L], spec [B,2,T,161].  The true lengths are stored as the pipeline holds them (full length).
     A pipeline built with ``audit=True`` on f16x2 operands also carries its range audit: region range_hist, uint32 [rows][32]
     (rows: ``pipe.range_rows`` in order, then unused ones up to the region's size), cleared and filled by every run."""
+    if getattr(pipe, "window", None) is not None:
+        raise ValueError("plan files hold one recorded plan: a pipeline built with window=%d runs a host loop around a window plan "
+                         "(pdse_window_gather / pdse_window_scatter are plain-argument calls)" % pipe.window)
     if pipe.stft is None:
         raise ValueError("the pipeline was built without the signal front / back end (pass L_)")
     if getattr(pipe, "ragged", False):

@@ -24,9 +24,9 @@ from itertools import chain
 import torch
 
 from . import _lib as L
-from . import nets, ops, raggedplan, wavdev, wavio
+from . import longplan, nets, ops, raggedplan, wavdev, wavio
 from .params import PRIOR_SCALE_C, params as default_params
-from .pipeline import RAGGED_PRIORS, SamplerPipeline, _expect, ragged_args
+from .pipeline import RAGGED_PRIORS, LongSampler, SamplerPipeline, _expect, ragged_args
 from .schedule import inference_schedule as _inference_schedule
 
 
@@ -79,7 +79,7 @@ class ComplexDDPMTrainer(object):
     channels = "mix"       # what generate_wav enhances of a multichannel file: "mix" (the mono mix) or "each" (every channel)
 
     def __init__(self, args, config, device=None, prior_state_dict=None, ddpm_state_dict=None, params=None, exclusive=None,
-                 dtype=None, split=None, audit=None, masked_prior=None, wav_formats=None, wav_out=None, channels=None):
+                 dtype=None, split=None, audit=None, masked_prior=None, wav_formats=None, wav_out=None, channels=None, window=None):
         """args: .retrain .joint .draw .sigma .checkpoint .generated_wav
         config: .model.name, .train.{fft_num, win_size, win_shift, feat_type}.  feat_type: the spectral compression the
         checkpoint was trained with - "sqrt", "normal", "cubic", "log_1x" or "none" (``SamplerPipeline(feat_type=...)``; any other
@@ -138,7 +138,13 @@ class ComplexDDPMTrainer(object):
         at B <= 4 may take the persistent launch.  A seeded run on a stereo file draws what the same run draws on its two
         channels stored as mono files that sort next to each other.  Mono files behave exactly as under "mix"; a source with
         more than 8 channels is enhanced as the mix and written as under "mix" (logged).  No x_T is shared between channels, and
-        the metrics score the mix.  None: "each" when the CLI set ``args.per_channel`` (``main.py --per-channel``), else "mix"."""
+        the metrics score the mix.  None: "each" when the CLI set ``args.per_channel`` (``main.py --per-channel``), else "mix".
+        window: W frames (a multiple of ``longplan.FRAME_TILE``): ``enhance`` and ``generate_wav`` send a recording of more than W
+        frames through the windowed pass (``pipeline.LongSampler``) - one window plan per batch size, whatever the
+        lengths - with the results of an ``exclusive=False`` trainer's whole-file pass; shorter recordings take today's path.
+        Priors GCRN and DiffUNet; with ``channels="each"`` or ``audit=True``: ValueError.  None: ``args.window``
+        (``main.py --window``), else off."""
+        self.window = longplan.window_arg(getattr(args, "window", None) if window is None else window)
         if channels is None:
             channels = "each" if getattr(args, "per_channel", False) else "mix"
         if channels not in ("mix", "each"):
@@ -199,6 +205,11 @@ class ComplexDDPMTrainer(object):
             raise NotImplementedError("prior %r: built priors are %s" % (self.prior_name, sorted(ops.PRIOR_OPS)))
         self.prior_sd, self.ddpm_sd = prior_state_dict, ddpm_state_dict
         self._streaming = False           # enhance_stream: one stream per trainer at a time
+        if self.window is not None:
+            LongSampler.prior_check(self.prior_name)
+            longplan.window_conflicts(per_channel=self.channels == "each")
+            if self.audit:
+                raise ValueError("window= with audit=True: the range audit reads one recorded plan's table")
         if getattr(self.args, "retrain", False):                      # :91-97
             self._load_checkpoint()
         else:
@@ -232,6 +243,7 @@ class ComplexDDPMTrainer(object):
         self._slots = []                  # enhance_stream: one stream and a few recorded geometries per item in flight
         self._range_fallback = set()      # geometries whose f16x2 pass left the fp16 window once: they run on the three-plane bf16 split (_checked)
         self._audit_clean = set()         # geometries whose audited f16x2 pass came back clean once: their report is not read again
+        self._long = {}                   # windowed passes: ("long", B, W, sigma, fast sampling, split) -> LongSampler
 
     _hits = property(lambda self: self._pipes.hits)
 
@@ -346,6 +358,7 @@ class ComplexDDPMTrainer(object):
         (``exclusive=True``) takes the persistent LSTM at B <= 4 in ``enhance``, which is 1e-5 from these kernels and not
         bit-identical to them.  (Measured limit, DESIGN.md 4.9: at T = 401 three B = 1 graph replays sharing the GPU differed from
         the sequential pass in a few of 192 passes, with and without the verdict; the tests hold T <= 21 to ``torch.equal``.)"""
+        self._no_window("enhance_stream")
         inflight = _inflight_arg(inflight)
         if self.audit:
             raise ValueError("enhance_stream on a trainer built with audit=True: the range audit reads a report per pass")
@@ -456,6 +469,7 @@ class ComplexDDPMTrainer(object):
 
     def sample(self, feat, x_T=None, verify=True, members=1):
         """feat [B,2,T,161] compressed spectrogram -> enhanced compressed spectrogram.  verify, members: see ``enhance``."""
+        self._no_window("sample")
         members = L.members_arg(members)
         feat = feat.to(self.device)
         B, _, T, _ = feat.shape
@@ -464,7 +478,41 @@ class ComplexDDPMTrainer(object):
             return self._pipe(B, T=T, members=members).sample(feat, x_T)[0]
         return self._checked(lambda pipe, graph: pipe.sample(feat, x_T)[0], B=B, T=T, members=members)     # never replayed
 
-    def enhance(self, wav, x_T=None, verify=True, members=1):
+    def _no_window(self, entry):
+        """A trainer built with ``window=W`` runs windowed passes through ``enhance`` and ``generate_wav`` only: every other entry
+        point records whole-file plans and would silently ignore the option - ValueError instead, as ``members`` does it."""
+        if getattr(self, "window", None) is not None:
+            raise ValueError("%s on a trainer built with window=%d: windowed passes enhance one padded batch, one trajectory, one file "
+                             "at a time through enhance() and generate_wav(); build a trainer without window= for %s"
+                             % (entry, self.window, entry))
+
+    def _long_sampler(self, B, W):
+        """The windowed sampler of batch size B and window W: one per trainer and operand split, whatever the lengths
+        (``pipeline.LongSampler``).  A geometry whose f16x2 pass left the fp16 range once stays on "bf16x3" (``_range_fallback``)."""
+        geom = ("long", B, W, bool(getattr(self.args, "sigma", False)), bool(self.params.fast_sampling))
+        key = geom + (self._split_of(geom, self.split),)
+        if key not in self._long:
+            self._long[key] = LongSampler(self.device, self.prior_name, self.prior_sd, self.ddpm_sd, B, W,
+                                          fast_sampling=self.params.fast_sampling, use_sigma=geom[3], params=self.params,
+                                          deltamu=self.deltamu, cond=self.cond, bank=self.bank, xT_plus_init=self.xT_plus_init,
+                                          dtype=self.dtype, split=key[-1], feat_type=self.feat_type)
+        return self._long[key], geom
+
+    def _enhance_long(self, wav, x_T, W, verify):
+        long, geom = self._long_sampler(wav.shape[0], W)
+        out = long.enhance(wav, x_T)[0]
+        if verify:
+            try:
+                long.check()
+            except L.PdseRangeError as e:
+                logging.warning("%s - repeating the windowed pass with split='bf16x3'", e)
+                self._range_fallback.add(geom)
+                long, _ = self._long_sampler(wav.shape[0], W)
+                out = long.enhance(wav, x_T)[0]
+                long.check()
+        return out
+
+    def enhance(self, wav, x_T=None, verify=True, members=1, window=None):
         """wav [B,L] (any scale; RMS-normalised internally like :922-923) -> enhanced [B,L].
         verify (default): the pass is checked before its result is handed out (one synchronisation: persistent launches that
         gave up, and - f16x2 operands - an activation outside the fp16 window, in which case the geometry is repeated on the
@@ -473,12 +521,22 @@ class ComplexDDPMTrainer(object):
         (``SamplerPipeline(members=K)``); the result is the ensemble mean - taken in the compressed domain, then decompressed
         and inverted by the back end as ever.  x_T: [K,B,2,T,161] or [K B,2,T,161], member-major; None: K consecutive draws of
         [B,2,T,161], what K one-member calls draw.  Never replayed from a hipGraph.  1 (default): today's pass.
-        ``enhance_members`` returns the members, the spread map and the sums as well."""
+        ``enhance_members`` returns the members, the spread map and the sums as well.
+        window: W frames (None: the trainer's ``window``): a recording of more than W frames takes the windowed pass - see the
+        constructor; x_T is drawn for the whole file as ever.  With ``members`` > 1: ValueError."""
         members = L.members_arg(members)
+        window = getattr(self, "window", None) if window is None else longplan.window_arg(window)
         wav = wav.to(self.device, torch.float32)
         B, L_ = wav.shape
         T = 1 + L_ // 160
+        if window is not None:
+            longplan.window_conflicts(members=members, per_channel=self.channels == "each")
+            LongSampler.prior_check(self.prior_name)
+            if self.audit:
+                raise ValueError("window= with audit=True: the range audit reads one recorded plan's table")
         x_T = self._x_T((B, 2, T, 161), x_T, members)
+        if window is not None and T > window:
+            return self._enhance_long(wav, x_T, window, verify)
         # a geometry that comes back is replayed (``_plan``); an ensemble pass never is
         run = lambda pipe, graph: pipe.enhance(wav, x_T, graph=graph and members == 1)[0]   # noqa: E731
         if not verify:
@@ -493,6 +551,7 @@ class ComplexDDPMTrainer(object):
         bin), ``per_utt`` [B,2] and ``per_member`` [K,B] (float64 sums, ``ops.ensemble_stats``) and ``relative_spread`` [B] =
         sqrt(per_utt[b][0] / (K - 1) / per_utt[b][1]), the ensemble's standard deviation over the norm of its mean (zeros for
         K = 1).  Verified like ``enhance``.  members 1 is allowed: one member, zero spread."""
+        self._no_window("enhance_members")
         members = L.members_arg(members)
         wav = wav.to(self.device, torch.float32)
         B, L_ = wav.shape
@@ -524,6 +583,7 @@ class ComplexDDPMTrainer(object):
         own shape, in list order - the draws of the B = 1 calls.
         members: K > 1 returns the ensemble mean of K trajectories of the padded batch (``enhance``; x_T [K,B,2,T,161] or
         [K B,2,T,161]); with exact=True: ValueError (an exact ragged plan runs one trajectory)."""
+        self._no_window("enhance_batch")
         members = L.members_arg(members)
         wavs = [torch.as_tensor(w, dtype=torch.float32).flatten() for w in wavs]
         lens = [int(w.numel()) for w in wavs]
@@ -597,7 +657,8 @@ class ComplexDDPMTrainer(object):
         return enhanced, scores
 
     # ---- A2..A7: the reference's entry point --------------------------------
-    def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True, batch=1, inflight=1, members=1):
+    def generate_wav(self, load_pre_train=True, data_path="data/noisy_testset_wav", rng_fidelity=True, batch=1, inflight=1, members=1,
+                     window=None):
         """Per-file B=1 enhancement of ``data_path/*.wav`` into ``args.generated_wav``
         (:903-1018).  Returns the list of written paths instead of calling exit().
 
@@ -636,9 +697,17 @@ class ComplexDDPMTrainer(object):
         ``<args.log>/ensemble.json`` (``args.log``: ``<assets>/log/<doc>``; beside the written files where the arguments have
         none) then holds, per file, ``relative_spread`` and ``medoid``, the index of the member nearest the mean (the argmin of
         ``per_member``).  One file per pass: with ``batch`` > 1, ``inflight`` > 1, ``channels="each"`` or an ``audit=True``
-        trainer: ValueError."""
+        trainer: ValueError.
+
+        window (default None: the trainer's ``window``): W frames - a file of more than W frames takes the windowed pass
+        (``enhance(window=W)``): one window plan serves a directory of recordings of any lengths.  Same draws, same names.  One
+        file per pass: with ``batch`` > 1, ``inflight`` > 1, ``members`` > 1 or ``channels="each"``: ValueError."""
         inflight = _inflight_arg(inflight)
         members = L.members_arg(members)
+        window = getattr(self, "window", None) if window is None else longplan.window_arg(window)
+        if window is not None:
+            longplan.window_conflicts(ragged=int(batch) > 1, inflight=inflight, members=members, per_channel=self.channels == "each")
+            LongSampler.prior_check(self.prior_name)
         if inflight > 1 and int(batch) > 1:
             raise ValueError("generate_wav: inflight > 1 runs one file per pass (batch=1); streams of ragged windows are not built")
         if members > 1:
@@ -665,7 +734,7 @@ class ComplexDDPMTrainer(object):
             with open(os.path.join(log, "ensemble.json"), "w") as f:
                 json.dump({"members": members, "files": report}, f, indent=1)
             return written
-        return self._file_loop(data_path, rng_fidelity, one_by_one, partial(self._enhance_files, inflight=inflight))
+        return self._file_loop(data_path, rng_fidelity, one_by_one, partial(self._enhance_files, inflight=inflight, window=window))
 
     def _enhance_ensembles(self, windows, members, report):
         """``_file_loop``'s files one per pass as K-member ensembles: the file from the mean, its figures into ``report``."""
@@ -708,14 +777,15 @@ class ComplexDDPMTrainer(object):
         print("success!")
         return written
 
-    def _enhance_files(self, windows, inflight):
+    def _enhance_files(self, windows, inflight, window=None):
         """``_file_loop``'s files one per pass: through ``enhance`` (verified: ``SamplerPipeline.check()``, f16x2 window fallback)
         or, ``inflight`` > 1, through ``enhance_stream``, which asks for a file as a slot comes free."""
         files = chain.from_iterable(windows)
         if inflight == 1:
             for path, wav, x_T in files:
                 if wav.dim() == 1:
-                    yield path, self.enhance(wav[None], x_T=x_T)[0]
+                    # window None: the call as it always was
+                    yield path, (self.enhance(wav[None], x_T=x_T) if window is None else self.enhance(wav[None], x_T=x_T, window=window))[0]
                 else:                                # a file's channels: one exact ragged pass of equal lengths, nothing padded
                     yield path, torch.stack(self._enhance_ragged(list(wav), list(x_T), wav.shape[1]))
             return
@@ -884,6 +954,7 @@ class ComplexDDPMTrainer(object):
         every member's own [B, 2, T, 161] block against the label (``ops.spec_losses``), with ``per_utt_by_member`` [K, B, 2], its
         numerators; ``loss_member_mean`` and ``loss_member_std`` (over the K members; the sample standard deviation) and
         ``relative_spread`` [B] (``enhance_members``).  With exact=True: ValueError."""
+        self._no_window("validate_batch")
         from . import metrics, validation as V
 
         members = L.members_arg(members)
@@ -1047,6 +1118,7 @@ class ComplexDDPMTrainer(object):
         before the division by 11 (:668).  tensors=True: also clones of ``noisy``, ``target``, ``predicted``, ``init`` and
         ``label`` (the last two divided by 11), for tests and debugging.  One synchronisation: the pass's own check
         (``_checked``)."""
+        self._no_window("objective_batch")
         from . import validation as V
 
         noisy, clean, lens = self._pairs(noisy_wavs, clean_wavs)
