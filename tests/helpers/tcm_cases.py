@@ -417,18 +417,19 @@ def check_fp32(what, got, ref64, ref32, frames):
     return err, e32
 
 
-def check_bf16(what, got, rnd64, rnd32, plain64, frames):
+def check_bf16(what, got, rnd64, rnd32, plain64, frames, div=16):
     """np = 1: rel_l2(result, bf16-rounding float64 reference) <= max(4 * e32, e_b / 16), e32 between the fp32 and the float64
-    rounding references, e_b = rel_l2(rounding reference, unrounded reference), both float64."""
+    rounding references, e_b = rel_l2(rounding reference, unrounded reference), both float64.  div: the divisor where it is
+    not this file's 16 (tests/test_gpu_bglu_ops.py states its own)."""
     got, rnd64, rnd32, plain64 = own(got, frames), own(rnd64, frames), own(rnd32, frames), own(plain64, frames)
     if rnd64.size == 0:
         return 0.0, 0.0, 0.0
     e_b = rel_l2(rnd64, plain64)                                                         # e_b: what the roundings of np = 1 cost
     e32 = rel_l2(rnd32, rnd64)                                                           # fp32 against float64, both rounding (flips included)
     err = rel_l2(got, rnd64)                                                             # bound: max(4 * e32, e_b / 16)
-    bound = max(4 * e32, e_b / 16)
-    print("%s: result %.3e  e_b %.3e  e_b/16 %.3e  fp32 cpu %.3e  bound %.3e  result/(e_b/16) %.2f" % (
-        what, err, e_b, e_b / 16, e32, bound, 16 * err / e_b if e_b else math.inf))
+    bound = max(4 * e32, e_b / div)
+    print("%s: result %.3e  e_b %.3e  e_b/%d %.3e  fp32 cpu %.3e  bound %.3e  result/(e_b/%d) %.2f" % (
+        what, err, e_b, div, e_b / div, e32, bound, div, div * err / e_b if e_b else math.inf))
     assert np.isfinite(err) and err <= bound, (what, err, e_b, e32, bound)
     return err, e_b, e32
 
@@ -449,12 +450,19 @@ def check_hs_bf16(what, got, x_in, p_next, frames):
         a, b, c32 = own(g_, frames), own(ref, frames), own(ref32, frames)
         if b.size == 0:
             continue
-        e32 = rel_l2(c32, b)                                                             # fp32 on the CPU against float64 (unrounded transforms)
-        allow = max(4 * e32, 2e-6) * float(np.linalg.norm(b))
-        excess = np.abs(a - b) - (2.0 ** -8 * np.abs(b) + allow)
-        worst = max(worst, float(np.max(np.abs(a - b) / (2.0 ** -8 * np.abs(b) + allow))))
-        assert (excess <= 0).all(), (what, br, int((excess > 0).sum()), float(excess.max()))
+        worst = max(worst, check_elems_bf16((what, br), a, b, c32))
     print("%s: hs_out worst |diff| / (2^-8 |ref| + allowance) %.3f" % (what, worst))
+    return worst
+
+
+def check_elems_bf16(what, a, b, c32):
+    """The element rule of check_hs_bf16 on flat arrays: a the bf16 values a kernel stored, b the unrounded float64 reference, c32
+    the same statement in fp32.  -> the worst |a - b| / (2^-8 |b| + allowance)."""
+    e32 = rel_l2(c32, b)                                                                 # fp32 on the CPU against float64 (unrounded)
+    allow = max(4 * e32, 2e-6) * float(np.linalg.norm(b))
+    excess = np.abs(a - b) - (2.0 ** -8 * np.abs(b) + allow)
+    worst = float(np.max(np.abs(a - b) / (2.0 ** -8 * np.abs(b) + allow)))
+    assert (excess <= 0).all(), (what, int((excess > 0).sum()), float(excess.max()))
     return worst
 
 
