@@ -270,20 +270,23 @@ def run_gconv(d, mem):
 
 def run_time(d, mem):
     B, NF = d.B, d.NF
-    t = mem.arr(d.t, B)
-    table = mem.arr(d.table, d.max_steps * 128).reshape(d.max_steps, 128)
+    f64 = lambda a: np.asarray(a, np.float64)   # noqa: E731  (a folded bias is one cancelling sum of 512 products: no fp32 noise of the emulator's own on it)
+    t = f64(mem.arr(d.t, B))
+    table = f64(mem.arr(d.table, d.max_steps * 128).reshape(d.max_steps, 128))
     lo = np.clip(np.floor(t).astype(int), 0, d.max_steps - 1)
     hi = np.clip(np.ceil(t).astype(int), 0, d.max_steps - 1)
     x = table[lo] + (table[hi] - table[lo]) * (t - np.floor(t))[:, None]
-    p1T = mem.arr(d.p1T, 128 * 512).reshape(128, 512)
-    p2T = mem.arr(d.p2T, 512 * 512).reshape(512, 512)
+    p1T = f64(mem.arr(d.p1T, 128 * 512).reshape(128, 512))
+    p2T = f64(mem.arr(d.p2T, 512 * 512).reshape(512, 512))
     y = x @ p1T + mem.arr(d.b1, 512)
     y = y * _sig(y)
     y = y @ p2T + mem.arr(d.b2, 512)
-    y = (y * _sig(y)).astype(np.float32)
+    y = y * _sig(y)
     if d.temb:
         mem.arr(d.temb, B * 512)[:] = y.reshape(-1)
-    wfT = mem.arr(d.wfT, 512 * NF).reshape(512, NF)
+    if NF == 0:                                        # the embedding alone: no folded biases, wfT / bf may be null
+        return
+    wfT = f64(mem.arr(d.wfT, 512 * NF).reshape(512, NF))
     mem.arr(d.out, B * NF)[:] = (y @ wfT + mem.arr(d.bf, NF)).astype(np.float32).reshape(-1)
 
 
@@ -324,29 +327,62 @@ def run_compand(d, mem):
 
 
 def run_wavprep(d, mem):
+    """pdse_wavprep_desc.  lens: the RMS runs over an utterance's own samples (clamped to [1, L]); reflect_own with lens: the
+    reflection sits at the utterance's own end (at least pad + 1 samples), zeros behind the reflected tail."""
     x = mem.arr(d.wav, d.B * d.L).reshape(d.B, d.L)
-    lens = mem.arr(d.lens, d.B, np.int32).astype(np.float32) if d.lens else np.full(d.B, d.L, np.float32)
-    c = np.sqrt((x.astype(np.float32) ** 2).sum(1) / lens) if d.normalize else np.ones(d.B, np.float32)
+    lens = np.clip(mem.arr(d.lens, d.B, np.int32), 1, d.L) if d.lens else np.full(d.B, d.L, np.int64)
+    c = np.ones(d.B, np.float32)
+    if d.normalize:
+        c = np.array([np.sqrt((x[b, :n].astype(np.float32) ** 2).sum() / np.float32(n)) for b, n in enumerate(lens)], np.float32)
     if d.c:
         mem.arr(d.c, d.B)[:] = c
-    xp = np.pad(x / c[:, None], ((0, 0), (d.pad, d.pad)), mode="reflect")
-    mem.arr(d.xpad, d.B * (d.L + 2 * d.pad))[:] = xp.astype(np.float32).reshape(-1)
+    Lp = d.L + 2 * d.pad
+    xp = np.zeros((d.B, Lp), np.float32)
+    for b in range(d.B):
+        n = int(np.clip(mem.arr(d.lens, d.B, np.int32)[b], d.pad + 1, d.L)) if (d.reflect_own and d.lens) else d.L
+        xp[b, :n + 2 * d.pad] = np.pad(x[b, :n] / c[b], (d.pad, d.pad), mode="reflect")
+    mem.arr(d.xpad, d.B * Lp)[:] = xp.reshape(-1)
 
 
 def run_ola(d, mem):
+    """pdse_ola_desc.  nframes: utterance b owns its first nframes[b] frames (clamped to [0, T]; the others are not read);
+    lens: zeros from sample lens[b] on."""
     fr = mem.arr(d.frames, d.B * d.n_fft * d.T).reshape(d.B, d.n_fft, d.T)
     w2 = mem.arr(d.win2, d.n_fft)
     full = d.n_fft + d.hop * (d.T - 1)
-    y = np.zeros((d.B, max(full, d.n_fft // 2 + d.L)), np.float32)
-    env = np.zeros(y.shape[1], np.float32)
-    for t in range(d.T):
-        y[:, t * d.hop:t * d.hop + d.n_fft] += fr[:, :, t]
-        env[t * d.hop:t * d.hop + d.n_fft] += w2
+    n = max(full, d.n_fft // 2 + d.L)
     h = d.n_fft // 2
-    out = np.where(env[h:h + d.L] > 1e-11, y[:, h:h + d.L] / np.maximum(env[h:h + d.L], 1e-30), 0)
-    if d.c:
-        out = out * mem.arr(d.c, d.B)[:, None]
-    mem.arr(d.out, d.B * d.L)[:] = out.astype(np.float32).reshape(-1)
+    out = np.zeros((d.B, d.L), np.float32)
+    for b in range(d.B):
+        Tb = int(np.clip(mem.arr(d.nframes, d.B, np.int32)[b], 0, d.T)) if d.nframes else d.T
+        y, env = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        for t in range(Tb):
+            y[t * d.hop:t * d.hop + d.n_fft] += fr[b, :, t]
+            env[t * d.hop:t * d.hop + d.n_fft] += w2
+        v = np.where(env[h:h + d.L] > 1e-11, y[h:h + d.L] / np.maximum(env[h:h + d.L], 1e-30), 0)
+        if d.c:
+            v = v * mem.arr(d.c, d.B)[b]
+        if d.lens:
+            v[int(np.clip(mem.arr(d.lens, d.B, np.int32)[b], 0, d.L)):] = 0
+        out[b] = v
+    mem.arr(d.out, d.B * d.L)[:] = out.reshape(-1)
+
+
+def run_maskloss(d, mem):
+    """pdse_maskloss_desc: fp32 differences squared and added in double; partial [B][MASKLOSS_BLOCKS] as the launch's workgroups
+    own the elements (workgroup x of utterance b: elements i of every channel's live part with (i / 256) % blocks == x)."""
+    B, C_, T, F = d.B, d.C, d.T, d.F
+    nb = L.MASKLOSS_BLOCKS
+    fr = np.clip(mem.arr(d.frames, B, np.int32), 0, T)
+    esti = mem.arr(d.esti, B * C_ * T * F).reshape(B, C_, T * F)
+    label = mem.arr(d.label, B * C_ * T * F).reshape(B, C_, T * F)
+    partial = mem.arr(d.partial, B * nb, np.float64).reshape(B, nb)
+    for b in range(B):
+        live = int(fr[b]) * F
+        e = (esti[b, :, :live] - label[b, :, :live]).astype(np.float32).astype(np.float64) ** 2
+        owner = (np.arange(live) // 256) % nb
+        partial[b] = [e[:, owner == x].sum() for x in range(nb)]
+    mem.arr(d.out, 1)[:] = np.float32(partial.sum() / (float(fr.sum()) * C_ * F))
 
 
 def run_sigma(d, mem):
@@ -633,7 +669,8 @@ def run_gcrnlast(d, mem):
     y = (pre[0] + d.b1) * _sig(pre[1] + d.b2)
     y = y * d.bn_scale + d.bn_shift
     y = np.where(y > 0, y, np.expm1(np.minimum(y, 0)))
-    fcT = mem.arr(d.fcT, 161 * 161).reshape(161, 161).astype(np.float64)
+    # the kernel reads the packed matrix alone (fcp: packing.pack_a4, six 32-bin tiles, K = 161 padded to 168), never d.fcT
+    fcT = P.unpack_a4(mem.arr(d.fcp, 6 * 21 * 64 * 4), 6, 84)[:161, :161].astype(np.float64)
     res = (y @ fcT + mem.arr(d.fcb, 161)).astype(np.float32)                                     # [B,T,161]
     flat, off = mem.view(d.out)
     idx = off + np.arange(B)[:, None, None] * d.out_sb + np.arange(T)[None, :, None] * 161 + np.arange(161)[None, None, :]
@@ -819,7 +856,7 @@ def run_tcm2s(d, mem):
 
 
 RUNNERS = {L.Tcm2sDesc: run_tcm2s, L.BgluDesc: run_bglu, L.PlanesDesc: run_planes, L.GcrnLastDesc: run_gcrnlast, L.TcmDesc: run_tcm, L.Tcm2Desc: run_tcm2, L.GconvDesc: run_gconv, L.TimeDesc: run_time, L.EwDesc: run_ew, L.CompandDesc: run_compand,
-           L.WavprepDesc: run_wavprep, L.OlaDesc: run_ola, L.SigmaDesc: run_sigma, L.LnDesc: run_ln,
+           L.WavprepDesc: run_wavprep, L.OlaDesc: run_ola, L.MasklossDesc: run_maskloss, L.SigmaDesc: run_sigma, L.LnDesc: run_ln,
            L.LstmDesc: run_lstm, L.GlstmDesc: run_glstm, L.GlstmpDesc: run_glstmp}
 
 
